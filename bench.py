@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: env-steps/s of the fused VSS-v0 3v3 step at 4096 envs per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode step|rollout] [--envs B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode step|rollout] [--envs B] [--full] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 starts its own N ranks (one process per GPU, `torch.distributed.run` on
 127.0.0.1) when it is not already running under torchrun; the torchrun form works as well:
@@ -17,8 +17,10 @@ reported).  All inputs are resident in HBM before the timed region.  With N > 1 
 envs [rank*B, (rank+1)*B) (weak scaling, no data-path collective); a 64-byte metrics vector is
 all-reduced over RCCL every 100 steps (a ~20 us stream-ordered collective).
 
-Prints ONE JSON line on rank 0 (see the driver contract).  Besides the contract's keys:
-  roofline      dominant kernel of the timed leg, HIP-event launch average, algorithmic bytes
+Prints ONE JSON line on rank 0 (see the driver contract).  A plain run sets up, warms up, times the K steps and prints
+the line; besides the contract's keys it holds
+  roofline      dominant kernel of the timed leg, launch average, algorithmic bytes
+`--full` adds the legs that take runs of their own (`--no-cpu-baseline`, `--no-rollout`, `--no-extra` drop some again):
   steady        the same per-step launches over >= 2000 steps after >= 200,
                 whatever --steps / --warmup were
   rollout       the same K steps inside ONE launch
@@ -32,6 +34,12 @@ Prints ONE JSON line on rank 0 (see the driver contract).  Besides the contract'
   cpu_baseline  (N = 1) the CPU oracle on this box's host cores, bounded sample
   evidence      (N = 1, LAST key) compact digest of the large-batch legs: [us per step, nominal roofline fraction,
                 counter traffic / time over 6.29 TB/s] per leg, configs[2] / configs[3] step times, the policy-loop rates
+
+`--dump-outputs DIR` writes what the timed leg's last step computed, as a caller of the fused step receives it, to
+DIR/<name>.npy (float32): obs, reward, terminated, truncated, info, final_obs, actions, steps, state.  The inputs are
+fixed (seed 0, env ids from rank * B), so two builds run with the same flags can be compared array for array.
+Outputs above 64 MB are written for a fixed, seeded sample of the envs (DIR/env_index.npy lists them).
+With N > 1 rank r > 0 writes DIR/<name>_rank<r>.npy.
 """
 import argparse
 import json
@@ -54,6 +62,7 @@ LARGE_WARMUP = 200             # untimed steps before the large-batch legs of th
 EVENT_MIN_STEPS = 200           # shorter timed regions are measured by the wall clock alone (see timed())
 SWEEP_ENVS = (65536, 1048576, 4194304)
 HBM_ACHIEVABLE_GBS = 6290.0     # MI355X_MICROARCH.md: what a streaming kernel reaches of the 8 TB/s
+DUMP_MAX_BYTES = 64 << 20       # --dump-outputs: larger outputs are written for a fixed, seeded sample of the envs
 
 
 def usable_cores():
@@ -234,6 +243,32 @@ def efficiency_vs_n1(value, world):
     return {"efficiency_vs_n1": value / (world * n1), "n1_value": n1, "n1_source": "RSX_BENCH_N1_VALUE"}
 
 
+def dump_outputs(sim, out_dir, rank):
+    """--dump-outputs: the task tensors and the state after the last timed step, [envs, ...] float32 each (flags and counters
+    converted exactly); above DUMP_MAX_BYTES, the same fixed, seeded sample of envs for every array"""
+    import numpy as np
+    import torch
+    t = sim.task_tensors()
+    arrays = {"obs": t["obs"], "reward": t["reward"], "terminated": t["terminated"], "truncated": t["truncated"],
+              "info": t["info"].t(), "final_obs": t["final_obs"], "actions": t["actions"], "steps": t["steps"],
+              "state": sim.state_tensor().t()}
+    B = sim.num_envs
+    per_env = sum(4 * (a[0].numel() if a.dim() > 1 else 1) for a in arrays.values())
+    idx = None
+    if per_env * B > DUMP_MAX_BYTES:
+        n = DUMP_MAX_BYTES // per_env
+        idx = np.sort(np.random.default_rng(0).choice(B, n, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+    sel = None if idx is None else torch.from_numpy(idx).to(t["obs"].device)
+    for name, a in arrays.items():
+        if sel is not None:
+            a = a.index_select(0, sel)
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), a.to(torch.float32).cpu().numpy())
+    if idx is not None:
+        np.save(os.path.join(out_dir, f"env_index{sfx}.npy"), idx.astype(np.float64))
+
+
 def dry_run(args, rank, world):
     """Launcher / collective plumbing without a GPU (CPU test of `--gpus N`): the ranks shard the env ids, set up
     the metrics collective exactly like a real run (RCCL cannot come up without a device, so this exercises the
@@ -270,9 +305,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2000)
     ap.add_argument("--envs", type=int, default=4096, help="envs per GPU")
     ap.add_argument("--mode", choices=["step", "rollout"], default="step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-rollout", action="store_true", help="skip the extra one-launch rollout leg")
-    ap.add_argument("--no-extra", action="store_true", help="skip the steady / sweep / python_layer legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs beyond the timed one: steady, rollout, sweep, configs, python_layer, cpu_baseline, evidence")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU oracle leg")
+    ap.add_argument("--no-rollout", action="store_true", help="(--full) skip the extra one-launch rollout leg")
+    ap.add_argument("--no-extra", action="store_true", help="(--full) skip the steady / sweep / python_layer legs")
     ap.add_argument("--dry-run", action="store_true", help="launcher + collective plumbing only (no GPU)")
     ap.add_argument("--simulate-rccl-failure", default=None, metavar="all|RANK",
                     help="make the RCCL probe fail (on every rank, or on one): tests the degraded mode (metrics over gloo)")
@@ -394,11 +433,13 @@ def main():
         per_rank_ms = [float(x) for x in g.cpu()]
         tags = [None] * world
         torch.distributed.all_gather_object(tags, dev_tag, group=coll.ctl)
-    extra = not args.no_extra and args.mode == "step"
+    if args.dump_outputs:   # before any further leg steps the same handle
+        dump_outputs(sim, args.dump_outputs, rank)
+    extra = args.full and not args.no_extra and args.mode == "step"
     steady = None
     if extra and (K < STEADY_STEPS or W < STEADY_WARMUP):
         steady = timed(sim, STEADY_STEPS, max(0, STEADY_WARMUP - (W + K)), "step")
-    roll = timed(sim, K, W, "rollout") if args.mode == "step" and not args.no_rollout else None
+    roll = timed(sim, K, W, "rollout") if args.full and args.mode == "step" and not args.no_rollout else None
 
     metrics = sim.read_metrics()
     if distributed:
@@ -489,7 +530,7 @@ def main():
                               "after_steps": max(W + K, STEADY_WARMUP), "us_per_step": sd * 1e3 / STEADY_STEPS,
                               "roofline_frac": roofline_of(B, sd * 1e3 / STEADY_STEPS, B, "step")["frac"],
                               "note": "same per-step launches as `value`, SURVEY.md 8(d) config 2 sample size"}
-        elif args.mode == "step":
+        elif args.mode == "step" and args.full:
             line["steady"] = {"value": value, "unit": "env-steps/s", "steps": K, "after_steps": W,
                               "us_per_step": launch_us, "roofline_frac": line["roofline"]["frac"],
                               "note": "the timed leg itself meets SURVEY.md 8(d) config 2 (>= 2000 steps after >= 200)"}
@@ -507,7 +548,7 @@ def main():
         line["sweep"] = sweep(L, torch, dev, timed)
         line["configs"] = other_configs(L, torch, dev, timed)
         line["python_layer"] = python_layer(torch, dev)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(B)
     if rank == 0 and world == 1 and extra:
         line["evidence"] = evidence(line)   # LAST key: the driver keeps the tail of stdout

@@ -73,7 +73,7 @@ def _single_handle_metrics(total_envs, steps, warmup):
 
 @pytest.mark.gpu
 def test_bench_line_single_gpu_has_every_leg():
-    res, line = _run(["--steps", "20", "--warmup", "5", "--no-cpu-baseline"])
+    res, line = _run(["--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--full"])
     assert res.returncode == 0, res.stdout + res.stderr
     assert line["n_gpus"] == 1 and line["steps"] == 20 and line["warmup"] == 5
     assert line["env_steps_counted"] >= 4096 * 25          # counted on the device
@@ -88,6 +88,34 @@ def test_bench_line_single_gpu_has_every_leg():
             assert 0 < p["step"]["roofline_frac"] < 1 and 0 < p["rollout"]["roofline_frac"] < 1
     assert line["python_layer"]["vec_api_calls_per_s"] > 1000
     assert line["python_layer"]["single_env_steps_per_s"] > 100
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_only_its_steps_and_dumps_repeatable_outputs(tmp_path):
+    """a plain run steps the handle exactly W + K times (no further legs), and --dump-outputs writes the last timed step's
+    outputs as float32 arrays that a second run with the same flags reproduces bit for bit"""
+    B, K, W = 4096, 60, 15
+    lines, dumps = [], []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        res, line = _run(["--steps", str(K), "--warmup", str(W), "--dump-outputs", str(d)])
+        assert res.returncode == 0, res.stdout + res.stderr
+        lines.append(line)
+        dumps.append({f.stem: np.load(f) for f in sorted(d.glob("*.npy"))})
+    line = lines[0]
+    assert line["steps"] == K and line["warmup"] == W and line["ms_per_step"] > 0
+    assert abs(line["value"] - B * K / (line["ms_per_step"] * 1e-3 * K)) < 1e-6 * line["value"]
+    assert line["env_steps_counted"] == B * (K + W)
+    for leg in ("steady", "rollout", "sweep", "configs", "python_layer", "cpu_baseline", "evidence"):
+        assert leg not in line, leg
+    a, b = dumps
+    assert set(a) == {"obs", "reward", "terminated", "truncated", "info", "final_obs", "actions", "steps", "state"}
+    assert a["obs"].shape[0] == B and a["reward"].shape == (B,) and a["state"].shape[0] == B
+    for name in a:
+        assert a[name].dtype == np.float32, name
+        assert np.array_equal(a[name], b[name], equal_nan=True), name
+    m = _single_handle_metrics(B, K, W)
+    assert line["episodes"] == int(m[1])
 
 
 @pytest.mark.gpu

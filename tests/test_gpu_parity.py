@@ -539,7 +539,7 @@ def test_vss_v0_on_the_5v5_field_uses_16_lane_groups(oracle_mod):
     sim.close()
 
 
-def test_one_wavefront_per_env_layout_gives_identical_results():
+def test_one_wavefront_per_env_layout_gives_identical_results(tmp_path):
     """RSX_LANES_PER_ENV=64 selects the 'one wavefront per env' mapping of BASELINE.json's north
     star; results must not depend on the mapping (run in a subprocess: the variable is read at
     handle creation)."""
@@ -561,7 +561,7 @@ def test_one_wavefront_per_env_layout_gives_identical_results():
         env.pop("RSX_LANES_PER_ENV", None)
         if lanes:
             env["RSX_LANES_PER_ENV"] = lanes
-        path = "/tmp/rsx_lanes_%s.npy" % (lanes or "default")
+        path = str(tmp_path / ("rsx_lanes_%s.npy" % (lanes or "default")))
         subprocess.check_call([sys.executable, "-c", code, path], env=env)
         res.append(np.load(path))
     assert np.array_equal(res[0], res[1])

@@ -1,14 +1,22 @@
-"""The Python host layer against THE REFERENCE ITSELF, live, over random episodes — in the build container only.
+"""The Python host layer against THE REFERENCE ITSELF over random episodes.
 
 tests/golden/ pins this project's restatement of the reference's Python-side arithmetic (commands, observations, rewards, done, info,
-placement, OU noise) to vectors recorded from scripted episodes.  Where /root/reference is present (the build container; it does
-not exist on the GPU box, where this test skips) the same comparison can be made LIVE and on trajectories nobody scripted: a child
-process imports the reference's own env classes (rsoccer_gym/vss/env_vss/vss_gym.py:13, rsoccer_gym/ssl/ssl_hw_challenge/*.py) and
-this project's classes of the same names, gives BOTH the same simulator — tests/fake_robosim.py, the float64 oracle behind the
-`robosim` surface (rsoccer_gym/Simulators/rsim.py:2) — seeds the global `random` / `numpy.random` streams the reference draws from
-(vss_gym.py:194-233, Utils/Utils.py:5-29) identically, feeds both the same random actions and requires every observation, reward,
-flag and info value of every step to be EQUAL (float equality, no tolerance), across resets.  Nothing of the reference is copied or
-committed: it is imported from where it lies, and only here.
+placement, OU noise) to vectors recorded from scripted episodes.  This test makes the same comparison on trajectories nobody scripted:
+a child process drives this project's env classes and the reference's own (rsoccer_gym/vss/env_vss/vss_gym.py:13,
+rsoccer_gym/ssl/ssl_hw_challenge/*.py) through the same simulator — tests/fake_robosim.py, the float64 oracle behind the `robosim`
+surface (rsoccer_gym/Simulators/rsim.py:2) — with the global `random` / `numpy.random` streams the reference draws from
+(vss_gym.py:194-233, Utils/Utils.py:5-29) seeded identically and the same random actions, and requires every observation, reward,
+flag and info value of every step, and every command / state that crossed the `robosim` boundary, to be EQUAL (no tolerance),
+across resets.
+
+The reference's side of the test episodes is recorded in tests/golden/reference_live_digests.npz: one 16-byte digest per record
+of what the reference returned and of what crossed its simulator boundary, so the test needs nothing outside the repository.
+With a reference tree at hand the comparison runs live as well, and the digests are recorded from it:
+
+    python tests/test_reference_live.py REFERENCE_DIR --record     # live on the test's episodes, rewrites the digests
+    python tests/test_reference_live.py REFERENCE_DIR [STEPS]      # live soak on ten more seeds
+
+Nothing of the reference is copied or committed: it is imported from where it lies, and only in those two commands.
 """
 import json
 import os
@@ -21,10 +29,9 @@ import gymnasium_stub
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-REF = "/root/reference"
 
 CHILD = r'''
-import importlib, json, random, sys
+import hashlib, importlib, json, random, sys
 import numpy as np
 import fake_robosim
 
@@ -188,34 +195,96 @@ def same(a, b, where):
     assert np.array_equal(a[6], b[6])
 
 
+def _plain(v):
+    """JSON-able copy of an info value: floats as floats (-0.0 as 0.0), arrays as lists"""
+    if isinstance(v, dict):
+        return {str(k): _plain(u) for k, u in v.items()}
+    if hasattr(v, "tolist"):
+        v = v.tolist()
+    if isinstance(v, (list, tuple)):
+        return [_plain(u) for u in v]
+    if isinstance(v, float):
+        return v + 0.0
+    return v
+
+
+def _canon(x):
+    """bytes that are equal exactly when two records are equal value for value (as `same` compares them; -0.0 == 0.0)"""
+    if isinstance(x, np.ndarray):
+        a = x + x.dtype.type(0) if x.dtype.kind == "f" else x
+        return b"A" + a.dtype.str.encode() + repr(a.shape).encode() + np.ascontiguousarray(a).tobytes()
+    if isinstance(x, dict):
+        return b"D" + json.dumps(_plain(x), sort_keys=True).encode()
+    if isinstance(x, (bool, np.bool_)):
+        return b"B" + (b"1" if x else b"0")
+    if isinstance(x, (float, np.floating)):
+        return b"F" + repr(float(x) + 0.0).encode()
+    return b"S" + repr(x).encode()
+
+
+def digests(trace, simlog):
+    """[records, 2, 16] uint8: a digest of each record the env returned and of each record that crossed the robosim boundary"""
+    assert len(trace) == len(simlog)
+    out = np.zeros((len(trace), 2, 16), dtype=np.uint8)
+    for i, (tr, sl) in enumerate(zip(trace, simlog)):
+        for j, rec in enumerate((tr, sl)):
+            h = hashlib.blake2b(digest_size=16)
+            for x in rec:
+                c = _canon(x)
+                h.update(len(c).to_bytes(8, "little") + c)
+            out[i, j] = np.frombuffer(h.digest(), dtype=np.uint8)
+    return out
+
+
 out = {}
 worst = {}
-n_steps, seeds = int(sys.argv[1]), [int(s) for s in sys.argv[2].split(",")]
+n_steps, seeds, mode, golden_path = int(sys.argv[1]), [int(s) for s in sys.argv[2].split(",")], sys.argv[3], sys.argv[4]
+golden = dict(np.load(golden_path)) if mode == "check" else {}
 for env_id, (mod, cls, ad) in TASKS.items():
     total = ended = rewarded = 0
     for seed in seeds:
-        ref, ep, simlog = rollout("rsoccer_gym", mod, cls, ad, seed, n_steps, {})
+        key = f"{env_id}__{seed}"
+        if mode != "check":   # live: the reference itself plays the same episodes, and its records become the golden digests
+            ref, ep, simlog = rollout("rsoccer_gym", mod, cls, ad, seed, n_steps, {})
         mine, ep2, simlog2 = rollout("rsoccer_amd", mod, cls, ad, seed, n_steps, dict(sim_backend=fake_robosim))
-        assert len(ref) == len(mine) and ep == ep2, (env_id, seed, len(ref), len(mine))
-        for i, (a, b) in enumerate(zip(ref, mine)):
-            same(a, b, f"{env_id} seed {seed} record {i}")
-        for i, (a, b) in enumerate(zip(simlog, simlog2)):     # ... and the same traffic crossed the robosim boundary (commands, placements)
-            assert a[0] == b[0] and all(np.array_equal(x, y) for x, y in zip(a[1:], b[1:])), (env_id, seed, "boundary record", i)
+        if mode != "check":
+            assert len(ref) == len(mine) and ep == ep2, (env_id, seed, len(ref), len(mine))
+            for i, (a, b) in enumerate(zip(ref, mine)):
+                same(a, b, f"{env_id} seed {seed} record {i}")
+            for i, (a, b) in enumerate(zip(simlog, simlog2)):     # ... and the same traffic crossed the robosim boundary (commands, placements)
+                assert a[0] == b[0] and all(np.array_equal(x, y) for x, y in zip(a[1:], b[1:])), (env_id, seed, "boundary record", i)
+            golden[key] = digests(ref, simlog)
+            golden[key + "__episodes"] = np.array([ep], dtype=np.int64)
+        want, got = golden[key], digests(mine, simlog2)
+        assert int(golden[key + "__episodes"][0]) == ep2 and want.shape == got.shape, (env_id, seed, "records", want.shape, got.shape)
+        diff = np.nonzero((want != got).any(axis=2))
+        if len(diff[0]):
+            i, j = int(diff[0][0]), int(diff[1][0])
+            raise AssertionError(f"{env_id} seed {seed}: {len(diff[0])} records differ from the reference's; the first is record {i}, "
+                                 f"{('what the env returned', 'what crossed the robosim boundary')[j]}: {(mine, simlog2)[j][i]!r}")
         task = list(TASKS).index(env_id) + 1
         for prec in ("f64", "f32"):
-            w = replay_through_the_oracle(task, ref, simlog, prec)
+            w = replay_through_the_oracle(task, mine, simlog2, prec)
             for k, v in w.items():
                 worst[(env_id, prec, k)] = max(worst.get((env_id, prec, k), 0.0), v)
-        total += sum(1 for r in ref if r[0] == "step")
-        ended += sum(1 for r in ref if r[0] == "step" and (r[3] or r[4]))
-        rewarded += sum(1 for r in ref if r[0] == "step" and r[2] != 0.0)
+        total += sum(1 for r in mine if r[0] == "step")
+        ended += sum(1 for r in mine if r[0] == "step" and (r[3] or r[4]))
+        rewarded += sum(1 for r in mine if r[0] == "step" and r[2] != 0.0)
     out[env_id] = [total, ended, rewarded]
 out["worst"] = {" ".join(k): v for k, v in worst.items()}
+if mode == "record":
+    np.savez_compressed(golden_path, n_steps=np.array([n_steps]), seeds=np.array(seeds), **golden)
 print("REFERENCE_LIVE_OK", json.dumps(out))
 '''
 
 
-def _run(tmp_path, n_steps, seeds):
+GOLDEN = os.path.join(HERE, "golden", "reference_live_digests.npz")
+N_STEPS, SEEDS = 700, (3, 14, 159)
+
+
+def _run(tmp_path, n_steps, seeds, mode="check", ref=None):
+    """mode "check": this project's side against the recorded digests; "live": against the reference at `ref` as well;
+    "record": live, and the reference's digests are written to GOLDEN"""
     stub_root = gymnasium_stub.write(str(tmp_path / "site"))
     os.makedirs(os.path.join(stub_root, "pygame"), exist_ok=True)          # the reference's renderer imports it (rsoccer_gym/Render)
     open(os.path.join(stub_root, "pygame", "__init__.py"), "w").close()
@@ -223,23 +292,26 @@ def _run(tmp_path, n_steps, seeds):
     with open(os.path.join(stub_root, "robosim", "__init__.py"), "w") as f:
         f.write("from fake_robosim import VSS, SSL\n")
     env = dict(os.environ)
-    env["PYTHONPATH"] = os.pathsep.join([stub_root, REF, ROOT, HERE] + ([env["PYTHONPATH"]] if env.get("PYTHONPATH") else []))
-    r = subprocess.run([sys.executable, "-c", CHILD, str(n_steps), ",".join(str(s) for s in seeds)], env=env, capture_output=True, text=True,
-                       timeout=1500)
+    env["PYTHONPATH"] = os.pathsep.join([stub_root] + ([ref] if ref else []) + [ROOT, HERE]
+                                        + ([env["PYTHONPATH"]] if env.get("PYTHONPATH") else []))
+    r = subprocess.run([sys.executable, "-c", CHILD, str(n_steps), ",".join(str(s) for s in seeds), mode, GOLDEN if mode != "live" else ""],
+                       env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-6000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("REFERENCE_LIVE_OK")]
     assert line, r.stdout[-2000:]
     return json.loads(line[0].split(" ", 1)[1])
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "rsoccer_gym")), reason="the reference tree is only present in the build container")
 def test_host_layer_equals_the_reference_on_random_episodes(tmp_path, oracle_mod):
-    res = _run(tmp_path, 700, (3, 14, 159))
+    import numpy as np
+    g = np.load(GOLDEN)
+    assert int(g["n_steps"][0]) == N_STEPS and tuple(int(x) for x in g["seeds"]) == SEEDS   # the digests are of these episodes
+    res = _run(tmp_path, N_STEPS, SEEDS)
     worst = res.pop("worst")
     assert set(res) == {"VSS-v0", "SSLStaticDefenders-v0", "SSLDribbling-v0", "SSLContestedPossession-v0", "SSLPassEndurance-v0"}
     assert len(worst) == 5 * 2 * 4    # the oracle's task arithmetic was replayed in both precisions (obs / reward / info / cmds)
     for env_id, (steps, ended, rewarded) in res.items():
-        assert steps == 3 * 700 and rewarded > 0, (env_id, steps, rewarded)
+        assert steps == len(SEEDS) * N_STEPS and rewarded > 0, (env_id, steps, rewarded)
     # the short-episode tasks did end episodes on their own (terminal branches were compared, not only shaping terms)
     assert res["SSLStaticDefenders-v0"][1] > 0 and res["SSLContestedPossession-v0"][1] > 0 and res["SSLPassEndurance-v0"][1] > 0, res
 
@@ -247,5 +319,9 @@ def test_host_layer_equals_the_reference_on_random_episodes(tmp_path, oracle_mod
 if __name__ == "__main__":
     import pathlib
     import tempfile
+    ref = os.path.abspath(sys.argv[1])
     with tempfile.TemporaryDirectory() as d:
-        print(_run(pathlib.Path(d), int(sys.argv[1]) if len(sys.argv) > 1 else 3000, tuple(range(20, 30))))
+        if sys.argv[2:3] == ["--record"]:
+            print(_run(pathlib.Path(d), N_STEPS, SEEDS, "record", ref))
+        else:
+            print(_run(pathlib.Path(d), int(sys.argv[2]) if len(sys.argv) > 2 else 3000, tuple(range(20, 30)), "live", ref))

@@ -6,10 +6,10 @@ TAG=${1:-r02}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 tail -1 $OUT/bench.json | cut -c1-400
 # kernel trace + stats of the bench command (step mode only, no CPU leg)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python bench.py --no-cpu-baseline --no-rollout > $OUT/stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python bench.py --full --no-cpu-baseline --no-rollout > $OUT/stats.log 2>&1
 find $OUT/stats -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/bench_kernel_stats_pooled.csv
 # the same trace grouped by (kernel, grid size): the 4096-env launches of the headline kernel get their own row
 python tools/kernel_stats_by_grid.py $OUT/stats $OUT/bench_kernel_stats_by_grid.csv && cp $OUT/bench_kernel_stats_by_grid.csv $OUT/bench_kernel_stats.csv
@@ -29,7 +29,7 @@ tools/prof_leg_traffic.sh $OUT > $OUT/leg_traffic.log 2>&1
 python tools/bench_configs.py $OUT/configs_and_sweep.md > $OUT/configs.log 2>&1
 cat $OUT/configs_and_sweep.md
 # the driver's own flags
-python bench.py --steps 20 --warmup 5 > $OUT/bench_driver_flags.json 2> $OUT/bench_driver_flags.err
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_flags.json 2> $OUT/bench_driver_flags.err
 # one-lane-per-env kernel at 1 M envs: SQ + HBM counters
 tools/prof_epl.sh $OUT/epl > $OUT/epl.log 2>&1
 cat $OUT/epl/*.txt > $OUT/epl_counters_1M.txt
