@@ -346,6 +346,8 @@ int rsx_check_finite(rsx_sim* h, int64_t* n_bad, void* stream);
  * sizes, batch size and attached with the same task, seed and env_id_base makes every following step bit-identical
  * to what the saving handle would have produced — across kernel layouts (RSX_LAYOUT) and processes.  Host blob,
  * both calls synchronise `stream`. */
+/* Handles switched by rsx_physics_enable: the blob also holds the parameter rows, the coefficient rows and the
+ * randomisation ranges, and it loads only into another such handle (a blob of the other kind: RSX_ERR_ARG). */
 int rsx_task_checkpoint_size(rsx_sim* h, size_t* bytes);
 int rsx_task_checkpoint_save(rsx_sim* h, void* blob, size_t bytes, void* stream);
 int rsx_task_checkpoint_load(rsx_sim* h, const void* blob, size_t bytes, void* stream);
@@ -360,6 +362,60 @@ int rsx_read_metrics(rsx_sim* h, int64_t out[RSX_METRICS], void* stream);
  * metrics[1..6].  (Atomics of a whole grid on one cache line serialise: at 10^6 envs they, not the
  * physics, set the step time.)  rsx_read_metrics does it itself. */
 int rsx_metrics_fold(rsx_sim* h, void* stream);
+
+/* ---- per-env physics parameters / domain randomisation (additive extension of ABI 6) ---------------------------
+ * By default every env steps with the model constants of docs/PHYSICS.md section 3, compiled into the kernels.  A handle
+ * switched by rsx_physics_enable carries one float32 value per env of each parameter below instead, and steps with kernels
+ * that read them (always the lane-group layouts, "<L>-lanes-per-env" in rsx_task_layout, at any batch size; a handle
+ * forced to RSX_LANES_PER_ENV=64 is refused).  Units and defaults are those of docs/PHYSICS.md section 3.
+ * Valid values: masses > 0, restitutions in [0, 1], friction coefficients, rolling deceleration, spin deceleration and
+ * acceleration limits >= 0, all finite; RSX_PHYS_A_LAT is a VSS parameter and stays 0 for the SSL class.
+ * Values are rows [RSX_PHYS_PARAMS][num_envs].  The kernels use derived coefficients ([RSX_PHYS_COEFS][num_envs]: shares of
+ * the impulse, 1 + e, per-sub-step velocity changes), computed in double and rounded to float by the same expressions as
+ * the compiled-in constants; a value equal to the float32 rounding of its default stands for the exact default, so a
+ * handle at its defaults steps bit for bit like one that never called rsx_physics_enable. */
+#define RSX_PHYS_PARAMS   14
+#define RSX_PHYS_M_ROBOT   0 /* kg */
+#define RSX_PHYS_M_BALL    1 /* kg */
+#define RSX_PHYS_E_RR      2 /* restitution robot - robot */
+#define RSX_PHYS_E_RB      3 /* restitution robot - ball */
+#define RSX_PHYS_E_WB      4 /* restitution wall - ball */
+#define RSX_PHYS_E_WR      5 /* restitution wall - robot */
+#define RSX_PHYS_MU_RR     6 /* Coulomb friction robot - robot */
+#define RSX_PHYS_MU_RB     7 /* Coulomb friction robot - ball */
+#define RSX_PHYS_MU_WB     8 /* Coulomb friction wall - ball */
+#define RSX_PHYS_MU_G      9 /* rolling deceleration of the ball on the ground, m/s^2 */
+#define RSX_PHYS_SPIN_DEC 10 /* spin deceleration of the ball, rad/s^2 */
+#define RSX_PHYS_A_LIN    11 /* linear acceleration limit of a robot, m/s^2 */
+#define RSX_PHYS_A_ANG    12 /* angular acceleration limit of a robot, rad/s^2 */
+#define RSX_PHYS_A_LAT    13 /* VSS: lateral grip, m/s^2 (SSL: 0) */
+#define RSX_PHYS_COEFS    18
+#define RSX_PHYS_RAW       0 /* rsx_physics_get: the parameter rows */
+#define RSX_PHYS_COEF      1 /* rsx_physics_get: the derived coefficient rows */
+/* The defaults of a robot class (no device needed). */
+int rsx_physics_defaults(int kind, float out[RSX_PHYS_PARAMS]);
+/* The coefficients the kernels derive from one parameter set (no device needed); RSX_ERR_ARG for an invalid set. */
+int rsx_physics_derive(int kind, int time_step_ms, const float raw[RSX_PHYS_PARAMS], float coef[RSX_PHYS_COEFS]);
+/* Switch the handle to per-env physics, every env at the defaults.  Before or after rsx_task_attach, but before
+ * rsx_task_enable_capture (RSX_ERR_STATE otherwise); synchronises `stream`.  Handles that never call it allocate nothing for it. */
+int rsx_physics_enable(rsx_sim* h, void* stream);
+/* values [RSX_PHYS_PARAMS][num_envs]: NaN = keep the env's current value; env_mask [num_envs] bytes or NULL = every env.
+ * on_device = 0: both are host memory, checked here (RSX_ERR_ARG, nothing changed, for an invalid value); synchronises
+ * `stream`.  on_device = 1:
+ * both are device memory and the write is one kernel launch (capturable); an env with an invalid value keeps all of its
+ * values and is counted in the handle's error word (rsx_physics_errors). */
+int rsx_physics_set(rsx_sim* h, const float* values, int on_device, const uint8_t* env_mask, void* stream);
+/* which = RSX_PHYS_RAW: out [RSX_PHYS_PARAMS][num_envs]; RSX_PHYS_COEF: out [RSX_PHYS_COEFS][num_envs].  Host memory;
+ * synchronises `stream`. */
+int rsx_physics_get(rsx_sim* h, int which, float* out, void* stream);
+/* Domain randomisation: from the next episode start on (rsx_task_reset, rsx_task_reset_to, same-step auto-reset), the
+ * parameters p of param_mask (bit p) are redrawn per env on the device as lo[p] + (hi[p] - lo[p]) * u01(x) in float32, x the
+ * first word of philox4x32(counter = (env_id_base + env, episode, p, 5), key = seed), u01(x) = (x >> 8) * 2^-24 — independent of
+ * batch size and sharding; the others keep their values.  param_mask = 0 switches it off.  lo / hi: host [RSX_PHYS_PARAMS]
+ * (bits outside param_mask are ignored); RSX_ERR_ARG when lo > hi or either bound is invalid.  Stream-ordered. */
+int rsx_physics_randomize(rsx_sim* h, const float* lo, const float* hi, uint32_t param_mask, void* stream);
+/* envs refused by device-side rsx_physics_set calls since the last read (read and cleared; synchronises `stream`). */
+int rsx_physics_errors(rsx_sim* h, int64_t* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -43,11 +43,22 @@ def make_vec(id, num_envs, **kwargs):
     """``num_envs`` copies of a registered task on one GPU — the batched counterpart of ``make(id)`` (the shape of
     ``gymnasium.make_vec(id, num_envs=...)``): the fused class of :mod:`rsoccer_amd.vec` for that id, with the registry's episode
     limit unless ``max_episode_steps`` says otherwise.  Further keywords go to the class: ``device``, ``seed``, ``env_id_base``
-    (global id of env 0: shards of one population over several GPUs), ``max_episode_steps``."""
+    (global id of env 0: shards of one population over several GPUs), ``max_episode_steps``, and ``physics`` /
+    ``physics_ranges`` (per-env physics parameters and their domain-randomisation ranges: ``VecFusedEnv.set_physics`` /
+    ``set_physics_randomization``)."""
     if id not in VECTOR_CLASSES:
         raise KeyError(f"no batched environment for id {id!r}; registered: {sorted(VECTOR_CLASSES)}")
     from rsoccer_amd import vec
     return getattr(vec, VECTOR_CLASSES[id])(int(num_envs), **kwargs)
 
 
-__all__ = ["make", "make_vec", "register", "registry", "VECTOR_CLASSES", "__version__"]
+def physics_defaults(kind):
+    """the default per-env physics parameters of a robot class (``"vss"`` / ``"ssl"`` or 0 / 1): ``{name: float}``
+    (docs/PHYSICS.md section 3)"""
+    from rsoccer_amd import _lib
+    k = {"vss": _lib.KIND_VSS, "ssl": _lib.KIND_SSL}.get(kind, kind) if isinstance(kind, str) else int(kind)
+    vals = _lib.physics_defaults(k)
+    return {n: float(v) for n, v in zip(_lib.PHYSICS_PARAMS, vals) if not (k == _lib.KIND_SSL and n == "a_lat")}
+
+
+__all__ = ["make", "make_vec", "physics_defaults", "register", "registry", "VECTOR_CLASSES", "__version__"]

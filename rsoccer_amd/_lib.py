@@ -24,6 +24,12 @@ FIELD_KEYS = (
 )  # Entities/Field.py:5-21
 N_METRICS = 8
 X_ROWS = 2   # internal state rows behind get_state(): ball vertical velocity, ball spin (RSX_STATE_EXTRA_ROWS)
+# per-env physics parameters (include/rsx.h: RSX_PHYS_*), in row order; "a_lat" is a VSS parameter (SSL: 0)
+PHYSICS_PARAMS = ("m_robot", "m_ball", "e_rr", "e_rb", "e_wb", "e_wr", "mu_rr", "mu_rb", "mu_wb", "mu_g", "spin_dec",
+                  "a_lin", "a_ang", "a_lat")
+PHYSICS_COEFS = ("w_rb_r", "w_rb_b", "kt_rb_r", "kt_rb_b", "ope_rr", "ope_rb", "ope_wb", "e_wb", "e_wr", "mu_rr", "mu_rb", "mu_wb",
+                 "a_lin_h", "a_lin_h2", "a_lat_h", "a_ang_h", "mu_g_dt", "spin_dec_dt")
+PHYS_RAW, PHYS_COEF = 0, 1
 METRIC_NAMES = ("env_steps", "episodes", "goals_for", "goals_against", "return_sum_q20",
                 "episode_len_sum", "truncated_episodes", "reserved")
 
@@ -37,6 +43,8 @@ SYMBOLS = (
     "rsx_task_step_n", "rsx_task_rollout", "rsx_read_metrics", "rsx_metrics_fold", "rsx_check_finite",
     "rsx_task_checkpoint_size", "rsx_task_checkpoint_save", "rsx_task_checkpoint_load",
     "rsx_task_enable_capture", "rsx_task_tick", "rsx_drop_pending_hip_error",
+    "rsx_physics_defaults", "rsx_physics_derive", "rsx_physics_enable", "rsx_physics_set", "rsx_physics_get",
+    "rsx_physics_randomize", "rsx_physics_errors",
 )
 
 
@@ -114,6 +122,13 @@ def load():
     lib.rsx_task_enable_capture.argtypes = [vp, vp]
     lib.rsx_task_tick.argtypes = [vp, C.POINTER(C.c_uint32), vp]
     lib.rsx_drop_pending_hip_error.argtypes = []
+    lib.rsx_physics_defaults.argtypes = [ip, vp]
+    lib.rsx_physics_derive.argtypes = [ip, ip, vp, vp]
+    lib.rsx_physics_enable.argtypes = [vp, vp]
+    lib.rsx_physics_set.argtypes = [vp, vp, ip, vp, vp]
+    lib.rsx_physics_get.argtypes = [vp, ip, vp, vp]
+    lib.rsx_physics_randomize.argtypes = [vp, vp, vp, C.c_uint32, vp]
+    lib.rsx_physics_errors.argtypes = [vp, C.POINTER(C.c_int64), vp]
     if lib.rsx_abi_version() != 6:
         raise RsxError("librsx_hip.so ABI version mismatch")
     _lib = lib
@@ -433,6 +448,52 @@ class Sim:
         blob = np.ascontiguousarray(np.frombuffer(blob, dtype=np.uint8) if isinstance(blob, (bytes, bytearray)) else blob, dtype=np.uint8)
         _chk(self._lib.rsx_task_checkpoint_load(self._h, blob.ctypes.data_as(C.c_void_p), blob.size, self._stream(stream)))
 
+    # ---- per-env physics (include/rsx.h: rsx_physics_*) ----
+    def physics_enable(self, stream=None):
+        """every env gets its own physics parameters, all at the defaults (the lane-group kernels step the handle from now on)"""
+        _chk(self._lib.rsx_physics_enable(self._h, self._stream(stream)))
+        self.physics_on = True
+
+    def physics_set(self, values, env_mask=None, stream=None):
+        """``values``: [len(PHYSICS_PARAMS), num_envs] float32, NaN = keep.  A numpy array is checked on the host (RsxError for an
+        out-of-range value, nothing changed); a device tensor (anything with ``data_ptr``) is read on the device, where an env
+        with an invalid value keeps its values and is counted by ``physics_errors()``.  ``env_mask``: [num_envs] bytes in the
+        same memory, or None."""
+        want = (len(PHYSICS_PARAMS), self.num_envs)
+        if hasattr(values, "data_ptr"):
+            if tuple(values.shape) != want or not values.is_contiguous() or str(values.dtype) != "torch.float32":
+                raise ValueError(f"values must be a contiguous float32 tensor of shape {want}")
+            m = None
+            if env_mask is not None:
+                if tuple(env_mask.shape) != (self.num_envs,) or env_mask.element_size() != 1 or not env_mask.is_contiguous():
+                    raise ValueError("env_mask must be a contiguous 1-byte tensor of shape (num_envs,)")
+                m = C.c_void_p(env_mask.data_ptr())
+            _chk(self._lib.rsx_physics_set(self._h, C.c_void_p(values.data_ptr()), 1, m, self._stream(stream)))
+            return
+        v = np.ascontiguousarray(values, dtype=np.float32)
+        if v.shape != want:
+            raise ValueError(f"values must have shape {want}, got {v.shape}")
+        m = None if env_mask is None else np.ascontiguousarray(env_mask, dtype=np.uint8)
+        _chk(self._lib.rsx_physics_set(self._h, _ptr(v), 0, _ptr(m), self._stream(stream)))
+
+    def physics_get(self, which=PHYS_RAW, stream=None):
+        """[len(PHYSICS_PARAMS) | len(PHYSICS_COEFS), num_envs] float32 on the host (synchronises)"""
+        out = np.zeros((len(PHYSICS_PARAMS) if which == PHYS_RAW else len(PHYSICS_COEFS), self.num_envs), dtype=np.float32)
+        _chk(self._lib.rsx_physics_get(self._h, int(which), _ptr(out), self._stream(stream)))
+        return out
+
+    def physics_randomize(self, lo, hi, param_mask, stream=None):
+        """redraw the parameters of ``param_mask`` (bit p = PHYSICS_PARAMS[p]) in [lo[p], hi[p]) at every episode start"""
+        lo = np.ascontiguousarray(lo, dtype=np.float32).reshape(len(PHYSICS_PARAMS))
+        hi = np.ascontiguousarray(hi, dtype=np.float32).reshape(len(PHYSICS_PARAMS))
+        _chk(self._lib.rsx_physics_randomize(self._h, _ptr(lo), _ptr(hi), C.c_uint32(int(param_mask)), self._stream(stream)))
+
+    def physics_errors(self, stream=None):
+        """envs refused by device-side ``physics_set`` calls since the last call"""
+        n = C.c_int64(0)
+        _chk(self._lib.rsx_physics_errors(self._h, C.byref(n), self._stream(stream)))
+        return int(n.value)
+
     def metrics_fold(self, stream=None):
         """make the device copy of the episode counters (``task_tensors()["metrics"]``) exact, on ``stream``"""
         _chk(self._lib.rsx_metrics_fold(self._h, self._stream(stream)))
@@ -445,3 +506,20 @@ class Sim:
 
 def device_count():
     return int(load().rsx_device_count())
+
+
+def physics_defaults(kind):
+    """the per-env physics parameters' defaults of a robot class (rsx_physics_defaults): float32 [len(PHYSICS_PARAMS)]"""
+    out = np.zeros(len(PHYSICS_PARAMS), dtype=np.float32)
+    _chk(load().rsx_physics_defaults(int(kind), _ptr(out)))
+    return out
+
+
+def physics_derive(kind, time_step_ms, raw):
+    """the coefficients the kernels derive from one parameter set (rsx_physics_derive): float32 [len(PHYSICS_COEFS)]"""
+    raw = np.ascontiguousarray(raw, dtype=np.float32)
+    if raw.shape != (len(PHYSICS_PARAMS),):
+        raise ValueError(f"expected {len(PHYSICS_PARAMS)} parameters, got {raw.shape}")
+    out = np.zeros(len(PHYSICS_COEFS), dtype=np.float32)
+    _chk(load().rsx_physics_derive(int(kind), int(time_step_ms), _ptr(raw), _ptr(out)))
+    return out

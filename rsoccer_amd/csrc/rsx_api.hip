@@ -26,6 +26,12 @@ void launch_scrimmage_big(bool rollout, const Params& P, const Buffers& b, int n
 void launch_ssl_quad(const Params& P, const Buffers& b, int n_steps, hipStream_t s);   // rsx_quad_ssl.hpp: four lanes per env, single-step launches
 int ssl_quad_grid(int num_envs);   // workgroups of those launches
 int epl_grid(int num_envs);
+// rsx_phys.hip: the kernels of physics-enabled handles (rsx_physics_enable)
+void launch_task_phys(const Params& P, const Buffers& b, int L, int NR, float* phys, int n_steps, int mode, hipStream_t s);
+void launch_sim_phys(const Params& P, const Buffers& b, int L, int NR, float* phys, float* state_out, int rand_tick, hipStream_t s);
+void launch_phys_init(float* blk, int B, int S, int kind, int ts_ms, hipStream_t s);
+void launch_phys_set(float* blk, const float* vals, const uint8_t* mask, int B, int S, int vstride, hipStream_t s);
+void launch_phys_ranges(float* blk, const float* lo, const float* hi, uint32_t mask, hipStream_t s);
 }
 
 using namespace rsx;
@@ -134,6 +140,7 @@ struct rsx_sim {
     // rsx_kernels.hpp: step_tick) so that captured stepping launches advance it when a graph replays them
     bool tick_dev = false;
     int tick_slots = 0;                       // workgroups of the handle's per-step launches: the slots every stepping call keeps in sync
+    float* d_phys = nullptr;                  // rsx_physics_enable: the per-env physics block (rsx_phys.hpp: PhysHeader, rows), or null
     int tick_slots_alloc = 0;                 // slots allocated (the largest grid any layout of this batch could launch): rsx_task_enable_capture and
                                               // rsx_task_checkpoint_load write ALL of them, so that no grid ever reads a slot nobody has set
 };
@@ -217,6 +224,7 @@ void launch_sim_k(const rsx_sim* h, const Params& P_, float* state_out, int rand
     Buffers b = buffers_of(h, nullptr);
     if (cmds_src) b.cmds = cmds_src;                      // commands straight from pinned host memory (small batches)
     b.flags = reinterpret_cast<uint8_t*>(mirror);         // the raw step's fourth pointer slot: second copy of the new state, or null
+    if (h->d_phys) { launch_sim_phys(P_, b, h->L, h->NR, h->d_phys, state_out, rand_tick, s); return; }
     if (KIND == RSX_KIND_VSS && h->NR == 6 && h->L == 8) { RSX_LAUNCH_SIM((sim_step_kernel<KIND, 8, (KIND == RSX_KIND_VSS ? 6 : 0)>), P_, b); return; }
     if (KIND == RSX_KIND_VSS && h->NR == 10) { RSX_LAUNCH_SIM((sim_step_kernel<KIND, 16, (KIND == RSX_KIND_VSS ? 10 : 0)>), P_, b); return; }
     if (KIND == RSX_KIND_SSL && h->NR == 7 && h->L == 8) { RSX_LAUNCH_SIM((sim_step_kernel<KIND, 8, (KIND == RSX_KIND_SSL ? 7 : 0)>), P_, b); return; }
@@ -344,6 +352,7 @@ void launch_fixed(const rsx_sim* h, const float* actions, int n_steps, int mode,
 }
 
 void launch_task(const rsx_sim* h, const float* actions, int n_steps, int mode, hipStream_t s) {
+    if (h->d_phys) { launch_task_phys(h->P, buffers_of(h, mode == MODE_STEP ? actions : nullptr), h->L, h->NR, h->d_phys, n_steps, mode, s); return; }
     switch (h->P.task) {
         case RSX_TASK_VSS_V0: launch_task_k<RSX_KIND_VSS, RSX_TASK_VSS_V0, 6>(h, actions, n_steps, mode, s); break;
         case RSX_TASK_SSL_STATIC_DEFENDERS: launch_task_k<RSX_KIND_SSL, RSX_TASK_SSL_STATIC_DEFENDERS, 7>(h, actions, n_steps, mode, s); break;
@@ -359,6 +368,7 @@ void launch_task(const rsx_sim* h, const float* actions, int n_steps, int mode, 
 // per-workgroup tick slots of a device-keyed handle are sized and kept in sync by (rsx_kernels.hpp: step_tick)
 int step_grid(const rsx_sim* h, int mode) {
     const int B = h->P.num_envs;
+    if (h->d_phys) return (int)grid_for(h).x;   // (the per-env physics kernels: tiles only)
     if (h->epl) return epl_grid(B);
     if (h->quad && mode == MODE_STEP) return ssl_quad_grid(B);
     int g = (int)grid_for(h).x;
@@ -458,6 +468,8 @@ void free_all(rsx_sim* h) {
     h->alt_alloc = h->d_state_alt = nullptr;
     if (h->d_check) (void)hipFree(h->d_check);
     h->d_check = nullptr;
+    if (h->d_phys) (void)hipFree(h->d_phys);
+    h->d_phys = nullptr;
     if (h->arena_sim) (void)hipFree(h->arena_sim);
     if (h->arena_task) (void)hipFree(h->arena_task);
     h->arena_sim = h->arena_task = nullptr;
@@ -914,6 +926,7 @@ int rsx_task_attach(rsx_sim* h, int task, uint64_t seed, uint64_t env_id_base, i
         const size_t rows = (size_t)std::max(P.state_dim + X_ROWS, aux_rows(P.n_robots));
         if (rows * (size_t)P.row_stride * sizeof(float) >= ((size_t)1 << 31) || (size_t)P.num_envs * P.obs_dim * sizeof(float) >= ((size_t)1 << 31)) h->epl = false;
     }
+    if (h->d_phys) h->epl = h->big = h->quad = false;   // per-env physics: the lane-group kernels at every batch size
     h->task_ready = false;
     h->tick_dev = false;
     h->tick_slots = step_grid(h, MODE_STEP);
@@ -1120,13 +1133,19 @@ struct CkptHeader {
     int64_t metrics[RSX_METRICS];
 };
 constexpr uint64_t CKPT_MAGIC = 0x3254504B43585352ull;   // "RSXCKPT2", little endian
+// model word of a physics-enabled handle's blob: a section follows the others — the physics header (ranges), the parameter rows
+// and the coefficient rows (dense, like the rest); a blob of either kind is refused by a handle of the other
+constexpr int32_t CKPT_MODEL_PHYS = 1 << 16;
+size_t ckpt_phys_bytes(const CkptHeader& k) {
+    return (k.model & CKPT_MODEL_PHYS) ? sizeof(PhysHeader) + (size_t)(NPHYS + NCOEF) * (size_t)k.num_envs * sizeof(float) : 0;
+}
 CkptHeader ckpt_header(const rsx_sim* h) {
     CkptHeader k{};
     const size_t B = (size_t)h->P.num_envs;
     k.magic = CKPT_MAGIC; k.abi = RSX_ABI_VERSION; k.kind = h->P.kind; k.field_rows = h->M.rs; k.task = h->P.task;
     k.n_blue = h->P.n_blue; k.n_yellow = h->P.n_yellow; k.num_envs = h->P.num_envs;
     k.state_rows = h->P.state_dim + X_ROWS; k.aux_rows = aux_rows(h->P.n_robots); k.obs_dim = h->P.obs_dim;
-    k.field_type = h->field_type; k.time_step_ms = h->time_step_ms; k.max_steps = h->P.max_steps; k.model = RSX_PHYSICS_MODEL;
+    k.field_type = h->field_type; k.time_step_ms = h->time_step_ms; k.max_steps = h->P.max_steps; k.model = RSX_PHYSICS_MODEL | (h->d_phys ? CKPT_MODEL_PHYS : 0);
     k.key0 = h->P.key0; k.key1 = h->P.key1; k.env_id_base = h->P.env_id_base; k.tick = h->tick;
     k.state_bytes = (uint64_t)k.state_rows * B * sizeof(float);
     k.aux_bytes = (uint64_t)k.aux_rows * B * sizeof(float);
@@ -1134,7 +1153,7 @@ CkptHeader ckpt_header(const rsx_sim* h) {
     k.flag_bytes = 2 * B;
     return k;
 }
-size_t ckpt_size(const CkptHeader& k) { return sizeof(CkptHeader) + k.state_bytes + k.aux_bytes + 2 * k.obs_bytes + k.flag_bytes; }
+size_t ckpt_size(const CkptHeader& k) { return sizeof(CkptHeader) + k.state_bytes + k.aux_bytes + 2 * k.obs_bytes + k.flag_bytes + ckpt_phys_bytes(k); }
 }  // namespace
 
 extern "C" {
@@ -1162,6 +1181,11 @@ int rsx_task_checkpoint_save(rsx_sim* h, void* blob, size_t bytes, void* stream)
     HIP_TRY(hipMemcpyAsync(p, h->d_obs, k.obs_bytes, hipMemcpyDeviceToHost, s)); p += k.obs_bytes;
     HIP_TRY(hipMemcpyAsync(p, h->d_final_obs, k.obs_bytes, hipMemcpyDeviceToHost, s)); p += k.obs_bytes;
     HIP_TRY(hipMemcpyAsync(p, h->d_flags, k.flag_bytes, hipMemcpyDeviceToHost, s));
+    if (h->d_phys) {
+        p += k.flag_bytes;
+        HIP_TRY(hipMemcpyAsync(p, h->d_phys, sizeof(PhysHeader), hipMemcpyDeviceToHost, s)); p += sizeof(PhysHeader);
+        HIP_TRY(hipMemcpy2DAsync(p, rowb, phys_raw(h->d_phys), pitch, rowb, (size_t)(NPHYS + NCOEF), hipMemcpyDeviceToHost, s));   // raw rows, then the coefficient rows
+    }
     HIP_TRY(hipMemcpyAsync(k.metrics, h->d_metrics, sizeof(k.metrics), hipMemcpyDeviceToHost, s));
     if (h->tick_dev)   // device-keyed handle: the step counter is slot 0 of the per-workgroup slots (all equal between launches)
         HIP_TRY(hipMemcpyAsync(&k.tick, tick_words(h) + TICK_SLOT_WORD0, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -1194,6 +1218,8 @@ int rsx_task_checkpoint_load(rsx_sim* h, const void* blob, size_t bytes, void* s
     std::memcpy(&k, blob, sizeof(k));
     CkptHeader want = ckpt_header(h);
     if (k.magic != CKPT_MAGIC || k.abi != want.abi) return fail(RSX_ERR_ARG, "not a checkpoint of this library version");
+    if ((k.model & CKPT_MODEL_PHYS) != (want.model & CKPT_MODEL_PHYS))
+        return fail(RSX_ERR_ARG, "the checkpoint was taken from a handle with per-env physics on / off and this one has it off / on (rsx_physics_enable)");
     if (k.model != want.model) return fail(RSX_ERR_ARG, "the checkpoint was taken under another version of the physics model (RSX_PHYSICS_MODEL)");
     if (k.kind != want.kind || k.task != want.task || k.n_blue != want.n_blue || k.n_yellow != want.n_yellow ||
         k.num_envs != want.num_envs || k.state_rows != want.state_rows || k.aux_rows != want.aux_rows || k.obs_dim != want.obs_dim)
@@ -1218,6 +1244,15 @@ int rsx_task_checkpoint_load(rsx_sim* h, const void* blob, size_t bytes, void* s
     HIP_TRY(hipMemcpyAsync(h->d_obs, p, k.obs_bytes, hipMemcpyHostToDevice, s)); p += k.obs_bytes;
     HIP_TRY(hipMemcpyAsync(h->d_final_obs, p, k.obs_bytes, hipMemcpyHostToDevice, s)); p += k.obs_bytes;
     HIP_TRY(hipMemcpyAsync(h->d_flags, p, k.flag_bytes, hipMemcpyHostToDevice, s));
+    if (h->d_phys) {   // ranges and mask of the blob, this handle's error word
+        p += k.flag_bytes;
+        PhysHeader hd;
+        std::memcpy(&hd, p, sizeof(hd)); p += sizeof(PhysHeader);
+        if (hd.kind != h->P.kind || hd.ts_ms != h->time_step_ms) return fail(RSX_ERR_ARG, "the checkpoint's physics section is damaged");
+        launch_phys_ranges(h->d_phys, hd.lo, hd.hi, hd.mask, s);
+        HIP_TRY(launch_status());
+        HIP_TRY(hipMemcpy2DAsync(phys_raw(h->d_phys), pitch, p, rowb, rowb, (size_t)(NPHYS + NCOEF), hipMemcpyHostToDevice, s));
+    }
     HIP_TRY(hipMemsetAsync(h->d_mslots, 0, (size_t)MSLOTS * RSX_METRICS * sizeof(unsigned long long), s));
     HIP_TRY(hipMemcpyAsync(h->d_metrics, k.metrics, sizeof(k.metrics), hipMemcpyHostToDevice, s));
     if (h->tick_dev) {   // device-keyed handle: every slot takes the blob's step counter; a refused-launch mark is cleared with it
@@ -1252,6 +1287,129 @@ int rsx_read_metrics(rsx_sim* h, int64_t out[RSX_METRICS], void* stream) {
     if (h->tick_dev) HIP_TRY(hipMemcpyAsync(&refused, tick_words(h) + TICK_ERR_WORD, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (refused) return fail(RSX_ERR_STATE, "step counter exhausted: stepping launches of this device-keyed handle were refused on the device (out[] is valid; a handle takes at most 2^32 - 1 fused steps)");
+    return RSX_OK;
+}
+
+}  // extern "C"
+
+// ---- per-env physics parameters (rsx.h: rsx_physics_*; kernels and block layout: rsx_phys.hip, rsx_phys.hpp) ----
+namespace {
+int check_phys_set(int kind, const float* raw) {
+    for (int p = 0; p < NPHYS; ++p)
+        if (!phys_valid(kind, p, raw[p])) return fail(RSX_ERR_ARG, "physics parameter " + std::to_string(p) + " out of range (rsx.h: rsx_physics_*)");
+    return RSX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rsx_physics_defaults(int kind, float out[RSX_PHYS_PARAMS]) {
+    if (kind != RSX_KIND_VSS && kind != RSX_KIND_SSL) return fail(RSX_ERR_ARG, "kind must be RSX_KIND_VSS or RSX_KIND_SSL");
+    if (!out) return fail(RSX_ERR_ARG, "out is null");
+    for (int p = 0; p < NPHYS; ++p) out[p] = (float)phys_default(kind, p);
+    return RSX_OK;
+}
+
+int rsx_physics_derive(int kind, int time_step_ms, const float raw[RSX_PHYS_PARAMS], float coef[RSX_PHYS_COEFS]) {
+    if (kind != RSX_KIND_VSS && kind != RSX_KIND_SSL) return fail(RSX_ERR_ARG, "kind must be RSX_KIND_VSS or RSX_KIND_SSL");
+    if (!raw || !coef || time_step_ms < 0) return fail(RSX_ERR_ARG, "null argument or negative time step");
+    if (int rc = check_phys_set(kind, raw)) return rc;
+    derive_coefs(kind, time_step_ms, raw, coef);
+    return RSX_OK;
+}
+
+int rsx_physics_enable(rsx_sim* h, void* stream) {
+    RSX_ENTER(h);
+    if (h->d_phys) return RSX_OK;
+    if (h->L > 32) return fail(RSX_ERR_ARG, "per-env physics runs with up to 32 lanes per env (unset RSX_LANES_PER_ENV=64)");
+    if (h->tick_dev) return fail(RSX_ERR_STATE, "call rsx_physics_enable before rsx_task_enable_capture");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t S = (size_t)h->P.row_stride;
+    HIP_TRY(hipMalloc((void**)&h->d_phys, phys_block_bytes(S)));
+    HIP_TRY(hipMemsetAsync(h->d_phys, 0, phys_block_bytes(S), s));
+    PhysHeader hd{};
+    hd.kind = h->P.kind; hd.ts_ms = h->time_step_ms;
+    HIP_TRY(hipMemcpyAsync(h->d_phys, &hd, sizeof(hd), hipMemcpyHostToDevice, s));
+    launch_phys_init(h->d_phys, h->P.num_envs, (int)S, h->P.kind, h->time_step_ms, s);
+    HIP_TRY(launch_status());
+    HIP_TRY(hipStreamSynchronize(s));   // (the header travels from the stack)
+    if (h->P.task != RSX_TASK_NONE) {   // attached already: the layout of a physics-enabled handle
+        h->epl = h->big = h->quad = false;
+        h->tick_slots = step_grid(h, MODE_STEP);
+    }
+    return RSX_OK;
+}
+
+int rsx_physics_set(rsx_sim* h, const float* values, int on_device, const uint8_t* env_mask, void* stream) {
+    RSX_ENTER(h);
+    if (!h->d_phys) return fail(RSX_ERR_STATE, "per-env physics is off (rsx_physics_enable)");
+    if (!values) return fail(RSX_ERR_ARG, "values is null");
+    hipStream_t s = (hipStream_t)stream;
+    const int B = h->P.num_envs;
+    const size_t S = (size_t)h->P.row_stride;
+    h->host_state_valid = false;
+    if (on_device) {
+        launch_phys_set(h->d_phys, values, env_mask, B, (int)S, B, s);
+        HIP_TRY(launch_status());
+        return RSX_OK;
+    }
+    // host values: checked here (NaN = keep), then staged and written by the same kernel
+    for (int e = 0; e < B; ++e) {
+        if (env_mask && !env_mask[e]) continue;
+        for (int p = 0; p < NPHYS; ++p) {
+            const float v = values[(size_t)p * B + e];
+            if (v == v && !phys_valid(h->P.kind, p, v))
+                return fail(RSX_ERR_ARG, "physics parameter " + std::to_string(p) + " of env " + std::to_string(e) + " out of range (rsx.h: rsx_physics_*)");
+        }
+    }
+    float* const stage = phys_stage(h->d_phys, S);
+    uint8_t* const smask = phys_stage_mask(h->d_phys, S);
+    HIP_TRY(hipMemcpyAsync(stage, values, (size_t)NPHYS * B * sizeof(float), hipMemcpyHostToDevice, s));
+    if (env_mask) HIP_TRY(hipMemcpyAsync(smask, env_mask, (size_t)B, hipMemcpyHostToDevice, s));
+    launch_phys_set(h->d_phys, stage, env_mask ? smask : nullptr, B, (int)S, B, s);
+    HIP_TRY(launch_status());
+    HIP_TRY(hipStreamSynchronize(s));   // the caller's arrays may go away on return
+    return RSX_OK;
+}
+
+int rsx_physics_get(rsx_sim* h, int which, float* out, void* stream) {
+    RSX_ENTER(h);
+    if (!h->d_phys) return fail(RSX_ERR_STATE, "per-env physics is off (rsx_physics_enable)");
+    if (!out || (which != RSX_PHYS_RAW && which != RSX_PHYS_COEF)) return fail(RSX_ERR_ARG, "out is null or `which` unknown");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t S = (size_t)h->P.row_stride, rowb = (size_t)h->P.num_envs * sizeof(float);
+    const float* src = which == RSX_PHYS_RAW ? phys_raw(h->d_phys) : phys_coef(h->d_phys, S);
+    HIP_TRY(hipMemcpy2DAsync(out, rowb, src, S * sizeof(float), rowb, (size_t)(which == RSX_PHYS_RAW ? NPHYS : NCOEF), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return RSX_OK;
+}
+
+int rsx_physics_randomize(rsx_sim* h, const float* lo, const float* hi, uint32_t param_mask, void* stream) {
+    RSX_ENTER(h);
+    if (!h->d_phys) return fail(RSX_ERR_STATE, "per-env physics is off (rsx_physics_enable)");
+    if (param_mask >> NPHYS) return fail(RSX_ERR_ARG, "param_mask names a parameter that does not exist");
+    if (param_mask && (!lo || !hi)) return fail(RSX_ERR_ARG, "lo / hi are null");
+    for (int p = 0; p < NPHYS; ++p) {
+        if (!((param_mask >> p) & 1u)) continue;
+        if (!phys_valid(h->P.kind, p, lo[p]) || !phys_valid(h->P.kind, p, hi[p]) || !(lo[p] <= hi[p]))
+            return fail(RSX_ERR_ARG, "randomisation range of physics parameter " + std::to_string(p) + " is invalid (lo <= hi, both valid values)");
+    }
+    launch_phys_ranges(h->d_phys, param_mask ? lo : nullptr, param_mask ? hi : nullptr, param_mask, (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
+int rsx_physics_errors(rsx_sim* h, int64_t* out, void* stream) {
+    RSX_ENTER(h);
+    if (!h->d_phys) return fail(RSX_ERR_STATE, "per-env physics is off (rsx_physics_enable)");
+    if (!out) return fail(RSX_ERR_ARG, "out is null");
+    hipStream_t s = (hipStream_t)stream;
+    uint32_t* const w = &reinterpret_cast<PhysHeader*>(h->d_phys)->err;
+    uint32_t v = 0;
+    HIP_TRY(hipMemcpyAsync(&v, w, sizeof(v), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemsetAsync(w, 0, sizeof(uint32_t), s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *out = (int64_t)v;
     return RSX_OK;
 }
 

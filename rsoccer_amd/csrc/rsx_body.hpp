@@ -16,6 +16,7 @@
 
 #include "rsx_math.hpp"
 #include "rsx_params.hpp"
+#include "rsx_phys.hpp"
 
 namespace rsx {
 
@@ -242,21 +243,23 @@ __device__ __forceinline__ float2 held_diff(const float2 ha, const float2 hp) { 
 // A bounce of the BALL off a wall with Coulomb friction at the contact point: couples the velocity
 // component along the wall with the spin about the vertical axis.  (vx0, vy0) = velocity before
 // walls(): the ball moved INTO the wall, so its sign names the wall's side.
+// (mu_wb, ope_wb: the literals, or an env's own coefficients — rsx_phys.hpp)
 template <int KIND>
 __device__ __forceinline__ void ball_wall_spin(const int hit, const float vx0, const float vy0,
-                                               float& vx, float& vy, float& om) {
+                                               float& vx, float& vy, float& om,
+                                               const float mu_wb = KC<KIND>::mu_wb, const float ope_wb = KC<KIND>::ope_wb) {
     using K = KC<KIND>;
     if (hit & 2) {
         const float sg = vy0 < 0.0f ? -1.0f : 1.0f;
         const float vc = vx - (om * K::r_ball) * sg;
-        const float lim = K::mu_wb * (K::ope_wb * fabsf(vy0));
+        const float lim = mu_wb * (ope_wb * fabsf(vy0));
         const float d = clampf(-(vc * K::kw), -lim, lim);
         vx = vx + d; om = om - (sg * d) * K::spin_c;
     }
     if (hit & 1) {
         const float sg = vx0 < 0.0f ? -1.0f : 1.0f;
         const float vc = vy + (om * K::r_ball) * sg;
-        const float lim = K::mu_wb * (K::ope_wb * fabsf(vx0));
+        const float lim = mu_wb * (ope_wb * fabsf(vx0));
         const float d = clampf(-(vc * K::kw), -lim, lim);
         vy = vy + d; om = om + (sg * d) * K::spin_c;
     }
@@ -465,20 +468,20 @@ __device__ __forceinline__ void contact_pair(const Params& P, const Body& bi, co
 // speed removed with a grip cap, yaw rate towards t1.  SSL (holonomic): robot-frame velocity towards (t0, t1) with
 // a vector acceleration cap, yaw rate towards t2.  The heading is integrated in degrees (the wire unit); its
 // cosine / sine are carried by a small rotation (one exact sincos per step()).
-template <int KIND>
-__device__ __forceinline__ void actuate_robot(const Params& P, Body& o) {
+template <int KIND, class CF = LitCoef<KIND>>
+__device__ __forceinline__ void actuate_robot(const Params& P, Body& o, const CF& cf = CF{}) {
     float vf = fma_(o.vy, o.s, o.vx * o.c);
     float vl = fma_(o.vy, o.c, -(o.vx * o.s));
     if (KIND == RSX_KIND_VSS) {
-        vf = vf + clampf(o.t0 - vf, -P.a_lin_h, P.a_lin_h);
-        vl = vl - clampf(vl, -P.a_lat_h, P.a_lat_h);
-        o.om = o.om + clampf(o.t1 - o.om, -P.a_ang_h, P.a_ang_h);
+        vf = vf + clampf(o.t0 - vf, -cf.a_lin_h(P), cf.a_lin_h(P));
+        vl = vl - clampf(vl, -cf.a_lat_h(P), cf.a_lat_h(P));
+        o.om = o.om + clampf(o.t1 - o.om, -cf.a_ang_h(P), cf.a_ang_h(P));
     } else {
         float dx = o.t0 - vf, dy = o.t1 - vl;
         float d2 = fma_(dx, dx, dy * dy);
-        if (d2 > P.a_lin_h2) { float sc = P.a_lin_h / sqrtf(d2); dx = dx * sc; dy = dy * sc; }
+        if (d2 > cf.a_lin_h2(P)) { float sc = cf.a_lin_h(P) / sqrtf(d2); dx = dx * sc; dy = dy * sc; }
         vf = vf + dx; vl = vl + dy;
-        o.om = o.om + clampf(o.t2 - o.om, -P.a_ang_h, P.a_ang_h);
+        o.om = o.om + clampf(o.t2 - o.om, -cf.a_ang_h(P), cf.a_ang_h(P));
     }
     o.vx = fma_(vf, o.c, -(vl * o.s));
     o.vy = fma_(vf, o.s, vl * o.c);
@@ -515,19 +518,22 @@ __device__ __forceinline__ void integrate_ball(const Params& P, Body& ball) {
 }
 // once per step(), before the sub-steps: rolling resistance (a constant deceleration to an exact stop) while the
 // ball is on the ground, and the decay of its spin about the vertical axis
-__device__ __forceinline__ void ball_step_friction(const Params& P, Body& ball) {
+template <class CF>
+__device__ __forceinline__ void ball_step_friction(const Params& P, Body& ball, const CF& cf) {
     if (P.n_sub && !(ball.z > 0.0f || ball.vz > 0.0f)) {
         float sp2 = fma_(ball.vx, ball.vx, ball.vy * ball.vy);
         if (sp2 > 0.0f) {
-            float sp = sqrtf(sp2), ns = sp - P.mu_g_dt;
+            float sp = sqrtf(sp2), ns = sp - cf.mu_g_dt(P);
             if (ns < 0.0f) ns = 0.0f;
             float kk = ns / sp;
             ball.vx = ball.vx * kk; ball.vy = ball.vy * kk;
         }
-        const float aw = fabsf(ball.om) - P.spin_dec_dt;
+        const float aw = fabsf(ball.om) - cf.spin_dec_dt(P);
         ball.om = aw > 0.0f ? (ball.om < 0.0f ? -aw : aw) : 0.0f;
     }
 }
+// (the Params-borne values of the literal provider do not depend on the class)
+__device__ __forceinline__ void ball_step_friction(const Params& P, Body& ball) { ball_step_friction(P, ball, LitCoef<RSX_KIND_VSS>{}); }
 // the ball's wall clamp incl. the friction of a bounce
 template <int KIND>
 __device__ __forceinline__ void ball_walls(const Params& P, Body& ball) {

@@ -44,6 +44,7 @@
 #include "rsx_math.hpp"
 #include "rsx_params.hpp"
 #include "rsx_body.hpp"
+#include "rsx_phys.hpp"
 
 namespace rsx {
 
@@ -128,12 +129,51 @@ __device__ __forceinline__ unsigned long long env_lane_mask(const int g) {
     return m << g;
 }
 
+// ---- per-env physics (rsx_phys.hpp) ----
+// the env's coefficients into registers: one load per row, once per launch
+__device__ __forceinline__ void load_coefs(const Params& P, const float* __restrict__ phys, const int e, EnvCoef& cf) {
+    const float* const rows = phys + PHYS_HDR_FLOATS + (size_t)NPHYS * (size_t)P.row_stride;
+    const ix_t B4 = (ix_t)4 * (ix_t)P.row_stride, off = (ix_t)4 * (ix_t)e;
+#pragma unroll
+    for (int i = 0; i < NCOEF; ++i) cf.c[i] = at_byte(rows, off + (ix_t)i * B4);
+}
+// Episode start of env e (every lane of the env calls this): the parameters with a randomisation range are redrawn —
+// lo + (hi - lo) * u01(x), x from philox4x32(env_id, episode, p, DOM_PHYS) — and the coefficients re-derived; `writer` (one lane
+// of the env) stores both.  Nothing happens while no range is set.
+__device__ __forceinline__ void phys_redraw(const Params& P, float* __restrict__ phys, const int e, const uint32_t env_id,
+                                            const uint32_t episode, const bool writer, EnvCoef& cf) {
+    const PhysHeader* const hd = reinterpret_cast<const PhysHeader*>(phys);
+    const uint32_t mask = hd->mask;
+    if (mask == 0u) return;
+    const size_t S = (size_t)P.row_stride;
+    float* const raw = phys_raw(phys);
+    float v[NPHYS];
+#pragma unroll
+    for (int p = 0; p < NPHYS; ++p) {
+        if ((mask >> p) & 1u) {
+            const u32x4 u = philox4x32(env_id, episode, (uint32_t)p, DOM_PHYS, P.key0, P.key1);
+            v[p] = hd->lo[p] + (hd->hi[p] - hd->lo[p]) * u01(u.x);
+        } else {
+            v[p] = raw[(size_t)p * S + e];
+        }
+    }
+    derive_coefs(hd->kind, hd->ts_ms, v, cf.c);
+    if (writer) {
+        float* const co = phys_coef(phys, S);
+#pragma unroll
+        for (int p = 0; p < NPHYS; ++p)
+            if ((mask >> p) & 1u) raw[(size_t)p * S + e] = v[p];
+#pragma unroll
+        for (int i = 0; i < NCOEF; ++i) co[(size_t)i * S + e] = cf.c[i];
+    }
+}
+
 // VSS contact sweep with a run-time partner loop: exact integer overlap test into one bit per
 // partner, then the lane walks ITS partners in index order.  First sweep of the run-time-count
 // kernels and second sweep (rare) of all VSS kernels.  Returns whether some pair was deep.
-template <int KIND, int L>
+template <int KIND, int L, class CF = LitCoef<KIND>>
 __device__ __forceinline__ bool vss_sweep_loop(const Params& P, Body& o, const int N, const int g, const bool is_ball,
-                                               const bool ball_low, const Shared<L>& sh, bool& wallp, const float2 fo) {
+                                               const bool ball_low, const Shared<L>& sh, bool& wallp, const float2 fo, const CF& cf = CF{}) {
     using K = KC<KIND>;
     constexpr int G = 64 / L;
     constexpr uint32_t T_RR = __builtin_bit_cast(uint32_t, K::rs_rr2) - 1u;
@@ -161,9 +201,9 @@ __device__ __forceinline__ bool vss_sweep_loop(const Params& P, Body& o, const i
         const float2 fj = sh.F[LaneMap<L>::slot(j, g)];
         const float dx = oj.x - o.x, dy = oj.y - o.y;
         const bool rb = is_ball || j == N;
-        contact_response<KIND>(P, snap, oj, fma_(dx, dx, dy * dy), rb ? K::rs_rb : K::rs_rr, rb ? K::ope_rb : K::ope_rr,
-                         is_ball ? K::w_rb_b : (j == N ? K::w_rb_r : K::w_rr),
-                         is_ball ? K::kt_rb_b : (j == N ? K::kt_rb_r : K::kt_rr), rb ? K::mu_rb : K::mu_rr,
+        contact_response<KIND>(P, snap, oj, fma_(dx, dx, dy * dy), rb ? K::rs_rb : K::rs_rr, rb ? cf.ope_rb() : cf.ope_rr(),
+                         is_ball ? cf.w_rb_b() : (j == N ? cf.w_rb_r() : K::w_rr),
+                         is_ball ? cf.kt_rb_b() : (j == N ? cf.kt_rb_r() : K::kt_rr), rb ? cf.mu_rb() : cf.mu_rr(),
                          is_ball ? K::spin_c : 0.0f, fma_(wj, j == N ? K::r_ball : K::r_robot, snap.om * lever),
                          K::beta, K::pen2, !rb, v2w, avx, avy, apx, apy, aw, deep, wallp, fo, fj);
     }
@@ -217,10 +257,10 @@ struct BallOverride { bool ovr, okick; float ovx, ovy, ovz; };
 // NRX > 0: robot count known at compile time.  `first` is wave-uniform: both sweeps of a sub-step run
 // the SAME instructions (a second copy of this code would be cold in the instruction cache every
 // time it is needed, which costs more than the sweep itself).
-template <int KIND, int L, int NRX>
+template <int KIND, int L, int NRX, class CF = LitCoef<KIND>>
 __device__ __forceinline__ bool ssl_sweep(const Params& P, Body& o, const int N, const int g, const int lane,
                                           const bool is_robot, const bool is_ball, const bool ball_low,
-                                          const bool first, Shared<L>& sh, BallOverride& bo, bool& wallp) {
+                                          const bool first, Shared<L>& sh, BallOverride& bo, bool& wallp, const CF& cf = CF{}) {
     using K = KC<KIND>;
     constexpr int G = 64 / L;
     constexpr uint32_t T_RR = __builtin_bit_cast(uint32_t, K::rs_rr2) - 1u;
@@ -273,7 +313,7 @@ __device__ __forceinline__ bool ssl_sweep(const Params& P, Body& o, const int N,
                         nxw = sh.W[LaneMap<L>::slot(jn, g)];
                     }
                     const float dx = oj.x - o.x, dy = oj.y - o.y;
-                    contact_response<KIND>(P, o, oj, fma_(dx, dx, dy * dy), K::rs_rr, K::ope_rr, K::w_rr, K::kt_rr, K::mu_rr, 0.0f,
+                    contact_response<KIND>(P, o, oj, fma_(dx, dx, dy * dy), K::rs_rr, cf.ope_rr(), K::w_rr, K::kt_rr, cf.mu_rr(), 0.0f,
                                            fma_(wj, K::r_robot, o.om * K::r_robot), K::beta, K::pen2, true, L == 8 ? WALLS : v2w, avx, avy, apx, apy, aw, deep, wallp);
                     if (!more) break;
                 }
@@ -312,21 +352,21 @@ __device__ __forceinline__ bool ssl_sweep(const Params& P, Body& o, const int N,
             float vn = fma_(dvx, nx, dvy * ny);
             if (vn < 0.0f) {
                 const float omb = sh.W[LaneMap<L>::slot(N, g)];
-                float q = K::ope_rb * vn * K::w_rb_r; avx = fma_(q, nx, avx); avy = fma_(q, ny, avy);
+                float q = cf.ope_rb() * vn * cf.w_rb_r(); avx = fma_(q, nx, avx); avy = fma_(q, ny, avy);
                 const float wsum = fma_(omb, K::r_ball, o.om * (mouth ? K::dck : K::r_robot));
                 const float vt = fma_(dvy, nx, -(dvx * ny)) - wsum;
-                const float lim = q * K::mu_rb;
-                const float ft = clampf(vt * K::kt_rb_r, lim, -lim);
+                const float lim = q * cf.mu_rb();
+                const float ft = clampf(vt * cf.kt_rb_r(), lim, -lim);
                 avx = fma_(-ft, ny, avx); avy = fma_(ft, nx, avy);
                 // the ball's side of the same contact
-                float qb = K::ope_rb * vn * K::w_rb_b;
-                const float limb = qb * K::mu_rb;
-                const float ftb = clampf(vt * K::kt_rb_b, limb, -limb);
+                float qb = cf.ope_rb() * vn * cf.w_rb_b();
+                const float limb = qb * cf.mu_rb();
+                const float ftb = clampf(vt * cf.kt_rb_b(), limb, -limb);
                 r0.x = fma_(-ftb, ny, qb * nx); r0.y = fma_(ftb, nx, qb * ny); dws = ftb * K::spin_c; fl |= 1;
             }
-            float pc = K::beta * pen * K::w_rb_r;
+            float pc = K::beta * pen * cf.w_rb_r();
             apx = fma_(-pc, nx, apx); apy = fma_(-pc, ny, apy);
-            float pb = K::beta * pen * K::w_rb_b; r0.z = pb * nx; r0.w = pb * ny; fl |= 2;
+            float pb = K::beta * pen * cf.w_rb_b(); r0.z = pb * nx; r0.w = pb * ny; fl |= 2;
         }
         if (first) {
             o.ir = mouth && pen > -K::ir_tol;
@@ -378,9 +418,9 @@ __device__ __forceinline__ bool ssl_sweep(const Params& P, Body& o, const int N,
 //   b = body index of the lane (0..N-1 robots, N ball, > N idle), g = env slot in the wave
 //   NR > 0: robot count known at compile time (pair loops fully unrolled); NR == 0: run-time
 // ---------------------------------------------------------------------------------------------
-template <int KIND, int L, int NR>
+template <int KIND, int L, int NR, class CF = LitCoef<KIND>>
 __device__ __forceinline__ void physics(const Params& P, Body& o, const int b, const int g,
-                                        const bool live, Shared<L>& sh) {
+                                        const bool live, Shared<L>& sh, const CF& cf = CF{}) {
     using K = KC<KIND>;
     constexpr int G = 64 / L;
     const int N = NR ? NR : P.n_robots;
@@ -392,7 +432,7 @@ __device__ __forceinline__ void physics(const Params& P, Body& o, const int b, c
     // ball is on the ground (exact stop, never reverses) — keeps the sqrt + divide chain out of
     // the sub-step loop, where the ball lane's branch is serialised with the robots' work.
     // Same place: the spin about the vertical axis decays at a constant rate to an exact stop.
-    if (is_ball) ball_step_friction(P, o);
+    if (is_ball) ball_step_friction(P, o, cf);
 #ifdef RSX_TIMING_SUB   // development: where a sub-step's cycles go (sub-steps 1.. only; tools/exp_substep_phases.py)
     unsigned long long tsA = 0, tsB = 0, tsC = 0, ts0 = 0, ts1 = 0, ts2 = 0;
 #endif
@@ -403,7 +443,7 @@ __device__ __forceinline__ void physics(const Params& P, Body& o, const int b, c
 #endif
         // ---- A: actuation + integration ----
         if (is_robot) {   // rsx_body.hpp: the per-body arithmetic is stated once for all kernel layouts
-            actuate_robot<KIND>(P, o);
+            actuate_robot<KIND>(P, o, cf);
             o.th = advance_heading(P, o.om, o.th);
             rotate_heading(o.om * P.h, o.c, o.s);
         }
@@ -508,10 +548,10 @@ __device__ __forceinline__ void physics(const Params& P, Body& o, const int b, c
                                 const float dx = oj.x - o.x, dy = oj.y - o.y;
                                 const float d2 = fma_(dx, dx, dy * dy);   // the value the sweep above saw
                                 const bool rb = is_ball || j == NR;
-                                contact_response<KIND>(P, o, oj, d2, rb ? K::rs_rb : K::rs_rr, rb ? K::ope_rb : K::ope_rr,
-                                                       is_ball ? K::w_rb_b : (j == NR ? K::w_rb_r : K::w_rr),
-                                                       is_ball ? K::kt_rb_b : (j == NR ? K::kt_rb_r : K::kt_rr),
-                                                       rb ? K::mu_rb : K::mu_rr, is_ball ? K::spin_c : 0.0f,
+                                contact_response<KIND>(P, o, oj, d2, rb ? K::rs_rb : K::rs_rr, rb ? cf.ope_rb() : cf.ope_rr(),
+                                                       is_ball ? cf.w_rb_b() : (j == NR ? cf.w_rb_r() : K::w_rr),
+                                                       is_ball ? cf.kt_rb_b() : (j == NR ? cf.kt_rb_r() : K::kt_rr),
+                                                       rb ? cf.mu_rb() : cf.mu_rr(), is_ball ? K::spin_c : 0.0f,
                                                        fma_(wj, j == NR ? K::r_ball : K::r_robot, o.om * lever), K::beta, K::pen2, !rb, v2w,
                                                        avx, avy, apx, apy, aw, deep, wallp, fo, fj);
                                 if (!more) break;
@@ -523,11 +563,11 @@ __device__ __forceinline__ void physics(const Params& P, Body& o, const int b, c
                         }
                     } else {
                         publish_held();
-                        deep = vss_sweep_loop<KIND, L>(P, o, N, g, is_ball, ball_low, sh, wallp, fo);
+                        deep = vss_sweep_loop<KIND, L>(P, o, N, g, is_ball, ball_low, sh, wallp, fo, cf);
                     }
                 }
             } else {
-                deep = ssl_sweep<KIND, L, NR>(P, o, N, g, lane, is_robot && active, is_ball && active, ball_low, sweep == 0, sh, bo, wallp);
+                deep = ssl_sweep<KIND, L, NR>(P, o, N, g, lane, is_robot && active, is_ball && active, ball_low, sweep == 0, sh, bo, wallp, cf);
             }
             // second sweep for the envs in which some pair was deep: one ballot, usually no lane; a third and a fourth one for the
             // envs in which the last sweep also saw a wall pair (model v2: piles pressed against a wall)
@@ -560,15 +600,15 @@ __device__ __forceinline__ void physics(const Params& P, Body& o, const int b, c
             if constexpr (KIND == RSX_KIND_VSS) {
                 // the goal-post response shares the rare branch of the ball's wall friction (one exec-mask branch at the end of every
                 // sub-step instead of two: a lone wave pays for each one's compare -> scalar -> branch chain)
-                const float rb = is_ball ? K::r_ball : K::r_robot, eb = is_ball ? K::e_wb : K::e_wr;
+                const float rb = is_ball ? K::r_ball : K::r_robot, eb = is_ball ? cf.e_wb() : cf.e_wr();
                 walls<KIND, true>(P, rb, eb, o.x, o.y, o.vx, o.vy, hit);
                 if (RSX_RARE_B(KIND, 2, (is_ball && (hit & 3)) || (hit & 8))) {
                     if (hit & 8) post_response(P, rb, eb, o.x, o.y, o.vx, o.vy, hit);
-                    if (is_ball && (hit & 3)) ball_wall_spin<KIND>(hit, vx0, vy0, o.vx, o.vy, o.om);
+                    if (is_ball && (hit & 3)) ball_wall_spin<KIND>(hit, vx0, vy0, o.vx, o.vy, o.om, cf.mu_wb(), cf.ope_wb());
                 }
             } else {
-            walls<KIND>(P, is_ball ? K::r_ball : K::r_robot, is_ball ? K::e_wb : K::e_wr, o.x, o.y, o.vx, o.vy, hit);
-            if (RSX_RARE_B(KIND, 2, is_ball && hit)) ball_wall_spin<KIND>(hit, vx0, vy0, o.vx, o.vy, o.om);
+            walls<KIND>(P, is_ball ? K::r_ball : K::r_robot, is_ball ? cf.e_wb() : cf.e_wr(), o.x, o.y, o.vx, o.vy, hit);
+            if (RSX_RARE_B(KIND, 2, is_ball && hit)) ball_wall_spin<KIND>(hit, vx0, vy0, o.vx, o.vy, o.om, cf.mu_wb(), cf.ope_wb());
             }
         }
         wave_sync();  // A / W / Bq / Cq / Dq are rewritten by the next sub-step
@@ -733,53 +773,16 @@ static_assert(bytes_of(&probe) == RSX_HOT_ARGS_BYTES, "RSX_HOT_ARGS changed: upd
 // =============================================================================================
 template <int KIND, int L, int NR>
 __global__ __launch_bounds__(64) void sim_step_kernel(RSX_HOT_ARGS, const Params P_, const Buffers bufs_) {
-    Params P = P_; RSX_UNPACK_HOT(P);
-    Buffers bufs = bufs_; bufs.state = hp_state; bufs.cmds = hp_in;   // hp_in: the command buffer
-    float* const state_out = hp_aux;   // this kernel's second pointer slot: where the new state goes (== hp_state: in place)
-    // fourth pointer slot: a second copy of the new state, or nullptr.  The host-format calls of small batches
-    // (rsx_step / rsx_step_state: the robosim-shaped single-env path) hand in pinned host memory here and read their
-    // commands from pinned host memory too: one launch + one synchronisation per step instead of copy, launch, copy
-    float* const mirror = reinterpret_cast<float*>(hp_flags);
-    using K = KC<KIND>;
-    constexpr int G = 64 / L;
-    constexpr int CD = ModelD<KIND>::cmd_dim;
-    __shared__ Shared<L> sh;
-#ifdef RSX_TIMING
-    if (threadIdx.x == 0) sh.dbg = nullptr;
-#endif
-    const int lane = threadIdx.x;
-    const int b = LaneMap<L>::body(lane), g = LaneMap<L>::env(lane);
-    const int e = tile_of_block(hp_per_xcd) * G + g;
-    const int N = NR ? NR : P.n_robots;
-    const bool live = e < P.num_envs;
-    const bool is_robot = live && b < N, is_ball = live && b == N;
-    const size_t B = (size_t)P.num_envs;
-
-    Body o; float od, wd, w[4];
-    const RawBody raw = load_raw<KIND>(P, bufs.state, e, b, is_robot, is_ball);
-    float q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const int rand_tick = hp_n_steps;   // >= 0: commands are drawn here (rsx_step_dev_random), < 0: read from memory
-    if (is_robot) {
-        if (rand_tick >= 0) {
-            const u32x4 u = philox4x32(P.env_id_base + (uint32_t)e, (uint32_t)rand_tick, (uint32_t)b, DOM_RAW, P.key0, P.key1);
-            const float a0 = u01(u.x) * 2.0f - 1.0f, a1 = u01(u.y) * 2.0f - 1.0f, a2 = u01(u.z) * 2.0f - 1.0f;
-            if (KIND == RSX_KIND_SSL) { q[1] = a0 * 2.5f; q[2] = a1 * 2.5f; q[3] = a2 * 10.0f; }
-            else { q[0] = a0 * K::w_max; q[1] = a1 * K::w_max; }
-        } else {
-            const ix_t B4 = (ix_t)4 * (ix_t)P.row_stride, c0 = (ix_t)(b * CD) * B4 + (ix_t)4 * (ix_t)e;
-#pragma unroll
-            for (int i = 0; i < CD; ++i) q[i] = at_byte(bufs.cmds, c0 + (ix_t)i * B4);
-        }
-    }
-    interpret_body<KIND>(raw, is_robot, is_ball, o, od, wd, w);
-    if (is_robot) robot_targets<KIND>(P, o, q);
-    physics<KIND, L, NR>(P, o, b, g, live, sh);
-    if (is_robot) {
-        od = o.th; wd = o.om * K::rad2deg;
-        if (KIND == RSX_KIND_SSL) wheel_speeds<KIND>(P, o, w);
-    }
-    store_body<KIND>(P, state_out, e, b, is_robot, is_ball, o, od, wd, w, P.n_sub != 0 || state_out != hp_state);
-    if (mirror) store_body<KIND>(P, mirror, e, b, is_robot, is_ball, o, od, wd, w, true);
+    constexpr bool PHYS = false;
+    const float* const phys = nullptr;
+#include "rsx_sim_step_body.inc"
+}
+// the raw step of a physics-enabled handle (rsx_physics_enable): the same, each env with its own coefficients
+// (rsx_phys.hpp: EnvCoef from the coefficient rows of the block `phys`)
+template <int KIND, int L, int NR>
+__global__ __launch_bounds__(64) void sim_step_phys_kernel(RSX_HOT_ARGS, const Params P_, const Buffers bufs_, const float* phys) {
+    constexpr bool PHYS = true;
+#include "rsx_sim_step_body.inc"
 }
 
 // =============================================================================================
@@ -1370,422 +1373,16 @@ constexpr int MODE_STEP = 0, MODE_RESET = 1, MODE_REFRESH = 2, MODE_ROLLOUT = 3;
 #endif
 template <int KIND, int L, int TASK, int NR, int MODE>
 __global__ __launch_bounds__(64) RSX_TASK_KERNEL_ATTR void task_step_kernel(RSX_HOT_ARGS, const Params P_, const Buffers bufs_) {
-    // A multi-step launch is short of SGPRs, not of start-up latency: there the preloaded copies
-    // are left dead and everything is fetched from the kernarg segment when it is needed.
-    constexpr bool HOT = MODE != MODE_ROLLOUT;
-    Params P = P_;
-    Buffers bufs = bufs_;
-    if (HOT) {
-        RSX_UNPACK_HOT(P);
-        bufs.state = hp_state; bufs.aux = hp_aux; bufs.actions = hp_in; bufs.flags = hp_flags;
-    }
-    const int n_steps_arg = hp_n_steps & RSX_N_STEPS_MASK;
-    constexpr int mode = MODE == MODE_ROLLOUT ? MODE_STEP : MODE;
-    const int n_steps = MODE == MODE_ROLLOUT ? n_steps_arg : 1;
-    // the step counter of this launch (see step_tick): every workgroup — tiles, idle tail, placement helpers — takes part
-    const bool tick_dev = __builtin_expect((hp_n_steps & RSX_TICK_DEV) != 0, 0);
-    using K = KC<KIND>;
-    using T = TC<TASK>;
-    constexpr int G = 64 / L;
-    constexpr int ID = T::info_dim;
-    constexpr int AD = T::act_dim;
-    __shared__ Shared<L> sh;
-    // placement cache: single-step launches of the two rejection-sampled tasks in their fixed-size 8-lane variants
-    // (VSS-v0 3v3 would qualify as well and was measured: five resets per 4096-env launch — its slowest wave is a contact wave,
-    // 9.33 vs 9.30-9.38 us — for 112 B more reads per env-step; it keeps the inline placement)
-    constexpr bool PC = MODE == MODE_STEP && L == 8 && TASK == RSX_TASK_SSL_STATIC_DEFENDERS && NR == 7;
-    if constexpr (PC) {
-        if (__builtin_expect(bufs.pcache != nullptr && (int)blockIdx.x >= hp_per_xcd * 8, 0)) {   // a helper workgroup (behind the tiles)
-            const StepTick th = step_tick(tick_dev, P, bufs, 1u);
-            if (th.ok) placement_helper<KIND, L, TASK, (PC ? NR : 1)>(P, bufs, (int)blockIdx.x - hp_per_xcd * 8, th.t, sh);
-            return;
-        }
-    }
-    StepTick tk{0u, true};
-    if (MODE == MODE_STEP || MODE == MODE_ROLLOUT) {
-        tk = step_tick(tick_dev, P, bufs, (uint32_t)n_steps);
-        if (__builtin_expect(!tk.ok, 0)) return;
-    }
-    const uint32_t tick0 = tk.t;
-    const int lane = threadIdx.x;
-    const int b = LaneMap<L>::body(lane), g = LaneMap<L>::env(lane);
-    const int tile = tile_of_block(HOT ? hp_per_xcd : (int)(gridDim.x >> 3));
-    const int e = tile * G + g;
-    const int N = NR ? NR : P.n_robots;
-    const bool live = e < P.num_envs;
-    const bool is_robot = live && b < N, is_ball = live && b == N;
-    const size_t B = (size_t)P.num_envs;
-    const uint32_t env_id = P.env_id_base + (uint32_t)e;
-    // observation width: a compile-time constant when the team sizes are (lets the copy-out unroll)
-    constexpr int OD_C = NR == 0 ? 0
-        : TASK == RSX_TASK_VSS_V0 ? 4 + 6 * NR                // equal teams: 4 + 7*nb + 5*ny (vss_gym.py:64-67): 40 for 3v3, 64 for 5v5
-        : TASK == RSX_TASK_SSL_STATIC_DEFENDERS ? 4 + 8 + 2 * (NR - 1)
-        : TASK == RSX_TASK_SSL_SCRIMMAGE ? 2 + 2 * NR
-        : TASK == RSX_TASK_SSL_DRIBBLING ? 21 : TASK == RSX_TASK_SSL_CONTESTED ? 14 : 16;
-    const int OD = OD_C ? OD_C : P.obs_dim;
-#define auxe(ROW) at_byte(bufs.aux, (ix_t)(ROW) * ((ix_t)4 * (ix_t)P.row_stride) + (ix_t)4 * (ix_t)e)   // row ROW of this env in the scalar arena
-
-#ifdef RSX_TIMING
-#define RSX_STAMP(i) do { if (lane == 0) bufs.dbg[(size_t)(i) * gridDim.x + blockIdx.x] = __builtin_readcyclecounter(); } while (0)
-#else
-#define RSX_STAMP(i) do {} while (0)
-#endif
-#ifdef RSX_TIMING
-    if (lane == 0) { sh.dbg = bufs.dbg; bufs.dbg[(size_t)13 * gridDim.x + blockIdx.x] = __builtin_amdgcn_s_memrealtime(); }  // 100 MHz, chip-wide
-#endif
-    RSX_STAMP(0);
-    // ---- load ----
-    Body o; float od, wd, wheels[4];
-    const RawBody raw = load_raw<KIND>(P, bufs.state, e, b, is_robot, is_ball);
-    // Every launch starts with a cold instruction cache (the first pass through the code costs ~1 k cycles more than the later ones,
-    // profiles/r04_timeline_4096.txt).  The VSS single-step kernels touch the 8 KB of their own code that follow the entry point with
-    // ONE data load — a lane per 128-byte line; it lands with the state loads, long before the wave gets there — so that those
-    // instruction fetches find their lines in the L2: VSS-v0 at 4096 envs 9.02 -> 8.88 us per step (three interleaved rounds).
-    // Measured per kernel: later windows (+4, +8, +12 KB) or 16 / 24 KB gain nothing; the SSL kernels lose (11v11 +4 %, 1v6 +0.5 %).
-    constexpr bool CODE_PF = KIND == RSX_KIND_VSS && MODE == MODE_STEP;
-    uint32_t code_touch = 0;
-    if (CODE_PF) {
-        unsigned long long pc;
-        asm volatile("s_getpc_b64 %0" : "=s"(pc));
-        code_touch = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(pc) + 128u * (unsigned)lane));
-    }
-    int steps = 0; uint32_t episode = 0;
-    if (live) {
-        steps = __float_as_int(auxe(ROW_STEPS));
-        episode = __float_as_uint(auxe(ROW_EPISODE));
-    }
-    float ou0 = 0.0f, ou1 = 0.0f;
-    if (TASK == RSX_TASK_VSS_V0 && is_robot && b >= 1) {
-        ou0 = auxe(ROW_OU + 2 * b); ou1 = auxe(ROW_OU + 2 * b + 1);
-    }
-    float info[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    float prev_pot = 0.0f, ep_ret = 0.0f;
-    if (is_ball) {
-        // VSS-v0: rows 0, 4, 5 (goal counters) are zero except on a terminal step, and the step after it
-        // clears them: they are neither read nor — in the common case — written
-#pragma unroll
-        for (int i = 0; i < ID; ++i)
-            if (!(TASK == RSX_TASK_VSS_V0 && (i == 0 || i >= 4))) info[i] = auxe(ROW_INFO + i);
-        prev_pot = auxe(ROW_PREV_POT);
-        if (TASK != RSX_TASK_VSS_V0) ep_ret = auxe(ROW_EP_RET);   // VSS-v0: derived from the info terms
-    }
-    // metrics[0] (env-steps) is counted on the device by ONE lane of the grid: launches of a handle
-    // are stream-ordered, so a plain read-modify-write is race free and costs no atomic
-    const bool counts_steps = (MODE == MODE_STEP || MODE == MODE_ROLLOUT) && blockIdx.x == 0 && lane == 0;
-    unsigned long long steps_before = 0;
-    if (counts_steps) steps_before = bufs.metrics[0];
-    float reward = 0.0f; int term = 0, trunc = 0;
-    bool success = false;  // goal scored / course completed / pass received (metrics[2])
-    bool against = false;  // goal conceded (metrics[3]; scrimmage)
-    bool was_reset = false;
-    // caller-fed actions of the agent lane (robot 0); fed launches run a single step
-    const bool fed = MODE == MODE_STEP && bufs.actions != nullptr;
-    float act[AD];
-#pragma unroll
-    for (int i = 0; i < AD; ++i) act[i] = 0.0f;
-    if (TASK == RSX_TASK_SSL_SCRIMMAGE) {   // every robot is commanded: [B][N][4]
-        if (fed && is_robot) {
-#pragma unroll
-            for (int i = 0; i < AD; ++i) act[i] = at_byte(bufs.actions, (ix_t)4 * (((ix_t)e * (ix_t)N + (ix_t)b) * (ix_t)AD + (ix_t)i));   // ([B][N][AD] is smaller than the state array)
-        }
-    } else if (fed && is_robot && b == 0) {
-#pragma unroll
-        for (int i = 0; i < AD; ++i) act[i] = at_byte(bufs.actions, (ix_t)4 * ((ix_t)e * (ix_t)AD + (ix_t)i));
-    }
-
-    // placement cache: this body's pose in the env's next episode and the episode id it was made for, loaded with the state
-    float pcx = 0.0f, pcy = 0.0f, pcth = 0.0f;
-    uint32_t ptag = 0u;
-    bool pc_on = false;
-    if constexpr (PC) {
-        pc_on = bufs.pcache != nullptr;
-        if (pc_on && (is_robot || is_ball)) {
-            constexpr int NBD = (PC ? NR : 1) + 1;
-            const float* const pr = bufs.pcache + (size_t)((tick0 + 1u) & 1u) * (size_t)pcache_rows<NBD>() * B;
-            pcx = pr[(size_t)(0 * NBD + b) * B + e]; pcy = pr[(size_t)(1 * NBD + b) * B + e]; pcth = pr[(size_t)(2 * NBD + b) * B + e];
-            ptag = __float_as_uint(pr[(size_t)(3 * NBD) * B + e]);
-        }
-    }
-
-    // single-step launches: this step's random numbers, computed in the shadow of the loads
-    StepDraw pre;
-    if (MODE == MODE_STEP) pre = draw_for_step<KIND, TASK>(P, env_id, tick0, b, is_robot, fed);
-
-    // All loads land here, once.  Without this the compiler parks a vmcnt(0) at the top of the
-    // step loop (loop-carried values come from loads on the first trip), and on gfx9-class
-    // counters that wait also drains the previous trip's global STORES: one HBM write round
-    // trip per env step in the multi-step (rollout) launches.
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-    if (CODE_PF) asm volatile("" :: "v"(code_touch));   // (the value itself is of no interest)
-    interpret_body<KIND>(raw, is_robot, is_ball, o, od, wd, wheels);
-    RSX_STAMP(1);
-
-    for (int it = 0; it < n_steps; ++it) {
-        bool ended;
-        const float obs_ts = prev_pot;   // the task scalar as this step's observation sees it (before the reward moves it)
-        if (mode == 2) {
-            const bool flagged = live && bufs.flags[2 * B + e] != 0;   // third row of the flags array: the env mask of rsx_task_reset_to
-            if (flagged) {
-                episode += 1; steps = 0; ou0 = 0.0f; ou1 = 0.0f;
-                if (is_ball) {
-#pragma unroll
-                    for (int i = 0; i < 10; ++i) info[i] = 0.0f;
-#pragma unroll
-                    for (int i = 0; i < ID; ++i) auxe(ROW_INFO + i) = 0.0f;
-                    ep_ret = 0.0f; prev_pot = 0.0f;
-                }
-            }
-            // (only the re-placed envs: the observation of an env the mask leaves alone stays the one its last step wrote — recomputed here
-            // it would see the task scalar AFTER that step's reward moved it, e.g. the checkpoint count of SSLDribbling; found by
-            // tests/test_gpu_api_fuzz.py in 3 of 500 sequences)
-            if (flagged) write_obs<KIND, TASK>(P, bufs.obs + (size_t)e * OD, b, is_robot, is_ball, o.x, o.y, o.vx, o.vy, o.s, o.c, wd, o.ir, prev_pot);
-            wave_sync();
-            ended = false;
-        } else if (mode == 1) {
-            // reset(): nothing to simulate; fall through to the placement block below
-            ended = live;
-            episode += 1;
-            if (is_ball) {
-#pragma unroll
-                for (int i = 0; i < 10; ++i) info[i] = 0.0f;
-#pragma unroll
-                for (int i = 0; i < ID; ++i) auxe(ROW_INFO + i) = 0.0f;   // like reset_to above: the info rows of a fresh episode read zero
-                ep_ret = 0.0f; prev_pot = 0.0f;
-            }
-        } else {
-            const bool first_step = steps == 0;
-            const uint32_t t = tick0 + (uint32_t)it;   // per-step draws are keyed by the handle's step count, not by the env's counters
-            if (is_ball && first_step) {
-#pragma unroll
-                for (int i = 0; i < 10; ++i) info[i] = 0.0f;
-                ep_ret = 0.0f;
-            }
-            const float lastx = o.x, lasty = o.y;  // the reference's last_frame (pre-step)
-
-            // ---- actions -> commands ----
-            float q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            const StepDraw dr = MODE == MODE_STEP ? pre : draw_for_step<KIND, TASK>(P, env_id, t, b, is_robot, fed);
-            if (TASK == RSX_TASK_VSS_V0) {
-                if (is_robot) {
-                    float a0, a1;
-                    if (b == 0) {   // the agent: fed action or the step's uniform draw
-                        if (fed) { a0 = act[0]; a1 = act[1]; }
-                        else { a0 = dr.v[0]; a1 = dr.v[1]; }
-                    } else {  // Ornstein-Uhlenbeck noise, Utils/Utils.py:14-21, on the step's two normals
-                        ou0 = (ou0 + P.ou_theta_dt * (0.0f - ou0)) + P.ou_sig_sqdt * dr.v[0];
-                        ou1 = (ou1 + P.ou_theta_dt * (0.0f - ou1)) + P.ou_sig_sqdt * dr.v[1];
-                        a0 = ou0; a1 = ou1;
-                    }
-                    q[0] = vss_wheel(a0); q[1] = vss_wheel(a1);
-                }
-            } else if (TASK == RSX_TASK_SSL_SCRIMMAGE) {  // every robot: (v_x, v_y, v_theta, kick), block b of the step
-                if (is_robot) {
-                    float a[4];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) a[i] = fed ? act[i] : dr.v[i];
-                    q[1] = a[0] * T::max_v; q[2] = a[1] * T::max_v; q[3] = a[2] * 10.0f;
-                    q[5] = a[3] > 0.9f ? 5.0f : 0.0f;
-                }
-            } else {  // the SSL tasks: only blue 0 is driven by the agent
-                if (is_robot && b == 0) {
-                    float a[5] = {0, 0, 0, 0, 0};
-#pragma unroll
-                    for (int i = 0; i < AD; ++i) a[i] = fed ? act[i] : dr.v[i];
-                    ssl_agent_commands<TASK>(a, o.s, o.c, q);
-                }
-                if (TASK == RSX_TASK_SSL_PASS_ENDURANCE && is_robot && b == 1) q[7] = 1.0f;  // receiver: dribbler on
-            }
-            if (is_robot) robot_targets<KIND>(P, o, q);
-
-            // ---- physics ----
-            RSX_STAMP(2);
-            physics<KIND, L, NR>(P, o, b, g, live, sh);
-            RSX_STAMP(3);
-            if (MODE == MODE_STEP && KIND == RSX_KIND_SSL) {
-                // Single-step launches of the SSL tasks: what the rest of the step reads of the parameter block is fetched from the kernarg
-                // segment HERE, behind an opaque pointer, instead of being loaded at the kernel's entry and parked in VGPR lanes across
-                // the physics (these kernels run out of scalar registers: ~40 v_writelane at entry, ~60 v_readlane after the physics)
-                typedef const __attribute__((address_space(4))) uint32_t* kw_t;
-                constexpr size_t KOFF = RSX_PARAMS_KERNARG_OFFSET;   // after RSX_HOT_ARGS
-                static_assert(sizeof(Params) % 4 == 0 && KOFF % 4 == 0, "parameter block in dwords");
-                kw_t pk = (kw_t)__builtin_amdgcn_kernarg_segment_ptr() + KOFF / 4;
-                asm volatile("" : "+s"(pk));
-                struct Words { uint32_t w[sizeof(Params) / 4]; } raw;
-#pragma unroll
-                for (size_t i = 0; i < sizeof(Params) / 4; ++i) raw.w[i] = pk[i];
-                P = __builtin_bit_cast(Params, raw);
-                RSX_UNPACK_HOT(P);
-            }
-
-            // ---- wire-format values, observation, reward ----
-            if (is_robot) {
-                od = o.th; wd = o.om * K::rad2deg;
-                if (KIND == RSX_KIND_SSL) wheel_speeds<KIND>(P, o, wheels);
-                // omega lives in HBM as deg/s: keep the lane's copy equal to what a reload gives.
-                o.om = wd * K::deg2rad;
-                // the sub-steps carried (c, s) by small rotations; re-derive them exactly from the
-                // stored heading: this is what the observation reports and what a reload (the next
-                // launch, or the next step of a multi-step launch) starts from
-                sincos_f32(o.th * K::deg2rad, o.s, o.c);
-            } else if (is_ball) {
-                o.z = (K::r_ball + o.z) - K::r_ball;  // height goes through the wire format too
-            }
-            write_obs<KIND, TASK>(P, bufs.obs + (size_t)e * OD, b, is_robot, is_ball, o.x, o.y, o.vx, o.vy, o.s, o.c, wd, o.ir, obs_ts);
-            // what the reward lane (the ball's) needs from the robots' lanes
-            if (is_robot && b == 0) {
-                float* xr = sh.x0[g];
-                xr[0] = o.x; xr[1] = o.y;
-                if (TASK == RSX_TASK_VSS_V0) { xr[2] = o.vx; xr[3] = o.vy; xr[4] = q[0]; xr[5] = q[1]; }
-                else if (TASK == RSX_TASK_SSL_STATIC_DEFENDERS || TASK == RSX_TASK_SSL_CONTESTED) {
-                    xr[6] = lastx; xr[7] = lasty;
-                    xr[8] = wheels[0]; xr[9] = wheels[1]; xr[10] = wheels[2]; xr[11] = wheels[3];
-                }
-            } else if (is_robot) {
-                float* xr = sh.x0[g];
-                if (TASK == RSX_TASK_SSL_DRIBBLING) xr[1 + b] = (fabsf(o.vx) > 0.05f || fabsf(o.vy) > 0.05f) ? 1.0f : 0.0f;
-                if (TASK == RSX_TASK_SSL_CONTESTED && b == 1) xr[2] = (fabsf(o.vx) > 0.1f || fabsf(o.vy) > 0.1f) ? 1.0f : 0.0f;
-                if (TASK == RSX_TASK_SSL_PASS_ENDURANCE && b == 1) { xr[2] = o.x; xr[3] = o.y; xr[4] = o.ir ? 1.0f : 0.0f; }
-            }
-            wave_sync();
-            if (is_ball) {
-                const float* xr = sh.x0[g];
-                task_reward<KIND, TASK>(P, xr, o.x, o.y, lastx, lasty, first_step, prev_pot, info, reward, term, success, against);
-                ep_ret = ep_ret + reward;
-            }
-            steps += 1;
-            trunc = steps >= P.max_steps;
-            // episode-end flag of the env: held by its ball lane (lane N*G + g), spread with one
-            // ballot instead of an LDS round trip
-            const unsigned long long endm = __ballot(is_ball && (term | trunc));
-            ended = live && ((endm >> (LaneMap<L>::slot(N, g))) & 1ull) != 0;
-            if (is_ball) {
-                // info is reported as it stands after this step (cleared lazily at the next
-                // episode's first step), like the dict the reference returns with `done`
-#pragma unroll
-                for (int i = 0; i < ID; ++i)
-                    if (!(TASK == RSX_TASK_VSS_V0 && (i == 0 || i >= 4)) || term || first_step) auxe(ROW_INFO + i) = info[i];
-                auxe(ROW_REWARD) = reward;
-                if (MODE == MODE_STEP) { bufs.flags[(ix_t)e] = (uint8_t)term; bufs.flags[(ix_t)P.num_envs + (ix_t)e] = (uint8_t)trunc; }
-                else { bufs.flags[e] = (uint8_t)term; bufs.flags[B + e] = (uint8_t)trunc; }
-            }
-        }
-
-        RSX_STAMP(4);
-        // ---- episode end: same-step auto-reset (or reset()) ----
-        if (RSX_RARE_B(KIND, 4, __any(ended))) {
-            if (ended && mode == 0) {  // terminal observation
-                write_obs<KIND, TASK>(P, bufs.final_obs + (size_t)e * OD, b, is_robot, is_ball, o.x, o.y, o.vx, o.vy, o.s, o.c, wd, o.ir, obs_ts);
-            }
-            if (ended && mode == 0) episode += 1;   // every lane of the env: the new episode's id
-            if (KIND == RSX_KIND_VSS) {
-                if (ended && is_ball && mode == 0) {
-                    unsigned long long* const ms = metric_slot(bufs);
-                    atomicAdd(&ms[1], 1ull);
-                    if (info[4] > 0.0f) atomicAdd(&ms[2], 1ull);
-                    if (info[5] > 0.0f) atomicAdd(&ms[3], 1ull);
-                    atomicAdd(&ms[4], (unsigned long long)__float2ll_rn(vss_episode_return(info) * 1048576.0f));
-                    atomicAdd(&ms[5], (unsigned long long)steps);
-                    if (trunc && !term) atomicAdd(&ms[6], 1ull);
-                }
-            } else if (mode == 0) {
-                // SSL tasks (short episodes: several resetting waves in every launch): the ball lane
-                // holds the increments, lanes 0..5 of the env add one each, so the wave issues ONE
-                // atomic instruction instead of six guarded ones, each wrapped in wave-reduction
-                // code by the compiler.  Measured: static defenders 11.33 -> 11.03 us; VSS-v0 does
-                // not gain (8.83 -> 8.88) and keeps the plain form.
-                static_assert(KIND == RSX_KIND_VSS || L >= 6, "metrics fan-out needs 6 lanes per env");
-                uint32_t* const mv = reinterpret_cast<uint32_t*>(sh.x0[g]);   // 12 words, free again after the reward
-                if (ended && is_ball) {
-                    unsigned long long inc[6];
-                    inc[0] = 1ull;
-                    inc[1] = success ? 1ull : 0ull;
-                    inc[2] = against ? 1ull : 0ull;
-                    inc[3] = (unsigned long long)__float2ll_rn(ep_ret * 1048576.0f);
-                    inc[4] = (unsigned long long)steps;
-                    inc[5] = (trunc && !term) ? 1ull : 0ull;
-#pragma unroll
-                    for (int k = 0; k < 6; ++k) { mv[2 * k] = (uint32_t)inc[k]; mv[2 * k + 1] = (uint32_t)(inc[k] >> 32); }
-                }
-                wave_sync();
-                if (ended && b < 6) {
-                    const unsigned long long v = (unsigned long long)mv[2 * b] | ((unsigned long long)mv[2 * b + 1] << 32);
-                    if (v) atomicAdd(&metric_slot(bufs)[1 + b], v);
-                }
-            }
-            RSX_STAMP(15);
-            // an env whose next episode's poses were in the cache takes them from there; the others are placed here
-            const bool hit = PC && pc_on && ended && ptag == episode;
-            const bool place = ended && !hit;
-            const bool any_place = !PC || __any(place);
-            if (any_place) {
-                if (place) place_predraw<TASK, L>(P, env_id, episode, b, sh.draws[g]);
-                wave_sync();  // draws published; stage rows of ended envs are about to be overwritten
-            }
-            RSX_STAMP(16);
-            float4 pz = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            // A single-step launch waits for its slowest wave, which is one that resets an env:
-            // there the placement runs in its parallel form.  A multi-step launch pays for the
-            // average wave instead, and the sequential form issues fewer instructions.
-            if (TASK == RSX_TASK_SSL_SCRIMMAGE) {
-                // robot k in cell (k % 6, k / 6) of a 6 x 4 grid, one Philox block per body: every lane places itself
-                if (ended && (is_robot || is_ball)) {
-                    const u32x4 u = philox4x32(env_id, episode, (uint32_t)b, DOM_PLACE, P.key0, P.key1);
-                    const float jx = u01(u.x) * 2.0f - 1.0f, jy = u01(u.y) * 2.0f - 1.0f;
-                    if (is_ball) pz = make_float4(P.sc_jb * jx, P.sc_jb * jy, 0.0f, 0.0f);
-                    else pz = make_float4(P.sc_sx * ((float)(b % 6) - 2.5f) + P.sc_j * jx,
-                                          P.sc_sy * ((float)(b / 6) - 1.5f) + P.sc_j * jy, 360.0f * u01(u.z), 0.0f);
-                }
-            } else if ((TASK == RSX_TASK_VSS_V0 || TASK == RSX_TASK_SSL_STATIC_DEFENDERS) && MODE != MODE_ROLLOUT) {
-                if (any_place && place) pz = place_env_parallel<TASK, L, NR>(P, N, env_id, episode, b, g, is_robot, sh.A, sh.draws[g]);
-                if (hit) pz = make_float4(pcx, pcy, pcth, 0.0f);
-                if (PC && pc_on && bufs.pcstats && ended && is_ball) atomicAdd(&bufs.pcstats[hit ? 0 : 1], 1ull);
-            } else {
-                if (ended && is_ball) place_env<TASK, L>(P, N, env_id, episode, g, sh.A, sh.draws[g]);
-                wave_sync();
-                if (ended && (is_robot || is_ball)) pz = sh.A[LaneMap<L>::slot(b, g)];
-            }
-            RSX_STAMP(17);
-            if (ended) {
-                steps = 0; ou0 = 0.0f; ou1 = 0.0f; was_reset = true;
-                if (TASK >= RSX_TASK_SSL_DRIBBLING) prev_pot = 0.0f;  // checkpoints_count / stopped_steps
-                if (is_robot || is_ball) {
-                    o = Body{};
-                    o.x = pz.x; o.y = pz.y;
-                    od = pz.z; wd = 0.0f;
-                    wheels[0] = wheels[1] = wheels[2] = wheels[3] = 0.0f;
-                    if (is_robot) { o.th = od; sincos_f32(o.th * K::deg2rad, o.s, o.c); }
-                }
-                write_obs<KIND, TASK>(P, bufs.obs + (size_t)e * OD, b, is_robot, is_ball, o.x, o.y, o.vx, o.vy, o.s, o.c, wd, 0, 0.0f);
-            }
-            wave_sync();
-            RSX_STAMP(18);
-        }
-
-        wave_sync();
-    }
-
-    RSX_STAMP(5);
-    // ---- store (wire format: degrees, deg/s; SSL: infrared + wheel speeds) ----
-    if (mode != 2) store_body<KIND>(P, bufs.state, e, b, is_robot, is_ball, o, od, wd, wheels, P.n_sub != 0 || was_reset);
-    if (live && b == 0) {
-        auxe(ROW_STEPS) = __int_as_float(steps);
-        auxe(ROW_EPISODE) = __uint_as_float(episode);
-    }
-    if (TASK == RSX_TASK_VSS_V0 && is_robot && b >= 1) {
-        auxe(ROW_OU + 2 * b) = ou0; auxe(ROW_OU + 2 * b + 1) = ou1;
-    }
-    if (is_ball) {
-        auxe(ROW_PREV_POT) = prev_pot;
-        if (TASK != RSX_TASK_VSS_V0) auxe(ROW_EP_RET) = ep_ret;
-#undef auxe
-    }
-    if (counts_steps) bufs.metrics[0] = steps_before + (unsigned long long)P.num_envs * (unsigned long long)n_steps;
-    RSX_STAMP(6);
-#ifdef RSX_TIMING
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-    RSX_STAMP(7);
-    if (lane == 0) bufs.dbg[(size_t)14 * gridDim.x + blockIdx.x] = __builtin_amdgcn_s_memrealtime();
-#endif
+    constexpr bool PHYS = false;
+    float* const phys = nullptr;
+#include "rsx_task_step_body.inc"
+}
+// the fused step of a physics-enabled handle (rsx_physics_enable): each env with its own coefficients, redrawn at its episode
+// starts when a randomisation range is set.  Same launch shape as task_step_kernel, one more argument (the physics block).
+template <int KIND, int L, int TASK, int NR, int MODE>
+__global__ __launch_bounds__(64) void task_step_phys_kernel(RSX_HOT_ARGS, const Params P_, const Buffers bufs_, float* phys) {
+    constexpr bool PHYS = true;
+#include "rsx_task_step_body.inc"
 }
 
 }  // namespace rsx

@@ -39,7 +39,7 @@ class VecFusedEnv:
     TIME_STEP = 0.025
 
     def __init__(self, num_envs, device=0, seed=0, env_id_base=0, max_episode_steps=None,
-                 field_type=None):
+                 field_type=None, physics=None, physics_ranges=None):
         import torch
         self._torch = torch
         self.num_envs = int(num_envs)
@@ -48,6 +48,14 @@ class VecFusedEnv:
         self.sim = _lib.Sim(self.KIND, ft, self.N_BLUE, self.N_YELLOW, int(self.TIME_STEP * 1000),
                             self.num_envs, int(device))
         self.sim.task_attach(self.TASK, int(seed), int(env_id_base), int(max_episode_steps or 0))
+        # per-env physics: only when asked for (an env built without these keywords steps with the compiled-in constants)
+        self._physics = physics is not None or physics_ranges is not None
+        if self._physics:
+            self.sim.physics_enable(self._stream())
+            if physics:
+                self.set_physics(**physics)
+            if physics_ranges:
+                self.set_physics_randomization(**physics_ranges)
         self.max_episode_steps = self.sim.max_episode_steps
         self._t = self.sim.task_tensors()
         self._info_views = None
@@ -117,6 +125,89 @@ class VecFusedEnv:
         self.sim.task_step(ptr, self._stream())
         t = self._t
         return t["obs"], t["reward"], t["terminated"], t["truncated"], self._info()
+
+    # ---- per-env physics / domain randomisation (include/rsx.h: rsx_physics_*; docs/PHYSICS.md section 3) ----
+    def _physics_names(self):
+        names = _lib.PHYSICS_PARAMS
+        return names if self.KIND == _lib.KIND_VSS else tuple(n for n in names if n != "a_lat")
+
+    def _need_physics(self):
+        if not self._physics:
+            raise RuntimeError("this env was built without per-env physics: pass physics=... or physics_ranges=... "
+                               "(e.g. physics={}) to the constructor / make_vec")
+
+    def set_physics(self, env_ids=None, **values):
+        """Set physics parameters of the envs ``env_ids`` (None = all), e.g. ``set_physics(m_ball=0.05, mu_g=v)``.  A value is a
+        scalar, a numpy array of ``len(env_ids)`` (or ``num_envs``) values, or a device tensor of that length (read on the device,
+        no host copy).  Takes effect from the next step; out-of-range values raise (numpy / scalars) or are refused per env on
+        the device (``sim.physics_errors()``)."""
+        self._need_physics()
+        torch = self._torch
+        names = _lib.PHYSICS_PARAMS
+        for k in values:
+            if k not in self._physics_names():
+                raise KeyError(f"unknown physics parameter {k!r}; known: {self._physics_names()}")
+        B = self.num_envs
+        if env_ids is None:
+            mask = None
+        else:
+            ids = env_ids.cpu().numpy() if isinstance(env_ids, torch.Tensor) else np.asarray(env_ids)
+            ids = np.nonzero(ids)[0] if ids.dtype == bool else ids.astype(np.int64).reshape(-1)
+            mask = np.zeros(B, dtype=np.uint8)
+            mask[ids] = 1
+        on_dev = any(isinstance(v, torch.Tensor) and v.is_cuda for v in values.values())
+        if on_dev:
+            rows = torch.full((len(names), B), float("nan"), dtype=torch.float32, device=self.device)
+            for k, v in values.items():
+                v = torch.as_tensor(v, dtype=torch.float32, device=self.device)
+                if env_ids is None:
+                    rows[names.index(k)] = v.expand(B) if v.dim() == 0 else v
+                else:
+                    rows[names.index(k), torch.as_tensor(ids, device=self.device)] = v
+            m = None if mask is None else torch.from_numpy(mask).to(self.device)
+            self.sim.physics_set(rows, m, self._stream())
+            self._keep_phys = (rows, m)   # alive until the launch has read them
+            return
+        rows = np.full((len(names), B), np.nan, dtype=np.float32)
+        for k, v in values.items():
+            v = np.asarray(v, dtype=np.float32)
+            if env_ids is None:
+                rows[names.index(k)] = v
+            else:
+                rows[names.index(k), ids] = v
+        self.sim.physics_set(rows, mask, self._stream())
+
+    def physics(self):
+        """the current parameters: ``{name: (num_envs,) float32 tensor}`` on the env's device"""
+        self._need_physics()
+        raw = self.sim.physics_get(_lib.PHYS_RAW, self._stream())
+        t = self._torch.from_numpy(raw).to(self.device)
+        return {n: t[i] for i, n in enumerate(_lib.PHYSICS_PARAMS) if n in self._physics_names()}
+
+    def set_physics_randomization(self, **ranges):
+        """Domain randomisation: ``set_physics_randomization(m_ball=(0.04, 0.05), mu_g=None)`` — a parameter with a ``(lo, hi)``
+        range is redrawn per env, on the device, at every episode start (reset() and the same-step auto-reset), keyed by
+        ``(seed, env_id_base + env, episode)``; ``None`` removes its range (it then keeps its current values)."""
+        self._need_physics()
+        names = _lib.PHYSICS_PARAMS
+        cur = getattr(self, "_ranges", {})
+        for k, r in ranges.items():
+            if k not in self._physics_names():
+                raise KeyError(f"unknown physics parameter {k!r}; known: {self._physics_names()}")
+            if r is None:
+                cur.pop(k, None)
+            else:
+                lo, hi = r
+                cur[k] = (float(lo), float(hi))
+        lo = np.zeros(len(names), dtype=np.float32)
+        hi = np.zeros(len(names), dtype=np.float32)
+        mask = 0
+        for k, (a, b) in cur.items():
+            i = names.index(k)
+            lo[i], hi[i] = a, b
+            mask |= 1 << i
+        self.sim.physics_randomize(lo, hi, mask, self._stream())
+        self._ranges = cur
 
     def enable_graph_capture(self):
         """Make ``step()`` / ``step_random()`` capturable into a ``torch.cuda.CUDAGraph`` (hipGraph) and replayable.
