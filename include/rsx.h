@@ -417,6 +417,28 @@ int rsx_physics_randomize(rsx_sim* h, const float* lo, const float* hi, uint32_t
 /* envs refused by device-side rsx_physics_set calls since the last read (read and cleared; synchronises `stream`). */
 int rsx_physics_errors(rsx_sim* h, int64_t* out, void* stream);
 
+/* ---- trace evaluation for system identification (additive extension of ABI 6) --------------------------------------
+ * A trace is one recorded run: frames [n_frames][state_dim + RSX_STATE_EXTRA_ROWS] (the rsx_get_state_full layout) and the
+ * commands between them, cmds [n_frames - 1][N][C] (the rsx_step layout).  Evaluating it replays, in every env at once, the
+ * recorded commands from an anchor frame with the env's own physics parameters and measures how far the bodies drift from the
+ * recorded frames — the inner loop of fitting the parameters of docs/PHYSICS.md section 3 to another simulator. */
+#define RSX_TRACE_TERMS 6   /* ball xy (m^2), ball v (m^2/s^2), robot xy, robot heading (rad^2, wrapped), robot v, robot omega */
+/* Load a trace onto a physics-enabled raw handle (rsx_physics_enable, no task attached).  frames [n_frames][state_dim + 2] f64,
+ * cmds [n_frames - 1][N][C] f64, anchors [n_anchors] int32 frame indices.  num_envs % n_anchors == 0: env e evaluates
+ * candidate e / n_anchors from anchor e % n_anchors, with that env's physics row.  Host memory, converted to float32 once;
+ * replaces a trace loaded before.  RSX_ERR_STATE: physics off or a task attached; RSX_ERR_ARG: n_frames < 2, n_anchors < 1,
+ * num_envs % n_anchors != 0, an anchor outside [0, n_frames - 2] or a non-finite value.  Synchronises `stream`. */
+int rsx_trace_load(rsx_sim* h, const double* frames, const double* cmds, int n_frames,
+                   const int32_t* anchors, int n_anchors, void* stream);
+/* One launch: every env starts from its anchor frame, steps `horizon` times with the trace's commands and accumulates the
+ * squared deviation from the trace's frames.  loss_dev: device [RSX_TRACE_TERMS][num_envs] f32, dense.  Does not synchronise.
+ * The final state of each env is left in the handle's state buffer, bit for bit what set_state(anchor frame) followed by
+ * `horizon` rsx_step_dev calls with the trace's commands leaves there.  Terms are in SI units (converted from the wire format:
+ * degrees -> rad), summed over steps 1..horizon and over bodies; SSL wheel speeds and infrared are not part of them.
+ * RSX_ERR_STATE: physics off, a task attached or no trace loaded; RSX_ERR_ARG: horizon < 1, an anchor + horizon > n_frames - 1,
+ * loss_dev null. */
+int rsx_trace_eval(rsx_sim* h, int horizon, float* loss_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,8 @@ PHYSICS_PARAMS = ("m_robot", "m_ball", "e_rr", "e_rb", "e_wb", "e_wr", "mu_rr", 
 PHYSICS_COEFS = ("w_rb_r", "w_rb_b", "kt_rb_r", "kt_rb_b", "ope_rr", "ope_rb", "ope_wb", "e_wb", "e_wr", "mu_rr", "mu_rb", "mu_wb",
                  "a_lin_h", "a_lin_h2", "a_lat_h", "a_ang_h", "mu_g_dt", "spin_dec_dt")
 PHYS_RAW, PHYS_COEF = 0, 1
+# trace evaluation (include/rsx.h: RSX_TRACE_TERMS), in row order of the loss
+TRACE_TERMS = ("ball_xy", "ball_v", "robot_xy", "robot_heading", "robot_v", "robot_omega")
 METRIC_NAMES = ("env_steps", "episodes", "goals_for", "goals_against", "return_sum_q20",
                 "episode_len_sum", "truncated_episodes", "reserved")
 
@@ -45,6 +47,7 @@ SYMBOLS = (
     "rsx_task_enable_capture", "rsx_task_tick", "rsx_drop_pending_hip_error",
     "rsx_physics_defaults", "rsx_physics_derive", "rsx_physics_enable", "rsx_physics_set", "rsx_physics_get",
     "rsx_physics_randomize", "rsx_physics_errors",
+    "rsx_trace_load", "rsx_trace_eval",
 )
 
 
@@ -129,6 +132,8 @@ def load():
     lib.rsx_physics_get.argtypes = [vp, ip, vp, vp]
     lib.rsx_physics_randomize.argtypes = [vp, vp, vp, C.c_uint32, vp]
     lib.rsx_physics_errors.argtypes = [vp, C.POINTER(C.c_int64), vp]
+    lib.rsx_trace_load.argtypes = [vp, vp, vp, ip, vp, ip, vp]
+    lib.rsx_trace_eval.argtypes = [vp, ip, vp, vp]
     if lib.rsx_abi_version() != 6:
         raise RsxError("librsx_hip.so ABI version mismatch")
     _lib = lib
@@ -493,6 +498,26 @@ class Sim:
         n = C.c_int64(0)
         _chk(self._lib.rsx_physics_errors(self._h, C.byref(n), self._stream(stream)))
         return int(n.value)
+
+    # ---- trace evaluation (include/rsx.h: rsx_trace_*; rsoccer_amd/sysid.py) ----
+    def trace_load(self, frames, cmds, anchors, stream=None):
+        """``frames``: [n_frames, state_dim + 2] float64 (the ``get_state_full()`` layout), ``cmds``: [n_frames - 1, n_robots,
+        cmd_dim] float64, ``anchors``: frame indices, ``num_envs`` a multiple of their count (env e: candidate e // n_anchors
+        from anchor e % n_anchors).  Needs ``physics_enable()`` and no task; synchronises."""
+        f = np.ascontiguousarray(frames, dtype=np.float64)
+        if f.ndim != 2 or f.shape[1] != self.state_dim + X_ROWS or f.shape[0] < 2:
+            raise ValueError(f"frames must have shape (n_frames >= 2, {self.state_dim + X_ROWS}), got {f.shape}")
+        c = _f64(cmds, (f.shape[0] - 1, self.n_robots, self.cmd_dim))
+        a = np.ascontiguousarray(anchors, dtype=np.int32).reshape(-1)
+        _chk(self._lib.rsx_trace_load(self._h, _ptr(f), _ptr(c), int(f.shape[0]), _ptr(a), int(a.size), self._stream(stream)))
+
+    def trace_eval(self, horizon, loss, stream=None):
+        """one launch: ``loss`` (a contiguous float32 device tensor [len(TRACE_TERMS), num_envs]) receives every env's summed
+        squared deviation from the loaded trace over ``horizon`` steps; the final states stay in the state buffer.  No
+        synchronisation."""
+        if tuple(loss.shape) != (len(TRACE_TERMS), self.num_envs) or not loss.is_contiguous() or str(loss.dtype) != "torch.float32":
+            raise ValueError(f"loss must be a contiguous float32 tensor of shape {(len(TRACE_TERMS), self.num_envs)}")
+        _chk(self._lib.rsx_trace_eval(self._h, int(horizon), C.c_void_p(loss.data_ptr()), self._stream(stream)))
 
     def metrics_fold(self, stream=None):
         """make the device copy of the episode counters (``task_tensors()["metrics"]``) exact, on ``stream``"""

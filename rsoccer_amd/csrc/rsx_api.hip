@@ -8,6 +8,7 @@
 #include "rsx_launch.hpp"
 
 #include <cstdio>
+#include <cmath>
 #include <cstdlib>
 #include <algorithm>
 #include <cstring>
@@ -32,6 +33,9 @@ void launch_sim_phys(const Params& P, const Buffers& b, int L, int NR, float* ph
 void launch_phys_init(float* blk, int B, int S, int kind, int ts_ms, hipStream_t s);
 void launch_phys_set(float* blk, const float* vals, const uint8_t* mask, int B, int S, int vstride, hipStream_t s);
 void launch_phys_ranges(float* blk, const float* lo, const float* hi, uint32_t mask, hipStream_t s);
+// rsx_sysid.hip: trace evaluation (rsx_trace_eval)
+void launch_trace_eval(const Params& P, int L, int NR, const float* phys, float* state, float* loss, const float* frames,
+                       const float* cmds, const int32_t* anchors, int n_frames, int n_anchors, int horizon, hipStream_t s);
 }
 
 using namespace rsx;
@@ -141,6 +145,10 @@ struct rsx_sim {
     bool tick_dev = false;
     int tick_slots = 0;                       // workgroups of the handle's per-step launches: the slots every stepping call keeps in sync
     float* d_phys = nullptr;                  // rsx_physics_enable: the per-env physics block (rsx_phys.hpp: PhysHeader, rows), or null
+    // rsx_trace_load: one allocation, frames [state_dim + 2][trace_frames] | cmds [N * C][trace_frames - 1] | anchors int32, or null
+    float* d_trace = nullptr;
+    int trace_frames = 0, trace_anchors = 0, trace_anchor_max = 0;
+    size_t trace_cmds_off = 0, trace_anchors_off = 0;   // byte offsets into d_trace
     int tick_slots_alloc = 0;                 // slots allocated (the largest grid any layout of this batch could launch): rsx_task_enable_capture and
                                               // rsx_task_checkpoint_load write ALL of them, so that no grid ever reads a slot nobody has set
 };
@@ -470,6 +478,8 @@ void free_all(rsx_sim* h) {
     h->d_check = nullptr;
     if (h->d_phys) (void)hipFree(h->d_phys);
     h->d_phys = nullptr;
+    if (h->d_trace) (void)hipFree(h->d_trace);
+    h->d_trace = nullptr;
     if (h->arena_sim) (void)hipFree(h->arena_sim);
     if (h->arena_task) (void)hipFree(h->arena_task);
     h->arena_sim = h->arena_task = nullptr;
@@ -1411,6 +1421,68 @@ int rsx_physics_errors(rsx_sim* h, int64_t* out, void* stream) {
     HIP_TRY(hipStreamSynchronize(s));
     *out = (int64_t)v;
     return RSX_OK;
+}
+
+// ---- trace evaluation (rsx.h: rsx_trace_*; kernel: rsx_sysid.hip) ----
+int rsx_trace_load(rsx_sim* h, const double* frames, const double* cmds, int n_frames, const int32_t* anchors, int n_anchors,
+                   void* stream) {
+    RSX_ENTER(h);
+    if (!h->d_phys) return fail(RSX_ERR_STATE, "trace evaluation needs per-env physics (rsx_physics_enable)");
+    if (h->P.task != RSX_TASK_NONE) return fail(RSX_ERR_STATE, "trace evaluation runs on a raw handle: a task is attached");
+    if (!frames || !cmds || !anchors) return fail(RSX_ERR_ARG, "null argument");
+    if (n_frames < 2 || n_anchors < 1) return fail(RSX_ERR_ARG, "a trace needs n_frames >= 2 and n_anchors >= 1");
+    if (h->P.num_envs % n_anchors != 0) return fail(RSX_ERR_ARG, "num_envs must be a multiple of n_anchors");
+    const int rows = h->P.state_dim + X_ROWS, NC = h->P.n_robots * h->M.cmd_dim;
+    const size_t F = (size_t)n_frames, T = F - 1;
+    if ((size_t)rows * F * sizeof(float) >= ((size_t)1 << 32) || (size_t)NC * T * sizeof(float) >= ((size_t)1 << 32))
+        return fail(RSX_ERR_ARG, "trace too long: its arrays would reach 4 GB");
+    int amax = 0;
+    for (int a = 0; a < n_anchors; ++a) {
+        if (anchors[a] < 0 || anchors[a] > n_frames - 2) return fail(RSX_ERR_ARG, "anchor " + std::to_string(a) + " outside [0, n_frames - 2]");
+        amax = std::max(amax, (int)anchors[a]);
+    }
+    const size_t fbytes = align_up((size_t)rows * F * sizeof(float)), cbytes = align_up((size_t)NC * T * sizeof(float));
+    std::vector<char> host(fbytes + cbytes + (size_t)n_anchors * sizeof(int32_t), 0);
+    float* const hf = reinterpret_cast<float*>(host.data());
+    float* const hc = reinterpret_cast<float*>(host.data() + fbytes);
+    for (size_t f = 0; f < F; ++f)
+        for (int r = 0; r < rows; ++r) {
+            const double v = frames[f * rows + r];
+            if (!std::isfinite(v)) return fail(RSX_ERR_ARG, "non-finite value in frame " + std::to_string(f));
+            hf[(size_t)r * F + f] = (float)v;
+        }
+    for (size_t t = 0; t < T; ++t)
+        for (int j = 0; j < NC; ++j) {
+            const double v = cmds[t * NC + j];
+            if (!std::isfinite(v)) return fail(RSX_ERR_ARG, "non-finite value in the commands of step " + std::to_string(t));
+            hc[(size_t)j * T + t] = (float)v;
+        }
+    std::memcpy(host.data() + fbytes + cbytes, anchors, (size_t)n_anchors * sizeof(int32_t));
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipStreamSynchronize(s));   // a trace loaded before may still be read by a launch in flight
+    if (h->d_trace) { HIP_TRY(hipFree(h->d_trace)); h->d_trace = nullptr; h->trace_frames = 0; }
+    HIP_TRY(hipMalloc((void**)&h->d_trace, host.size()));
+    HIP_TRY(hipMemcpyAsync(h->d_trace, host.data(), host.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    h->trace_frames = n_frames; h->trace_anchors = n_anchors; h->trace_anchor_max = amax;
+    h->trace_cmds_off = fbytes; h->trace_anchors_off = fbytes + cbytes;
+    return RSX_OK;
+}
+
+int rsx_trace_eval(rsx_sim* h, int horizon, float* loss_dev, void* stream) {
+    RSX_ENTER(h);
+    if (!h->d_phys) return fail(RSX_ERR_STATE, "trace evaluation needs per-env physics (rsx_physics_enable)");
+    if (h->P.task != RSX_TASK_NONE) return fail(RSX_ERR_STATE, "trace evaluation runs on a raw handle: a task is attached");
+    if (!h->d_trace) return fail(RSX_ERR_STATE, "no trace loaded (rsx_trace_load)");
+    if (!loss_dev) return fail(RSX_ERR_ARG, "loss_dev is null");
+    if (horizon < 1 || (int64_t)h->trace_anchor_max + horizon > (int64_t)h->trace_frames - 1)
+        return fail(RSX_ERR_ARG, "horizon must be >= 1 and every anchor + horizon <= n_frames - 1");
+    h->host_state_valid = false;
+    const char* const base = reinterpret_cast<const char*>(h->d_trace);
+    launch_trace_eval(h->P, h->L, h->NR, h->d_phys, h->d_state, loss_dev, h->d_trace, reinterpret_cast<const float*>(base + h->trace_cmds_off),
+                      reinterpret_cast<const int32_t*>(base + h->trace_anchors_off), h->trace_frames, h->trace_anchors, horizon, (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return debug_finite(h, (hipStream_t)stream, "rsx_trace_eval");
 }
 
 }  // extern "C"

@@ -46,6 +46,12 @@ class _Sim:
             self._state = None    # handed out once: every call returns a fresh array, like robosim
         return s
 
+    def get_state_full(self):
+        """``get_state()`` followed by the two internal rows (ball vertical speed, ball spin): what a trace records
+        (rsoccer_amd.sysid) where the module has it"""
+        self._state = None
+        return self._sim.get_state_full()[0]
+
     def reset(self, ball_pos, blue_robots_pos, yellow_robots_pos):
         nb, ny = self.n_robots_blue, self.n_robots_yellow
         blue = np.asarray(blue_robots_pos, dtype=np.float64).reshape(nb, 3) if nb else None
