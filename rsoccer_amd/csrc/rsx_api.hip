@@ -5,8 +5,6 @@
 // reset at :38; field at :50; destroyed at :41).  HIP only: there is no CPU path in this library.
 #include <hip/hip_runtime.h>
 
-#include "rsx_launch.hpp"
-
 #include <cstdio>
 #include <cmath>
 #include <cstdlib>
@@ -16,27 +14,8 @@
 #include <vector>
 
 #include "rsx.h"
-#include "rsx_kernels.hpp"
-
-namespace rsx {
-// rsx_epl.hip (own translation unit, own compiler flags)
-void launch_vss_epl(bool rollout, const Params& P, const Buffers& b, int n_steps, hipStream_t s);
-void launch_ssl_epl(int task, bool rollout, const Params& P, const Buffers& b, int n_steps, hipStream_t s);
-// rsx_big.hip: the 32-lanes-per-env kernel of the SSL 11v11 scrimmage task built for large batches
-void launch_scrimmage_big(bool rollout, const Params& P, const Buffers& b, int n_steps, hipStream_t s);
-void launch_ssl_quad(const Params& P, const Buffers& b, int n_steps, hipStream_t s);   // rsx_quad_ssl.hpp: four lanes per env, single-step launches
-int ssl_quad_grid(int num_envs);   // workgroups of those launches
-int epl_grid(int num_envs);
-// rsx_phys.hip: the kernels of physics-enabled handles (rsx_physics_enable)
-void launch_task_phys(const Params& P, const Buffers& b, int L, int NR, float* phys, int n_steps, int mode, hipStream_t s);
-void launch_sim_phys(const Params& P, const Buffers& b, int L, int NR, float* phys, float* state_out, int rand_tick, hipStream_t s);
-void launch_phys_init(float* blk, int B, int S, int kind, int ts_ms, hipStream_t s);
-void launch_phys_set(float* blk, const float* vals, const uint8_t* mask, int B, int S, int vstride, hipStream_t s);
-void launch_phys_ranges(float* blk, const float* lo, const float* hi, uint32_t mask, hipStream_t s);
-// rsx_sysid.hip: trace evaluation (rsx_trace_eval)
-void launch_trace_eval(const Params& P, int L, int NR, const float* phys, float* state, float* loss, const float* frames,
-                       const float* cmds, const int32_t* anchors, int n_frames, int n_anchors, int horizon, hipStream_t s);
-}
+#include "rsx_units.hpp"
+#include "rsx_variants.hpp"
 
 using namespace rsx;
 
@@ -165,11 +144,10 @@ int pick_lanes(int n_bodies) {
     return L;
 }
 
-dim3 grid_for(const rsx_sim* h) {
-    const int G = 64 / h->L;
-    const int tiles = (h->P.num_envs + G - 1) / G;
-    return dim3((unsigned)(((tiles + 7) / 8) * 8));
-}
+// workgroups of the handle's lane-group launches, and the placement helpers behind them in a single-step launch of a handle
+// with a placement cache (rsx_task_attach: 8 lanes per env, exact robot count): one per 64 envs
+int grid_for(const rsx_sim* h) { return lane_grid(h->L, h->P.num_envs); }
+int helpers_for(const rsx_sim* h, int mode) { return mode == MODE_STEP && h->d_pcache ? (h->P.num_envs + 63) / 64 : 0; }
 
 #ifdef RSX_TIMING
 unsigned long long* g_dbg = nullptr;  // development builds: s_memtime stamps
@@ -204,46 +182,16 @@ Buffers buffers_of(const rsx_sim* h, const float* actions) {
     return b;
 }
 
-// Kernel variants: the common team sizes get the robot count as a template constant (pair
-// loops unrolled); anything else runs the generic variant of its lane-group width.
-void pick_variant(rsx_sim* h) {
-    const int N = h->P.n_robots;
-    h->NR = 0;
-    if (h->P.kind == RSX_KIND_VSS && N == 6 && (h->L == 8 || h->L == 16) && h->P.n_blue == 3) h->NR = 6;   // 16: RSX_LANES_PER_ENV=16 (four envs per wave)
-    if (h->P.kind == RSX_KIND_VSS && N == 10 && h->L == 16 && h->P.n_blue == 5) h->NR = 10;   // 5v5 field
-    if (h->P.kind == RSX_KIND_SSL && N == 7 && (h->L == 8 || h->L == 16)) h->NR = 7;
-    if (h->P.kind == RSX_KIND_SSL && N == 12 && h->L == 16) h->NR = 12;   // 6v6 (field_type 0, ssl/README.md:4)
-    if (h->P.kind == RSX_KIND_SSL && N == 22 && h->L == 32) h->NR = 22;
-}
-
-// hot arguments first (preloaded into SGPRs, see RSX_HOT_ARGS), then the by-value structs
-#define RSX_LAUNCH_SIM(kernel, P, b) rsx_launch((kernel), grid, dim3(64), 0, s, (b).state, state_out, (b).cmds, (b).flags, \
-                                                        (P).num_envs, RSX_HOT_DIM((P).state_dim, (P).row_stride, (P).num_envs), (int)(grid.x >> 3), rand_tick, (P), (b))
-#define RSX_LAUNCH(kernel, P, b, n) rsx_launch((kernel), grid, dim3(64), 0, s, (b).state, (b).aux, (b).actions, (b).flags, \
-                                                       (P).num_envs, RSX_HOT_DIM((P).state_dim, (P).row_stride, (P).num_envs), (int)(grid.x >> 3), (n), (P), (b))
-// the same with `extra` helper workgroups behind the tile workgroups (the tile map still sees the tile grid)
-#define RSX_LAUNCH_X(kernel, P, b, n, extra) rsx_launch((kernel), dim3(grid.x + (unsigned)(extra)), dim3(64), 0, s, (b).state, (b).aux, (b).actions, \
-                                                                (b).flags, (P).num_envs, RSX_HOT_DIM((P).state_dim, (P).row_stride, (P).num_envs), (int)(grid.x >> 3), (n), (P), (b))
-
 template <int KIND>
 void launch_sim_k(const rsx_sim* h, const Params& P_, float* state_out, int rand_tick, hipStream_t s,
                   const float* cmds_src, float* mirror) {
-    const dim3 grid = grid_for(h);
     Buffers b = buffers_of(h, nullptr);
     if (cmds_src) b.cmds = cmds_src;                      // commands straight from pinned host memory (small batches)
     b.flags = reinterpret_cast<uint8_t*>(mirror);         // the raw step's fourth pointer slot: second copy of the new state, or null
     if (h->d_phys) { launch_sim_phys(P_, b, h->L, h->NR, h->d_phys, state_out, rand_tick, s); return; }
-    if (KIND == RSX_KIND_VSS && h->NR == 6 && h->L == 8) { RSX_LAUNCH_SIM((sim_step_kernel<KIND, 8, (KIND == RSX_KIND_VSS ? 6 : 0)>), P_, b); return; }
-    if (KIND == RSX_KIND_VSS && h->NR == 10) { RSX_LAUNCH_SIM((sim_step_kernel<KIND, 16, (KIND == RSX_KIND_VSS ? 10 : 0)>), P_, b); return; }
-    if (KIND == RSX_KIND_SSL && h->NR == 7 && h->L == 8) { RSX_LAUNCH_SIM((sim_step_kernel<KIND, 8, (KIND == RSX_KIND_SSL ? 7 : 0)>), P_, b); return; }
-    if (KIND == RSX_KIND_SSL && h->NR == 12) { RSX_LAUNCH_SIM((sim_step_kernel<KIND, 16, (KIND == RSX_KIND_SSL ? 12 : 0)>), P_, b); return; }
-    if (KIND == RSX_KIND_SSL && h->NR == 22) { RSX_LAUNCH_SIM((sim_step_kernel<KIND, 32, (KIND == RSX_KIND_SSL ? 22 : 0)>), P_, b); return; }
-    switch (h->L) {
-        case 8: RSX_LAUNCH_SIM((sim_step_kernel<KIND, 8, 0>), P_, b); break;
-        case 16: RSX_LAUNCH_SIM((sim_step_kernel<KIND, 16, 0>), P_, b); break;
-        case 32: RSX_LAUNCH_SIM((sim_step_kernel<KIND, 32, 0>), P_, b); break;
-        default: RSX_LAUNCH_SIM((sim_step_kernel<KIND, 64, 0>), P_, b); break;
-    }
+    with_sim_variant<KIND, 64>(h->L, h->NR, [&](auto l, auto nr) {
+        launch_sim_hot((sim_step_kernel<KIND, l, nr>), {grid_for(h)}, s, state_out, rand_tick, P_, b);
+    });
 }
 
 // state_out: where the new state is written (nullptr = in place)
@@ -292,96 +240,40 @@ __global__ void wire_state_out_kernel(const float* __restrict__ st, double* __re
     wire[i] = (double)st[(size_t)f * S + e];
 }
 
-template <int KIND, int TASK, int NRS, int MODE>
+// One launch of the handle's task kernels.  First the layout rsx_task_attach chose for the handle's stepping launches (the flags
+// imply the team sizes and lanes per env their kernels are built for), then the lane-group variant of the shared table
+template <int KIND, int TASK, int NRS, bool FIXED, int MODE>
 void launch_task_m(const rsx_sim* h, const float* actions, int n_steps, hipStream_t s) {
+    constexpr bool STEPPING = MODE == MODE_STEP || MODE == MODE_ROLLOUT;
     const Buffers b = buffers_of(h, actions);
-    if (TASK == RSX_TASK_VSS_V0 && (MODE == MODE_STEP || MODE == MODE_ROLLOUT) && h->epl && h->NR == 6 && h->L == 8) {
-        launch_vss_epl(MODE == MODE_ROLLOUT, h->P, b, n_steps, s);
+    if (STEPPING && h->epl) {
+        if (TASK == RSX_TASK_VSS_V0) launch_vss_epl(MODE == MODE_ROLLOUT, h->P, b, n_steps, s);
+        else launch_ssl_epl(TASK, MODE == MODE_ROLLOUT, h->P, b, n_steps, s);
         return;
     }
-    if (TASK == RSX_TASK_SSL_STATIC_DEFENDERS && (MODE == MODE_STEP || MODE == MODE_ROLLOUT) && h->epl && h->NR == 7 && h->L == 8) {
-        launch_ssl_epl(TASK, MODE == MODE_ROLLOUT, h->P, b, n_steps, s);
-        return;
-    }
-    const dim3 grid = grid_for(h);
-    if (NRS <= 7 && h->NR == NRS && h->L == 8) {
-        // single-step launches of a handle with a placement cache: ceil(B / 64) helper workgroups behind the tiles
-        const int helpers = (MODE == MODE_STEP && h->d_pcache) ? (h->P.num_envs + 63) / 64 : 0;
-        RSX_LAUNCH_X((task_step_kernel<KIND, 8, TASK, (NRS <= 7 ? NRS : 0), MODE>), h->P, b, n_steps, helpers);
-        return;
-    }
-    if (NRS <= 7 && h->NR == NRS && h->L == 16) { RSX_LAUNCH((task_step_kernel<KIND, 16, TASK, (NRS <= 7 ? NRS : 0), MODE>), h->P, b, n_steps); return; }
-    if (TASK == RSX_TASK_SSL_SCRIMMAGE && h->NR == 22 && h->L == 32) {   // 11v11: robot count known at compile time
-        if (h->quad && MODE == MODE_STEP) { launch_ssl_quad(h->P, b, n_steps, s); return; }
-        if (h->big && (MODE == MODE_STEP || MODE == MODE_ROLLOUT)) { launch_scrimmage_big(MODE == MODE_ROLLOUT, h->P, b, n_steps, s); return; }
-        RSX_LAUNCH((task_step_kernel<KIND, 32, TASK, (TASK == RSX_TASK_SSL_SCRIMMAGE ? 22 : 0), MODE>), h->P, b, n_steps);
-        return;
-    }
-    if (TASK == RSX_TASK_VSS_V0 && h->NR == 10 && h->L == 16) {   // VSS-v0 on the 5v5 field
-        RSX_LAUNCH((task_step_kernel<KIND, 16, TASK, (TASK == RSX_TASK_VSS_V0 ? 10 : 0), MODE>), h->P, b, n_steps);
-        return;
-    }
-    switch (h->L) {
-        case 8: RSX_LAUNCH((task_step_kernel<KIND, 8, TASK, 0, MODE>), h->P, b, n_steps); break;
-        case 16: RSX_LAUNCH((task_step_kernel<KIND, 16, TASK, 0, MODE>), h->P, b, n_steps); break;
-        case 32: RSX_LAUNCH((task_step_kernel<KIND, 32, TASK, 0, MODE>), h->P, b, n_steps); break;
-        default: RSX_LAUNCH((task_step_kernel<KIND, 64, TASK, 0, MODE>), h->P, b, n_steps); break;
-    }
-}
-
-template <int KIND, int TASK, int NRS>
-void launch_task_k(const rsx_sim* h, const float* actions, int n_steps, int mode, hipStream_t s) {
-    switch (mode) {
-        case MODE_STEP: launch_task_m<KIND, TASK, NRS, MODE_STEP>(h, actions, n_steps, s); break;   // n_steps = 1 | flags
-        case MODE_ROLLOUT: launch_task_m<KIND, TASK, NRS, MODE_ROLLOUT>(h, nullptr, n_steps, s); break;
-        case MODE_RESET: launch_task_m<KIND, TASK, NRS, MODE_RESET>(h, nullptr, 1, s); break;
-        default: launch_task_m<KIND, TASK, NRS, MODE_REFRESH>(h, nullptr, 1, s); break;
-    }
-}
-
-// mode: MODE_STEP (one step, optional fed actions), MODE_ROLLOUT (n_steps in one launch),
-// MODE_RESET, MODE_REFRESH
-// tasks whose team sizes are fixed by the task: one variant each (8 lanes per env, exact robot count)
-template <int TASK, int NRS, int MODE>
-void launch_fixed_m(const rsx_sim* h, const float* actions, int n_steps, hipStream_t s) {
-    const dim3 grid = grid_for(h);
-    const Buffers b = buffers_of(h, actions);
-    if ((MODE == MODE_STEP || MODE == MODE_ROLLOUT) && h->epl) { launch_ssl_epl(TASK, MODE == MODE_ROLLOUT, h->P, b, n_steps, s); return; }
-    RSX_LAUNCH((task_step_kernel<RSX_KIND_SSL, 8, TASK, NRS, MODE>), h->P, b, n_steps);
-}
-template <int TASK, int NRS>
-void launch_fixed(const rsx_sim* h, const float* actions, int n_steps, int mode, hipStream_t s) {
-    switch (mode) {
-        case MODE_STEP: launch_fixed_m<TASK, NRS, MODE_STEP>(h, actions, n_steps, s); break;
-        case MODE_ROLLOUT: launch_fixed_m<TASK, NRS, MODE_ROLLOUT>(h, nullptr, n_steps, s); break;
-        case MODE_RESET: launch_fixed_m<TASK, NRS, MODE_RESET>(h, nullptr, 1, s); break;
-        default: launch_fixed_m<TASK, NRS, MODE_REFRESH>(h, nullptr, 1, s); break;
-    }
+    if (MODE == MODE_STEP && h->quad) { launch_ssl_quad(h->P, b, n_steps, s); return; }
+    if (STEPPING && h->big) { launch_scrimmage_big(MODE == MODE_ROLLOUT, h->P, b, n_steps, s); return; }
+    with_task_variant<TASK, NRS, FIXED, 64>(h->L, h->NR, [&](auto l, auto nr) {
+        launch_task_hot((task_step_kernel<KIND, l, TASK, nr, MODE>), {grid_for(h), helpers_for(h, MODE)}, s, n_steps, h->P, b);
+    });
 }
 
 void launch_task(const rsx_sim* h, const float* actions, int n_steps, int mode, hipStream_t s) {
-    if (h->d_phys) { launch_task_phys(h->P, buffers_of(h, mode == MODE_STEP ? actions : nullptr), h->L, h->NR, h->d_phys, n_steps, mode, s); return; }
-    switch (h->P.task) {
-        case RSX_TASK_VSS_V0: launch_task_k<RSX_KIND_VSS, RSX_TASK_VSS_V0, 6>(h, actions, n_steps, mode, s); break;
-        case RSX_TASK_SSL_STATIC_DEFENDERS: launch_task_k<RSX_KIND_SSL, RSX_TASK_SSL_STATIC_DEFENDERS, 7>(h, actions, n_steps, mode, s); break;
-        case RSX_TASK_SSL_DRIBBLING: launch_fixed<RSX_TASK_SSL_DRIBBLING, 5>(h, actions, n_steps, mode, s); break;
-        case RSX_TASK_SSL_CONTESTED: launch_fixed<RSX_TASK_SSL_CONTESTED, 2>(h, actions, n_steps, mode, s); break;
-        case RSX_TASK_SSL_SCRIMMAGE: case RSX_TASK_SSL_SCRIMMAGE_CROWDED:
-            launch_task_k<RSX_KIND_SSL, RSX_TASK_SSL_SCRIMMAGE, 22>(h, actions, n_steps, mode, s); break;
-        default: launch_fixed<RSX_TASK_SSL_PASS_ENDURANCE, 2>(h, actions, n_steps, mode, s); break;
-    }
+    actions = mode_actions(mode, actions);
+    if (h->d_phys) { launch_task_phys(h->P, buffers_of(h, actions), h->L, h->NR, h->d_phys, n_steps, mode, s); return; }
+    with_task(h->P.task, [&](auto kind, auto task, auto nrs, auto fixed) {
+        with_mode(mode, [&](auto m) { launch_task_m<kind, task, nrs, fixed, m>(h, actions, mode_steps(m, n_steps), s); });
+    });
 }
 
 // workgroups of the handle's stepping launches (MODE_STEP / MODE_ROLLOUT), mirroring the dispatch above: what the
 // per-workgroup tick slots of a device-keyed handle are sized and kept in sync by (rsx_kernels.hpp: step_tick)
 int step_grid(const rsx_sim* h, int mode) {
     const int B = h->P.num_envs;
-    if (h->d_phys) return (int)grid_for(h).x;   // (the per-env physics kernels: tiles only)
+    if (h->d_phys) return grid_for(h);   // (the per-env physics kernels: tiles only)
     if (h->epl) return epl_grid(B);
     if (h->quad && mode == MODE_STEP) return ssl_quad_grid(B);
-    int g = (int)grid_for(h).x;
-    if (mode == MODE_STEP && h->d_pcache) g += (B + 63) / 64;   // placement helpers behind the tiles
-    return g;
+    return grid_for(h) + helpers_for(h, mode);
 }
 uint32_t* tick_words(const rsx_sim* h) { return reinterpret_cast<uint32_t*>(h->d_metrics); }
 
@@ -578,7 +470,7 @@ int rsx_create(rsx_sim** out, int kind, int field_type, int n_blue, int n_yellow
     h->device = device_id;
     h->field_type = field_type; h->time_step_ms = time_step_ms;
     h->L = pick_lanes(h->P.n_robots + 1);
-    pick_variant(h);
+    h->NR = specialised_robots(h->P.kind, h->P.n_robots, h->P.n_blue, h->L);
     auto bail = [&](hipError_t e, const char* what) {
         std::string m = std::string(what) + ": " + hipGetErrorString(e);
         free_all(h); delete h;
@@ -882,7 +774,7 @@ int rsx_task_attach(rsx_sim* h, int task, uint64_t seed, uint64_t env_id_base, i
     const size_t n_act = align_up(B * h->M.act_dim * sizeof(float));
     // metrics[8] | error word | (256 bytes in) one step-counter slot per workgroup of the largest stepping launch any layout
     // of this batch could use (rsx_kernels.hpp: step_tick; only the first tick_slots are kept in sync)
-    const size_t n_met = align_up((size_t)TICK_SLOT_WORD0 * 4 + ((size_t)grid_for(h).x + (B + 63) / 64) * sizeof(uint32_t));
+    const size_t n_met = align_up((size_t)TICK_SLOT_WORD0 * 4 + ((size_t)grid_for(h) + (B + 63) / 64) * sizeof(uint32_t));
     const size_t n_slots = align_up((size_t)MSLOTS * RSX_METRICS * sizeof(unsigned long long));
     // placement cache: static defenders 1v6 (short episodes: several resetting waves per launch) at latency-bound batches
     const bool pc = !std::getenv("RSX_NO_PCACHE") && h->L == 8 && P.num_envs <= RSX_PCACHE_MAX_ENVS && P.n_sub > 0 &&
@@ -940,7 +832,7 @@ int rsx_task_attach(rsx_sim* h, int task, uint64_t seed, uint64_t env_id_base, i
     h->task_ready = false;
     h->tick_dev = false;
     h->tick_slots = step_grid(h, MODE_STEP);
-    h->tick_slots_alloc = std::max(h->tick_slots, (int)grid_for(h).x + (P.num_envs + 63) / 64);
+    h->tick_slots_alloc = std::max(h->tick_slots, grid_for(h) + (P.num_envs + 63) / 64);
     HIP_TRY(hipDeviceSynchronize());   // null-stream memsets done before any caller stream steps
     return RSX_OK;
 }

@@ -7,23 +7,18 @@
 // another symbol name, and the host picks by batch size (RSX_BIG_MIN_ENVS).  Same source, same results.
 #include <hip/hip_runtime.h>
 
-#include "rsx_launch.hpp"
-
 #define task_step_kernel task_step_kernel_big
 #include "rsx_kernels.hpp"
+
+#include "rsx_units.hpp"
+#include "rsx_variants.hpp"
 
 namespace rsx {
 
 void launch_scrimmage_big(bool rollout, const Params& P, const Buffers& b, int n_steps, hipStream_t s) {
-    constexpr int L = 32, G = 64 / L;
-    const int tiles = (P.num_envs + G - 1) / G;
-    const dim3 grid((unsigned)(((tiles + 7) / 8) * 8));
-    if (rollout)
-        rsx_launch((task_step_kernel_big<RSX_KIND_SSL, 32, RSX_TASK_SSL_SCRIMMAGE, 22, MODE_ROLLOUT>), grid, dim3(64), 0, s, b.state, b.aux,
-                           b.actions, b.flags, P.num_envs, RSX_HOT_DIM(P.state_dim, P.row_stride, P.num_envs), (int)(grid.x >> 3), n_steps, P, b);
-    else
-        rsx_launch((task_step_kernel_big<RSX_KIND_SSL, 32, RSX_TASK_SSL_SCRIMMAGE, 22, MODE_STEP>), grid, dim3(64), 0, s, b.state, b.aux,
-                           b.actions, b.flags, P.num_envs, RSX_HOT_DIM(P.state_dim, P.row_stride, P.num_envs), (int)(grid.x >> 3), n_steps, P, b);
+    const HotGrid grid{lane_grid(32, P.num_envs)};
+    if (rollout) launch_task_hot((task_step_kernel_big<RSX_KIND_SSL, 32, RSX_TASK_SSL_SCRIMMAGE, 22, MODE_ROLLOUT>), grid, s, n_steps, P, b);
+    else launch_task_hot((task_step_kernel_big<RSX_KIND_SSL, 32, RSX_TASK_SSL_SCRIMMAGE, 22, MODE_STEP>), grid, s, n_steps, P, b);
 }
 
 }  // namespace rsx

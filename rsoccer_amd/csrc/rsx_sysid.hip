@@ -3,7 +3,7 @@
 //
 // trace_eval_phys_kernel runs, per env, `horizon` raw simulator steps from an anchor frame of a recorded trace with the env's own
 // physics coefficients (rsx_phys.hpp: EnvCoef), all in registers, and sums the squared deviation of every body from the trace's
-// next frame after each step.  Lanes per env and variants are those of sim_step_phys_kernel (rsx_phys.hip: sim_k).
+// next frame after each step.  Lanes per env and variants are those of sim_step_phys_kernel (rsx_variants.hpp: with_sim_variant).
 //
 // Between two steps the lane's record goes through exactly what a store_body -> load_raw -> interpret_body round trip applies
 // (wire_of below, then interpret_body): heading kept in degrees, rate stored in deg/s and converted back, ball height stored as
@@ -14,9 +14,9 @@
 // an anchor reads the same frames: they stay L2-resident.
 #include <hip/hip_runtime.h>
 
-#include "rsx_launch.hpp"
 #include "rsx.h"
-#include "rsx_kernels.hpp"
+#include "rsx_units.hpp"
+#include "rsx_variants.hpp"
 
 namespace rsx {
 
@@ -143,28 +143,13 @@ __global__ __launch_bounds__(64) void trace_eval_phys_kernel(float* __restrict__
     }
 }
 
-dim3 grid_of(const int L, const int B) {   // = grid_for in rsx_api.hip
-    const int G = 64 / L;
-    const int tiles = (B + G - 1) / G;
-    return dim3((unsigned)(((tiles + 7) / 8) * 8));
-}
-
 template <int KIND>
 void trace_k(const Params& P, const int L, const int NR, const float* phys, float* state, float* loss, const TraceArgs& tr,
              const int horizon, hipStream_t s) {
-    const dim3 grid = grid_of(L, P.num_envs);
-#define RSX_LAUNCH_TRACE(kernel) rsx_launch((kernel), grid, dim3(64), 0, s, state, loss, (int)(grid.x >> 3), horizon, P, phys, tr)
-    if (KIND == RSX_KIND_VSS && NR == 6 && L == 8) { RSX_LAUNCH_TRACE((trace_eval_phys_kernel<KIND, 8, (KIND == RSX_KIND_VSS ? 6 : 0)>)); return; }
-    if (KIND == RSX_KIND_VSS && NR == 10) { RSX_LAUNCH_TRACE((trace_eval_phys_kernel<KIND, 16, (KIND == RSX_KIND_VSS ? 10 : 0)>)); return; }
-    if (KIND == RSX_KIND_SSL && NR == 7 && L == 8) { RSX_LAUNCH_TRACE((trace_eval_phys_kernel<KIND, 8, (KIND == RSX_KIND_SSL ? 7 : 0)>)); return; }
-    if (KIND == RSX_KIND_SSL && NR == 12) { RSX_LAUNCH_TRACE((trace_eval_phys_kernel<KIND, 16, (KIND == RSX_KIND_SSL ? 12 : 0)>)); return; }
-    if (KIND == RSX_KIND_SSL && NR == 22) { RSX_LAUNCH_TRACE((trace_eval_phys_kernel<KIND, 32, (KIND == RSX_KIND_SSL ? 22 : 0)>)); return; }
-    switch (L) {   // (64 lanes per env: refused by rsx_physics_enable)
-        case 8: RSX_LAUNCH_TRACE((trace_eval_phys_kernel<KIND, 8, 0>)); break;
-        case 16: RSX_LAUNCH_TRACE((trace_eval_phys_kernel<KIND, 16, 0>)); break;
-        default: RSX_LAUNCH_TRACE((trace_eval_phys_kernel<KIND, 32, 0>)); break;
-    }
-#undef RSX_LAUNCH_TRACE
+    const int grid = lane_grid(L, P.num_envs);
+    with_sim_variant<KIND, 32>(L, NR, [&](auto l, auto nr) {
+        rsx_launch((trace_eval_phys_kernel<KIND, l, nr>), dim3((unsigned)grid), dim3(64), 0, s, state, loss, grid >> 3, horizon, P, phys, tr);
+    });
 }
 
 }  // namespace

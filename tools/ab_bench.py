@@ -40,4 +40,6 @@ for arg in sys.argv[1:]:
     lib, _, sets = arg.partition(":")
     extra = dict(kv.split("=", 1) for kv in sets.split(",") if kv)
     print("==", arg, flush=True)
-    subprocess.run([sys.executable, "-c", CHILD], env=dict(os.environ, RSX_LIB=os.path.abspath(lib), **extra))
+    rc = subprocess.run([sys.executable, "-c", CHILD], env=dict(os.environ, RSX_LIB=os.path.abspath(lib), **extra)).returncode
+    if rc:   # a build that failed or faulted: nothing more is started on the device
+        sys.exit(f"{arg}: exit status {rc}")

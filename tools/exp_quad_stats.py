@@ -1,5 +1,5 @@
 """Development: what the contact path of the four-lanes-per-env 11v11 kernel does per sub-step (counters of a
--DRSX_QSTATS build: tools/build_variant.sh qstats -DRSX_QSTATS; RSX_LIB=tools/_dev/librsx_qstats.so RSX_LAYOUT=quad)."""
+-DRSX_QSTATS build: python tools/build_variant.py qstats -DRSX_QSTATS; RSX_LIB=tools/_dev/librsx_qstats.so RSX_LAYOUT=quad)."""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.getcwd())
 import torch

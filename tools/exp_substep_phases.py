@@ -1,6 +1,6 @@
 """Development: where the cycles of a sub-step go in the lane-group kernels (A: actuation + integration, B: contacts incl. the
 LDS exchange, C: walls + the closing wave_sync), sub-steps 1.. of single-step launches.  Needs a -DRSX_TIMING -DRSX_TIMING_SUB
-build (tools/build_variant.sh subt -DRSX_TIMING -DRSX_TIMING_SUB; RSX_LIB=tools/_dev/librsx_subt.so); CFG / B / LANES as in
+build (python tools/build_variant.py subt -DRSX_TIMING -DRSX_TIMING_SUB; RSX_LIB=tools/_dev/librsx_subt.so); CFG / B / LANES as in
 exp_timeline2.py.  The stamps (s_memtime + a wait on lgkmcnt) add ~5 % to the sub-step themselves."""
 import os, sys, ctypes
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,5 +1,6 @@
 """In-kernel timeline incl. per-sub-step stamps, single-step launch vs the last step of a
-multi-step launch (needs the -DRSX_TIMING build of tools/build_timing.sh: RSX_LIB=tools/_dev/librsx_hip_timing.so)."""
+multi-step launch (needs the -DRSX_TIMING build, python tools/build_variant.py hip_timing -DRSX_TIMING:
+RSX_LIB=tools/_dev/librsx_hip_timing.so)."""
 import os, sys, ctypes
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

@@ -1,4 +1,5 @@
-"""In-kernel timeline of the SSL one-lane-per-env kernel (needs tools/build_timing.sh; RSX_LIB=tools/_dev/librsx_hip_timing.so).
+"""In-kernel timeline of the SSL one-lane-per-env kernel (needs python tools/build_variant.py hip_timing -DRSX_TIMING;
+RSX_LIB=tools/_dev/librsx_hip_timing.so).
 usage: B=65536 TASK=6 python tools/exp_timeline_epl.py"""
 import os, sys, ctypes
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

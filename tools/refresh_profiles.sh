@@ -64,7 +64,7 @@ find $OUT/hooks -name "*memory_copy_stats.csv" -o -name "*memory_copy_trace.csv"
   for f in $(find $OUT/hooks -name "*memory_copy_trace.csv" | head -1); do echo "memory copies in the whole run: $(($(wc -l < $f) - 1))"; python tools/memcopy_window.py $f $OUT/hooks; done ) > $OUT/hooks_memcopy.txt 2>&1
 cat $OUT/hooks_memcopy.txt
 # in-kernel timeline of the headline kernel
-tools/build_timing.sh > /dev/null 2>&1 && RSX_LIB=tools/_dev/librsx_hip_timing.so python tools/exp_timeline2.py > $OUT/timeline.txt 2>&1
+python tools/build_variant.py hip_timing -DRSX_TIMING > /dev/null 2>&1 && RSX_LIB=tools/_dev/librsx_hip_timing.so python tools/exp_timeline2.py > $OUT/timeline.txt 2>&1
 head -40 $OUT/timeline.txt
 for t in 2 3 5; do echo "== task $t, 1 048 576 envs, one lane per env"; RSX_LIB=tools/_dev/librsx_hip_timing.so B=1048576 TASK=$t python tools/exp_timeline_epl.py 2>&1 | grep -v amdgpu; done > $OUT/timeline_ssl_epl_1M.txt
 cat $OUT/timeline_ssl_epl_1M.txt
