@@ -439,6 +439,43 @@ int rsx_trace_load(rsx_sim* h, const double* frames, const double* cmds, int n_f
  * loss_dev null. */
 int rsx_trace_eval(rsx_sim* h, int horizon, float* loss_dev, void* stream);
 
+/* ---- batched rgb frames (additive extension of ABI 6) ----------------------------------------------------------------
+ * render() of the base envs (vss_gym_base.py:108-181, ssl_gym_base.py:108-181) for a whole batch, on the device: frame i is the
+ * top-down picture of one env's current state, uint8 rgb, drawn by the rules of rsoccer_amd/Render/raster.py (same window
+ * geometry, same world -> pixel map px = x * scale + centre, no y flip, same drawing order: field, blue robots by id, yellow
+ * robots, ball; each robot its body and then its heading mark).  The static field is drawn once per view on the host in double
+ * precision and equals FieldRaster(view)._field byte for byte; the bodies are evaluated per pixel in float32.  One deliberate
+ * difference: pixels of a body or a heading mark that fall outside the window are dropped (raster.py clamps the samples of a
+ * heading mark onto the border). */
+typedef struct rsx_render_view {   /* the keys of Render/raster.py's VSS_VIEW / SSL_VIEW, metres unless noted */
+    double length, width, margin, circle, pen_len, pen_wid, goal_wid, goal_dep;
+    double scale;                  /* pixels per metre */
+    double robot, ball;            /* drawn radii */
+    int32_t square;                /* 1: robots are rotated squares (VSS), 0: discs (SSL) */
+} rsx_render_view;
+/* The reference's fixed window of a robot class (raster.py: VSS_VIEW / SSL_VIEW).  No device needed. */
+int rsx_render_view_reference(int kind, rsx_render_view* out);
+/* Frame size of a view: width = int(length * scale + 2 * (margin * scale)), height likewise from `width`.  A view is valid when
+ * every value is finite, scale > 0 and both sides are between 8 and 4096 pixels; RSX_ERR_ARG otherwise.  No device needed. */
+int rsx_render_size(const rsx_render_view* v, int* width, int* height);
+/* The static field image of a view, out_hwc [height][width][3] host memory.  No device needed. */
+int rsx_render_field(const rsx_render_view* v, uint8_t* out_hwc);
+/* Make `v` the view rsx_render draws (raw handles and handles with a task alike).  A view the handle has not been given before is
+ * checked (RSX_ERR_ARG), its field drawn on the host and uploaded as a background template: that synchronises `stream` and is refused
+ * inside a stream capture (RSX_ERR_STATE).  A view the handle was given before is only selected: no allocation, no copy, no
+ * synchronisation.  Templates are never freed or moved before rsx_destroy — a captured rsx_render holds its view's template and
+ * geometry in the graph, and keeps drawing THAT view on every replay, whatever rsx_render_open selects in between — so a handle takes
+ * at most 16 different views (RSX_ERR_STATE beyond).  Handles that never call it allocate nothing for it. */
+int rsx_render_open(rsx_sim* h, const rsx_render_view* v, void* stream);
+/* One launch: n frames of the CURRENT state buffer (the one rsx_state_buffers reports as current) into out_dev — [n][H][W][3]
+ * uint8, or [n][3][H][W] with channels_first != 0; dense, 16-byte aligned (RSX_ERR_ARG otherwise).  Frame i shows env
+ * env_ids_dev[i] (device int32 [n]; NULL = envs 0..n-1, then n <= num_envs); any order, duplicates allowed.  An id outside
+ * [0, num_envs) leaves its frame as the bare field and is counted (rsx_render_errors).  Stream-ordered, never synchronises, holds
+ * no host state (capturable into a hipGraph); reads the state, writes nothing but out_dev.  RSX_ERR_STATE before rsx_render_open. */
+int rsx_render(rsx_sim* h, const int32_t* env_ids_dev, int n, int channels_first, uint8_t* out_dev, void* stream);
+/* frames with an out-of-range env id since the last read (read and cleared; synchronises `stream`). */
+int rsx_render_errors(rsx_sim* h, int64_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

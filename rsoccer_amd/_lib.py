@@ -48,6 +48,7 @@ SYMBOLS = (
     "rsx_physics_defaults", "rsx_physics_derive", "rsx_physics_enable", "rsx_physics_set", "rsx_physics_get",
     "rsx_physics_randomize", "rsx_physics_errors",
     "rsx_trace_load", "rsx_trace_eval",
+    "rsx_render_view_reference", "rsx_render_size", "rsx_render_field", "rsx_render_open", "rsx_render", "rsx_render_errors",
 )
 
 
@@ -66,6 +67,27 @@ class TaskView(C.Structure):
                 ("obs", C.c_void_p), ("reward", C.c_void_p), ("terminated", C.c_void_p),
                 ("truncated", C.c_void_p), ("info", C.c_void_p), ("final_obs", C.c_void_p),
                 ("steps", C.c_void_p), ("actions", C.c_void_p), ("metrics", C.c_void_p), ("row_stride", C.c_int32)]
+
+
+# the keys of Render/raster.py's view dicts, in the order of rsx_render_view
+RENDER_VIEW_KEYS = ("length", "width", "margin", "circle", "pen_len", "pen_wid", "goal_wid", "goal_dep", "scale", "robot", "ball", "square")
+
+
+class RenderView(C.Structure):
+    _fields_ = [(k, C.c_double) for k in RENDER_VIEW_KEYS[:-1]] + [("square", C.c_int32)]
+
+    @classmethod
+    def from_dict(cls, view):
+        """a view dict in raster.py's format (VSS_VIEW / SSL_VIEW) as the C struct"""
+        missing = [k for k in RENDER_VIEW_KEYS if k not in view]
+        if missing:
+            raise ValueError(f"render view lacks {missing}")
+        return cls(*[float(view[k]) for k in RENDER_VIEW_KEYS[:-1]], 1 if view["square"] else 0)
+
+    def to_dict(self):
+        d = {k: float(getattr(self, k)) for k in RENDER_VIEW_KEYS[:-1]}
+        d["square"] = bool(self.square)
+        return d
 
 
 _lib = None
@@ -134,6 +156,12 @@ def load():
     lib.rsx_physics_errors.argtypes = [vp, C.POINTER(C.c_int64), vp]
     lib.rsx_trace_load.argtypes = [vp, vp, vp, ip, vp, ip, vp]
     lib.rsx_trace_eval.argtypes = [vp, ip, vp, vp]
+    lib.rsx_render_view_reference.argtypes = [ip, C.POINTER(RenderView)]
+    lib.rsx_render_size.argtypes = [C.POINTER(RenderView), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.rsx_render_field.argtypes = [C.POINTER(RenderView), vp]
+    lib.rsx_render_open.argtypes = [vp, C.POINTER(RenderView), vp]
+    lib.rsx_render.argtypes = [vp, vp, ip, ip, vp, vp]
+    lib.rsx_render_errors.argtypes = [vp, C.POINTER(C.c_int64), vp]
     if lib.rsx_abi_version() != 6:
         raise RsxError("librsx_hip.so ABI version mismatch")
     _lib = lib
@@ -519,6 +547,37 @@ class Sim:
             raise ValueError(f"loss must be a contiguous float32 tensor of shape {(len(TRACE_TERMS), self.num_envs)}")
         _chk(self._lib.rsx_trace_eval(self._h, int(horizon), C.c_void_p(loss.data_ptr()), self._stream(stream)))
 
+    # ---- batched rgb frames (include/rsx.h: rsx_render_*; rsoccer_amd/vec/render.py) ----
+    _render_key = None   # the view rsx_render draws (the values of RENDER_VIEW_KEYS), and its frame size
+    _render_hw = None
+
+    def render_open(self, view, stream=None, key=None):
+        """make ``view`` (a dict in ``Render/raster.py``'s format or a ``RenderView``) the one ``render`` draws; returns the frame size
+        (H, W).  A view the handle has not seen is drawn on the host and uploaded (synchronises; not inside a capture); one it has
+        seen is only selected, and the view already current costs no FFI crossing.  Views stay allocated until ``close()`` — a
+        captured ``render`` keeps drawing the view it was captured with — so a handle takes at most 16 different ones.
+        ``key``: the view's values as a tuple, for callers that keep it (``vec/render.py``)."""
+        v = view if isinstance(view, RenderView) else RenderView.from_dict(view)
+        if key is None:
+            key = tuple(getattr(v, k) for k in RENDER_VIEW_KEYS)
+        if key != self._render_key:
+            _chk(self._lib.rsx_render_open(self._h, C.byref(v), self._stream(stream)))
+            self._render_key, self._render_hw = key, render_size(v)
+        return self._render_hw
+
+    def render(self, env_ids_ptr, n, channels_first, out_ptr, stream=None):
+        """one launch: ``n`` frames of the current state into the device buffer at ``out_ptr`` ([n, H, W, 3] uint8, or [n, 3, H, W]);
+        ``env_ids_ptr``: device address of ``n`` int32 env ids, or None = envs 0..n-1.  Plain ints go straight to ctypes."""
+        rc = self._lib.rsx_render(self._h, env_ids_ptr, n, 1 if channels_first else 0, out_ptr, stream)
+        if rc:
+            _chk(rc)
+
+    def render_errors(self, stream=None):
+        """frames whose env id was out of range since the last call (they show the bare field)"""
+        n = C.c_int64(0)
+        _chk(self._lib.rsx_render_errors(self._h, C.byref(n), self._stream(stream)))
+        return int(n.value)
+
     def metrics_fold(self, stream=None):
         """make the device copy of the episode counters (``task_tensors()["metrics"]``) exact, on ``stream``"""
         _chk(self._lib.rsx_metrics_fold(self._h, self._stream(stream)))
@@ -547,4 +606,28 @@ def physics_derive(kind, time_step_ms, raw):
         raise ValueError(f"expected {len(PHYSICS_PARAMS)} parameters, got {raw.shape}")
     out = np.zeros(len(PHYSICS_COEFS), dtype=np.float32)
     _chk(load().rsx_physics_derive(int(kind), int(time_step_ms), _ptr(raw), _ptr(out)))
+    return out
+
+
+def render_view_reference(kind):
+    """the reference's fixed window of a robot class as a view dict (rsx_render_view_reference): raster.py's VSS_VIEW / SSL_VIEW"""
+    v = RenderView()
+    _chk(load().rsx_render_view_reference(int(kind), C.byref(v)))
+    return v.to_dict()
+
+
+def render_size(view):
+    """(H, W) of the frames of a view (rsx_render_size); RsxError for an invalid view.  No device needed."""
+    v = view if isinstance(view, RenderView) else RenderView.from_dict(view)
+    w, h = C.c_int(0), C.c_int(0)
+    _chk(load().rsx_render_size(C.byref(v), C.byref(w), C.byref(h)))
+    return int(h.value), int(w.value)
+
+
+def render_field(view):
+    """the static field image of a view, uint8 [H, W, 3] (rsx_render_field): equals ``FieldRaster(view)._field``.  No device needed."""
+    v = view if isinstance(view, RenderView) else RenderView.from_dict(view)
+    h, w = render_size(v)
+    out = np.empty((h, w, 3), dtype=np.uint8)
+    _chk(load().rsx_render_field(C.byref(v), _ptr(out)))
     return out

@@ -128,6 +128,17 @@ struct rsx_sim {
     float* d_trace = nullptr;
     int trace_frames = 0, trace_anchors = 0, trace_anchor_max = 0;
     size_t trace_cmds_off = 0, trace_anchors_off = 0;   // byte offsets into d_trace
+    // rsx_render_open: every view the handle was ever given stays allocated until rsx_destroy (a captured rsx_render holds its view's
+    // template pointer in the graph); d_render_err: the error word all of them share.  render_cur: the view rsx_render draws, or -1
+    struct RenderSlot {
+        rsx_render_view view;
+        RenderGeom geom;
+        uint8_t* tpl;        // one allocation: field image [H][W][3] | the same as planes [3][H][W]
+        size_t tpl_bytes;    // size of each
+    };
+    std::vector<RenderSlot> render_views;
+    int render_cur = -1;
+    uint32_t* d_render_err = nullptr;
     int tick_slots_alloc = 0;                 // slots allocated (the largest grid any layout of this batch could launch): rsx_task_enable_capture and
                                               // rsx_task_checkpoint_load write ALL of them, so that no grid ever reads a slot nobody has set
 };
@@ -372,6 +383,10 @@ void free_all(rsx_sim* h) {
     h->d_phys = nullptr;
     if (h->d_trace) (void)hipFree(h->d_trace);
     h->d_trace = nullptr;
+    for (auto& rv : h->render_views) (void)hipFree(rv.tpl);
+    h->render_views.clear(); h->render_cur = -1;
+    if (h->d_render_err) (void)hipFree(h->d_render_err);
+    h->d_render_err = nullptr;
     if (h->arena_sim) (void)hipFree(h->arena_sim);
     if (h->arena_task) (void)hipFree(h->arena_task);
     h->arena_sim = h->arena_task = nullptr;
@@ -1375,6 +1390,102 @@ int rsx_trace_eval(rsx_sim* h, int horizon, float* loss_dev, void* stream) {
                       reinterpret_cast<const int32_t*>(base + h->trace_anchors_off), h->trace_frames, h->trace_anchors, horizon, (hipStream_t)stream);
     HIP_TRY(launch_status());
     return debug_finite(h, (hipStream_t)stream, "rsx_trace_eval");
+}
+
+// ---- batched rgb frames (rsx.h: rsx_render_*; field image and kernel: rsx_render.hip) ----
+int rsx_render_view_reference(int kind, rsx_render_view* out) {
+    if (!out || (kind != RSX_KIND_VSS && kind != RSX_KIND_SSL)) return fail(RSX_ERR_ARG, "out is null or `kind` unknown");
+    // Render/raster.py: VSS_VIEW / SSL_VIEW (raster.py is the specification and stays as it is, so the values stand here once more;
+    // tests/test_render_batch.py::test_views holds the two, and Render.reference_view, together)
+    if (kind == RSX_KIND_VSS) *out = rsx_render_view{1.5, 1.3, 0.1, 0.2, 0.15, 0.7, 0.4, 0.1, 500.0, 0.04, 0.0215, 1};
+    else *out = rsx_render_view{9.0, 6.0, 0.35, 1.0, 1.0, 2.0, 1.0, 0.18, 100.0, 0.09, 0.0215, 0};
+    return RSX_OK;
+}
+
+int rsx_render_size(const rsx_render_view* v, int* width, int* height) {
+    if (!width || !height) return fail(RSX_ERR_ARG, "null argument");
+    if (const char* msg = render_check_view(v, width, height)) return fail(RSX_ERR_ARG, msg);
+    return RSX_OK;
+}
+
+int rsx_render_field(const rsx_render_view* v, uint8_t* out_hwc) {
+    int W = 0, H = 0;
+    if (const char* msg = render_check_view(v, &W, &H)) return fail(RSX_ERR_ARG, msg);
+    if (!out_hwc) return fail(RSX_ERR_ARG, "out_hwc is null");
+    render_field_host(*v, W, H, out_hwc);
+    return RSX_OK;
+}
+
+// views a handle may hold (none is freed before rsx_destroy: see rsx_sim::render_views)
+#ifndef RSX_RENDER_MAX_VIEWS
+#define RSX_RENDER_MAX_VIEWS 16
+#endif
+
+int rsx_render_open(rsx_sim* h, const rsx_render_view* v, void* stream) {
+    RSX_ENTER(h);
+    int W = 0, H = 0;
+    if (const char* msg = render_check_view(v, &W, &H)) return fail(RSX_ERR_ARG, msg);
+    for (size_t i = 0; i < h->render_views.size(); ++i) {   // a view the handle already holds: selected, nothing else happens
+        const rsx_render_view& o = h->render_views[i].view;
+        if (o.length == v->length && o.width == v->width && o.margin == v->margin && o.circle == v->circle && o.pen_len == v->pen_len &&
+            o.pen_wid == v->pen_wid && o.goal_wid == v->goal_wid && o.goal_dep == v->goal_dep && o.scale == v->scale &&
+            o.robot == v->robot && o.ball == v->ball && o.square == v->square) {
+            h->render_cur = (int)i;
+            return RSX_OK;
+        }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    {   // a new view allocates, uploads and synchronises: not inside a capture
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
+        else if (cs != hipStreamCaptureStatusNone) return fail(RSX_ERR_STATE, "rsx_render_open of a new view cannot be captured: open it before the capture");
+    }
+    if ((int)h->render_views.size() >= RSX_RENDER_MAX_VIEWS)
+        return fail(RSX_ERR_STATE, "the handle holds " + std::to_string(RSX_RENDER_MAX_VIEWS) + " render views already (views live until rsx_destroy: captured launches may read them)");
+    const size_t HW = (size_t)W * (size_t)H, fb = 3 * HW, tpl = align_up(fb);
+    std::vector<uint8_t> host(2 * tpl, 0);
+    uint8_t* const hwc = host.data();
+    uint8_t* const chw = hwc + tpl;
+    render_field_host(*v, W, H, hwc);
+    for (size_t p = 0; p < HW; ++p)
+        for (size_t c = 0; c < 3; ++c) chw[c * HW + p] = hwc[3 * p + c];
+    if (!h->d_render_err) {
+        HIP_TRY(hipMalloc((void**)&h->d_render_err, 256));
+        HIP_TRY(hipMemsetAsync(h->d_render_err, 0, 256, s));
+    }
+    rsx_sim::RenderSlot rv{*v, render_geom(*v, W, H), nullptr, tpl};
+    HIP_TRY(hipMalloc((void**)&rv.tpl, host.size()));
+    hipError_t e = hipMemcpyAsync(rv.tpl, host.data(), host.size(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { (void)hipFree(rv.tpl); return fail(RSX_ERR_HIP, std::string("rsx_render_open upload: ") + hipGetErrorString(e)); }
+    h->render_views.push_back(rv);
+    h->render_cur = (int)h->render_views.size() - 1;
+    return RSX_OK;
+}
+
+int rsx_render(rsx_sim* h, const int32_t* env_ids_dev, int n, int channels_first, uint8_t* out_dev, void* stream) {
+    RSX_ENTER(h);
+    if (h->render_cur < 0) return fail(RSX_ERR_STATE, "no render view (rsx_render_open)");
+    if (!out_dev || ((uintptr_t)out_dev & 15u)) return fail(RSX_ERR_ARG, "out_dev must be a 16-byte aligned device pointer");
+    if (n < 1 || (!env_ids_dev && n > h->P.num_envs)) return fail(RSX_ERR_ARG, "n must be >= 1, and <= num_envs without env_ids_dev");
+    const rsx_sim::RenderSlot& rv = h->render_views[(size_t)h->render_cur];
+    launch_render(rv.geom, h->d_state, h->P.num_envs, h->P.row_stride, h->P.kind, h->P.n_blue, h->P.n_yellow,
+                  rv.tpl + (channels_first ? rv.tpl_bytes : 0), h->d_render_err, env_ids_dev, n, channels_first != 0, out_dev, (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
+int rsx_render_errors(rsx_sim* h, int64_t* out, void* stream) {
+    RSX_ENTER(h);
+    if (!h->d_render_err) return fail(RSX_ERR_STATE, "no render view (rsx_render_open)");
+    if (!out) return fail(RSX_ERR_ARG, "out is null");
+    hipStream_t s = (hipStream_t)stream;
+    uint32_t v = 0;
+    HIP_TRY(hipMemcpyAsync(&v, h->d_render_err, sizeof(v), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemsetAsync(h->d_render_err, 0, sizeof(uint32_t), s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *out = (int64_t)v;
+    return RSX_OK;
 }
 
 }  // extern "C"

@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+struct rsx_render_view;   // include/rsx.h
+
 namespace rsx {
 
 struct Params;
@@ -29,5 +31,13 @@ void launch_phys_ranges(float* blk, const float* lo, const float* hi, uint32_t m
 // rsx_sysid.hip: trace evaluation (rsx_trace_eval)
 void launch_trace_eval(const Params& P, int L, int NR, const float* phys, float* state, float* loss, const float* frames,
                        const float* cmds, const int32_t* anchors, int n_frames, int n_anchors, int horizon, hipStream_t s);
+// rsx_render.hip: batched rgb frames (rsx_render_*).  render_check_view: nullptr when the view is valid (and the frame size), else the
+// message; render_field_host: the static field image [H][W][3]; RenderGeom: what the kernel needs of a view, in float32
+struct RenderGeom { int W, H; float s, cx, cy, r, rb; int square; };
+const char* render_check_view(const rsx_render_view* v, int* W, int* H);
+void render_field_host(const rsx_render_view& v, int W, int H, uint8_t* out_hwc);
+RenderGeom render_geom(const rsx_render_view& v, int W, int H);
+void launch_render(const RenderGeom& g, const float* state, int num_envs, int row_stride, int kind, int n_blue, int n_yellow,
+                   const uint8_t* tpl, uint32_t* err, const int32_t* env_ids, int n, int channels_first, uint8_t* out, hipStream_t s);
 
 }  // namespace rsx

@@ -3,6 +3,7 @@ import numpy as np
 
 from rsoccer_amd import _lib
 from rsoccer_amd import gymshim as gym
+from rsoccer_amd.vec.render import RenderMixin
 
 _VSS_INFO = ("goal_score", "move", "ball_grad", "energy", "goals_blue", "goals_yellow")
 _SD_INFO = ("goal", "rbt_in_gk_area", "done_ball_out", "done_ball_out_right", "done_rbt_out",
@@ -16,7 +17,7 @@ def batched_space(single, n):
     return gym.spaces.Box(low=low, high=high, shape=(n,) + tuple(single.shape), dtype=single.dtype)
 
 
-class VecFusedEnv:
+class VecFusedEnv(RenderMixin):
     """``num_envs`` copies of a fused task on one GPU.
 
     ``reset()`` -> ``(obs, info)``; ``step(actions)`` -> ``(obs, reward, terminated, truncated,
@@ -272,7 +273,8 @@ class VecFusedEnv:
 
     @property
     def state(self):
-        """[state_dim + 2, num_envs] float32 view of the SoA simulator state — for READING (frames for logging, rendering, analysis).
+        """[state_dim + 2, num_envs] float32 view of the SoA simulator state — for READING (logging, analysis; pictures of the envs
+        come from ``render()``, on the device).
         Writing it moves bodies behind the task's back: observations and per-episode task scalars are not refreshed (include/rsx.h:
         rsx_set_state); to re-place envs use ``reset_to``."""
         return self.sim.state_tensor()
@@ -327,6 +329,7 @@ class VecSSLScrimmageEnv(VecFusedEnv):
     the ball (worst-case all-pairs contacts)."""
     KIND = _lib.KIND_SSL
     INFO_KEYS = ("goals_blue", "goals_yellow")
+    RENDER_VIEW = "field"   # division A / B: the reference's fixed 9 x 6 m window does not contain the field
 
     def __init__(self, num_envs, n_blue=11, n_yellow=11, field_type=1, crowded=False, **kw):
         self.N_BLUE, self.N_YELLOW, self.FIELD_TYPE = int(n_blue), int(n_yellow), int(field_type)

@@ -12,6 +12,7 @@ import numpy as np
 
 from rsoccer_amd import _lib
 from rsoccer_amd.Entities import Field
+from rsoccer_amd.vec.render import RenderMixin
 
 _VSS_BLOCK = ("x", "y", "theta", "v_x", "v_y", "v_theta")
 _SSL_BLOCK = _VSS_BLOCK + ("infrared", "v_wheel0", "v_wheel1", "v_wheel2", "v_wheel3")
@@ -51,7 +52,7 @@ class VecFrame:
         return VecFrame(self.state.clone(), *self._shape)
 
 
-class _VecBaseEnv:
+class _VecBaseEnv(RenderMixin):
     """``num_envs`` envs behind the four hooks of the reference's base classes, with the episode
     bookkeeping of ``gymnasium.vector`` done ON THE DEVICE: ``step()`` sets ``truncated`` from the
     registry's TimeLimit (``max_episode_steps``), re-places the envs whose episode ended inside the
