@@ -330,6 +330,39 @@ int rsx_drop_pending_hip_error(void);
 /* fused steps this handle has taken since attach (the counter above).  Device-keyed handles: synchronises `stream`. */
 int rsx_task_tick(rsx_sim* h, uint32_t* out, void* stream);
 
+/* ---- exact lookahead over candidate action sequences (additive extension of ABI 6) ------------------------------------
+ * Every random draw of a fused task — the OU noise of the robots the agent does not control included — is keyed by (seed, global env
+ * id, episode, step counter), so the future of an env under a given action sequence is a fixed function of its current state.  This
+ * call evaluates it: from where each env stands NOW, what would each of n_candidates action sequences earn over the next `horizon`
+ * steps?  (The planning primitive of model-predictive control, random shooting / MPPI and tree search.)  One launch, one lane group
+ * per (env, candidate) pair, all steps in registers.
+ *   actions_dev  [num_envs][n_candidates][horizon][act_dim] f32 device memory, dense; act_dim as rsx_task_view reports it (4 N
+ *                for the scrimmage).  Step t of a pair uses the candidate's action t in place of the fed action and the handle's real
+ *                draws for step counter + t for everything else.
+ *   returns_dev  [num_envs][n_candidates] f32: the discounted return up to the pair's episode end or `horizon`, accumulated in
+ *                float32 in this order: ret = ret + disc * reward; disc = disc * gamma (disc starts at 1).
+ *   steps_dev    [num_envs][n_candidates] int32: steps simulated; < horizon exactly when the episode ended inside the horizon.
+ *   flags_dev    [num_envs][n_candidates] uint8: bit 0 terminated, bit 1 truncated, at the last simulated step.
+ *   last_obs_dev [num_envs][n_candidates][obs_dim] f32, or NULL: the observation after the last simulated step; the terminal one
+ *                (what rsx_task_step leaves in final_obs) if the pair ended.
+ * Exactness: rewards, flags and observations of a pair are bit for bit those of `horizon` rsx_task_step calls with the candidate's
+ * actions from the same state (the wire-format round trip between two steps is applied in registers), on every kernel layout
+ * and with per-env physics (rsx_physics_enable: each env with its own coefficients).
+ * A pair STOPS at its env's first episode end (terminated, or truncated = steps >= max_episode_steps): no placement, no auto-reset
+ * and no physics redraw is simulated; the pair's outputs are those of its last simulated step.
+ * No side effects: the call reads the state, the per-env task scalars and the step counter and writes nothing but the four output
+ * arrays — no state, no observations / rewards / flags / final_obs, no metrics, no step counter, no placement cache:
+ * the handle is left exactly as it was, and the next step does what it would have done without the call.
+ * Stream-ordered, never synchronises.  Refusals (nothing is enqueued): RSX_ERR_STATE before the first reset, when step counter +
+ * horizon would pass the 2^32 - 1 limit, and on a host-keyed handle inside a stream capture (like the stepping calls: the counter
+ * is then a launch argument); RSX_ERR_ARG for n_candidates < 1, horizon < 1, a null required pointer, a non-finite gamma, a grid
+ * beyond the launch limit (workgroups = tiles of the batch x n_candidates <= 2^31 - 1) or a handle forced to 64 lanes per env.
+ * Device-keyed handles (rsx_task_enable_capture): the call reads the counter on the device without advancing it and may be captured
+ * and replayed; there the counter limit is checked on the device, and a launch that would pass it simulates nothing: every pair
+ * reports 0 steps, return 0, flags 0, and last_obs_dev is not written. */
+int rsx_task_lookahead(rsx_sim* h, const float* actions_dev, int n_candidates, int horizon, float gamma,
+                       float* returns_dev, int32_t* steps_dev, uint8_t* flags_dev, float* last_obs_dev, void* stream);
+
 /* Debugging aid: number of non-finite floats in the state rows and, with a task attached, in the
  * observations, rewards and info rows.  Synchronises `stream`.  With RSX_DEBUG_FINITE=1 in the
  * environment every stepping call (rsx_step_dev, rsx_task_step, rsx_task_step_n, rsx_task_rollout)

@@ -44,7 +44,7 @@ SYMBOLS = (
     "rsx_task_view_get", "rsx_task_reseed", "rsx_task_layout", "rsx_task_placement_cache_stats", "rsx_task_reset", "rsx_task_reset_to", "rsx_task_step",
     "rsx_task_step_n", "rsx_task_rollout", "rsx_read_metrics", "rsx_metrics_fold", "rsx_check_finite",
     "rsx_task_checkpoint_size", "rsx_task_checkpoint_save", "rsx_task_checkpoint_load",
-    "rsx_task_enable_capture", "rsx_task_tick", "rsx_drop_pending_hip_error",
+    "rsx_task_enable_capture", "rsx_task_tick", "rsx_drop_pending_hip_error", "rsx_task_lookahead",
     "rsx_physics_defaults", "rsx_physics_derive", "rsx_physics_enable", "rsx_physics_set", "rsx_physics_get",
     "rsx_physics_randomize", "rsx_physics_errors",
     "rsx_trace_load", "rsx_trace_eval",
@@ -147,6 +147,7 @@ def load():
     lib.rsx_task_enable_capture.argtypes = [vp, vp]
     lib.rsx_task_tick.argtypes = [vp, C.POINTER(C.c_uint32), vp]
     lib.rsx_drop_pending_hip_error.argtypes = []
+    lib.rsx_task_lookahead.argtypes = [vp, vp, ip, ip, C.c_float, vp, vp, vp, vp, vp]
     lib.rsx_physics_defaults.argtypes = [ip, vp]
     lib.rsx_physics_derive.argtypes = [ip, ip, vp, vp]
     lib.rsx_physics_enable.argtypes = [vp, vp]
@@ -449,6 +450,16 @@ class Sim:
 
     def task_rollout(self, n, stream=None):
         _chk(self._lib.rsx_task_rollout(self._h, int(n), self._stream(stream)))
+
+    def task_lookahead(self, actions_ptr, n_candidates, horizon, gamma, returns_ptr, steps_ptr, flags_ptr, last_obs_ptr=None, stream=None):
+        """rsx_task_lookahead: one launch that scores ``n_candidates`` action sequences of ``horizon`` steps per env from the current
+        state and leaves the handle exactly as it was.  Device addresses: actions [B][K][H][act_dim] f32, returns [B][K] f32, steps
+        [B][K] i32, flags [B][K] u8 (bit 0 terminated, bit 1 truncated), last_obs [B][K][obs_dim] f32 or None.  Plain ints go
+        straight to ctypes."""
+        rc = self._lib.rsx_task_lookahead(self._h, actions_ptr, int(n_candidates), int(horizon), float(gamma), returns_ptr, steps_ptr,
+                                          flags_ptr, last_obs_ptr, stream)
+        if rc:
+            _chk(rc)
 
     def task_enable_capture(self, stream=None):
         """rsx_task_enable_capture: move the step counter to device memory so that stepping calls can be captured into a

@@ -1031,6 +1031,27 @@ int rsx_task_rollout(rsx_sim* h, int n, void* stream) {
     return debug_finite(h, (hipStream_t)stream, "rsx_task_rollout");
 }
 
+int rsx_task_lookahead(rsx_sim* h, const float* actions_dev, int n_candidates, int horizon, float gamma, float* returns_dev,
+                       int32_t* steps_dev, uint8_t* flags_dev, float* last_obs_dev, void* stream) {
+    RSX_ENTER(h);   // (not RSX_ENTER_TASK: nothing the handle owns changes, the host's copy of the state included)
+    if (h->P.task == RSX_TASK_NONE) return fail(RSX_ERR_STATE, "no task attached (rsx_task_attach)");
+    RSX_NEED_RESET(h);
+    if (n_candidates < 1 || horizon < 1) return fail(RSX_ERR_ARG, "n_candidates and horizon must be >= 1");
+    if (!actions_dev || !returns_dev || !steps_dev || !flags_dev) return fail(RSX_ERR_ARG, "actions_dev, returns_dev, steps_dev and flags_dev must not be null");
+    if (!std::isfinite(gamma)) return fail(RSX_ERR_ARG, "gamma must be finite");
+    if (h->L > 32) return fail(RSX_ERR_ARG, "rsx_task_lookahead has no 64-lanes-per-env kernels (unset RSX_LANES_PER_ENV)");
+    if (lookahead_grid(h->L, h->P.num_envs, n_candidates) > 0x7FFFFFFFll)
+        return fail(RSX_ERR_ARG, "num_envs x n_candidates exceeds the launch limit (2^31 - 1 workgroups): split the candidates over several calls");
+    int fl = 0;
+    if (int rc = step_prologue(h, (hipStream_t)stream, (uint64_t)horizon, &fl)) return rc;   // capture of a host-keyed handle, counter limit
+    Params P = h->P;
+    P.tick_base = h->tick;   // the tick the next step would take; not advanced
+    launch_task_lookahead(P, h->L, h->NR, h->d_state, h->d_aux, h->tick_dev ? tick_words(h) + TICK_SLOT_WORD0 : nullptr, h->d_phys,
+                          actions_dev, n_candidates, horizon, gamma, returns_dev, steps_dev, flags_dev, last_obs_dev, (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
 int rsx_check_finite(rsx_sim* h, int64_t* n_bad, void* stream) {
     RSX_ENTER(h);
     if (!n_bad) return fail(RSX_ERR_ARG, "n_bad is null");

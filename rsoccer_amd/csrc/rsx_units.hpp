@@ -31,6 +31,13 @@ void launch_phys_ranges(float* blk, const float* lo, const float* hi, uint32_t m
 // rsx_sysid.hip: trace evaluation (rsx_trace_eval)
 void launch_trace_eval(const Params& P, int L, int NR, const float* phys, float* state, float* loss, const float* frames,
                        const float* cmds, const int32_t* anchors, int n_frames, int n_anchors, int horizon, hipStream_t s);
+// rsx_plan.hip: exact lookahead over candidate action sequences (rsx_task_lookahead).  state / aux: the handle's buffers, read only;
+// ticks: the step-counter slots of a device-keyed handle (slot 0 is read) or nullptr = P.tick_base; phys: the physics block or nullptr.
+// lookahead_grid: workgroups of that launch
+long long lookahead_grid(int L, int num_envs, int n_candidates);
+void launch_task_lookahead(const Params& P, int L, int NR, const float* state, const float* aux, const uint32_t* ticks, const float* phys,
+                           const float* actions, int n_candidates, int horizon, float gamma, float* returns, int32_t* steps,
+                           uint8_t* flags, float* last_obs, hipStream_t s);
 // rsx_render.hip: batched rgb frames (rsx_render_*).  render_check_view: nullptr when the view is valid (and the frame size), else the
 // message; render_field_host: the static field image [H][W][3]; RenderGeom: what the kernel needs of a view, in float32
 struct RenderGeom { int W, H; float s, cx, cy, r, rb; int square; };

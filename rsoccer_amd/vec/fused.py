@@ -127,6 +127,50 @@ class VecFusedEnv(RenderMixin):
         t = self._t
         return t["obs"], t["reward"], t["terminated"], t["truncated"], self._info()
 
+    def lookahead(self, actions, gamma=1.0, return_obs=False):
+        """Score candidate action sequences from where every env stands now, without touching the env (``rsx_task_lookahead``).
+
+        ``actions``: ``[num_envs, K, H, act_dim]`` float32 — for each env ``K`` candidate sequences of ``H`` actions (a CUDA float32
+        contiguous torch tensor is zero-copy; anything else is converted the way ``step()`` converts).  One launch simulates every
+        (env, candidate) pair for up to ``H`` steps with the candidate's actions and the env's REAL future draws (the OU noise of the
+        other robots), so the result is exact: bit for bit what ``H`` calls of ``step()`` with those actions would return.  A pair
+        stops at its env's first episode end; nothing behind it (placement, auto-reset) is simulated.
+
+        Returns a dict of fresh device tensors (caller-owned: not views of engine buffers, not overwritten by the next call):
+        ``return`` ``[num_envs, K]`` float32 — ``sum_t gamma^t reward_t`` up to the pair's end, ``steps`` int32 — steps simulated
+        (``< H`` exactly when the episode ended inside the horizon), ``terminated`` / ``truncated`` bool — at the last simulated
+        step, and with ``return_obs=True`` ``last_obs`` ``[num_envs, K, obs_dim]`` — the observation after the last simulated step
+        (the terminal one if the pair ended).  The env is left exactly as it was: the next ``step()`` does what it would have done.
+        Capturable into a ``torch.cuda.CUDAGraph`` after ``enable_graph_capture()``."""
+        torch = self._torch
+        shape = tuple(np.shape(actions))
+        if len(shape) != 4 or shape[0] != self.num_envs or shape[3] != self.sim.act_dim:   # checked on the INPUT
+            raise ValueError(f"actions must be [{self.num_envs}, K, H, {self.sim.act_dim}], got {shape}")
+        K, H = int(shape[1]), int(shape[2])
+        if K < 1 or H < 1:
+            raise ValueError(f"actions must hold at least one candidate and one step, got K={K}, H={H}")
+        gamma = float(gamma)
+        if not np.isfinite(gamma):
+            raise ValueError("gamma must be finite")
+        if isinstance(actions, torch.Tensor):
+            a = actions
+            if a.device != self.device or a.dtype != torch.float32 or not a.is_contiguous():
+                a = a.to(device=self.device, dtype=torch.float32).contiguous()
+        else:
+            a = torch.from_numpy(np.ascontiguousarray(actions, dtype=np.float32)).to(self.device)
+        B = self.num_envs
+        ret = torch.empty((B, K), dtype=torch.float32, device=self.device)
+        steps = torch.empty((B, K), dtype=torch.int32, device=self.device)
+        flags = torch.empty((B, K), dtype=torch.uint8, device=self.device)
+        obs = torch.empty((B, K, self.sim.obs_dim), dtype=torch.float32, device=self.device) if return_obs else None
+        self.sim.task_lookahead(a.data_ptr(), K, H, gamma, ret.data_ptr(), steps.data_ptr(), flags.data_ptr(),
+                                obs.data_ptr() if return_obs else None, self._stream())
+        self._keep_plan = a   # alive until the launch has consumed it
+        out = {"return": ret, "steps": steps, "terminated": (flags & 1).bool(), "truncated": (flags & 2).bool()}
+        if return_obs:
+            out["last_obs"] = obs
+        return out
+
     # ---- per-env physics / domain randomisation (include/rsx.h: rsx_physics_*; docs/PHYSICS.md section 3) ----
     def _physics_names(self):
         names = _lib.PHYSICS_PARAMS
