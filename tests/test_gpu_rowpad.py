@@ -76,8 +76,9 @@ def test_default_pad_applies_to_large_batches_only():
 
 
 def test_parity_suites_with_padded_rows():
-    """the oracle parity tests, the graph-replay tests and the env-level tests once more, every handle with rows 320 floats longer than its batch"""
+    """the oracle parity tests, the graph-replay tests, the env-level tests, the per-env physics tests and the lookahead tests once more, every handle with rows 320 floats longer than its batch"""
     env = dict(os.environ, RSX_ROW_PAD="320")
     r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "tests/test_gpu_parity.py", "tests/test_gpu_graph.py", "tests/test_gpu_envs.py",
+                        "tests/test_gpu_physics_params.py", "tests/test_gpu_lookahead.py",
                         "-k", "not full_size and not soak"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
