@@ -509,6 +509,41 @@ int rsx_render(rsx_sim* h, const int32_t* env_ids_dev, int n, int channels_first
 /* frames with an out-of-range env id since the last read (read and cleared; synchronises `stream`). */
 int rsx_render_errors(rsx_sim* h, int64_t* out, void* stream);
 
+/* ---- transfer of running episodes between envs and handles (additive extension of ABI 6) --------------------------------
+ * Branching: for i in 0..n-1, env src_ids_dev[i] of `src` is copied into env dst_ids_dev[i] of `dst`, on the device, in stream order
+ * (what population methods, particle resampling, restarts from an archive of states and tree search need; the only other route is
+ * rsx_task_checkpoint_save + _load of whole handles through the host).  A handle that is never stepped serves as a device-resident
+ * bank of states; rsx_task_lookahead works on it unchanged.
+ * What travels is everything per-env that the checkpoint blob carries: the state rows (the two internal rows included), every row of
+ * the scalar arena (last reward, task scalar, episode return, step count, EPISODE ID, cumulative info terms, OU noise), the obs and
+ * final_obs rows, the terminated and truncated bytes and, on physics-enabled handles, the env's parameter and coefficient rows.
+ * What stays with the handle: metrics, the step counter, seed and env_id_base, the randomisation ranges, the rsx_task_reset_to mask,
+ * the action buffer and the placement cache (which needs no invalidation: its entries are tagged by episode and are a pure function
+ * of seed, global env id and episode).  The destination env continues the source's episode under the DESTINATION's random streams:
+ * its per-step draws stay keyed by dst's seed, dst's global env id and dst's step counter; its next placement and physics redraw by
+ * dst's seed and env id and the copied episode id.
+ * The copy is exact and layout-independent: rsx_task_checkpoint_save of `dst` afterwards holds src's columns byte for byte, and the
+ * task scalar that the one-lane-per-env VSS-v0 kernel does not keep in memory is written for the destination as the checkpoint
+ * writes it — source and destination may be stepped by different kernel layouts and differ in row_stride (RSX_ROW_PAD) and num_envs.
+ *   ids         device int32 [n]; NULL = the identity map 0..n-1 on that side (then n <= that handle's num_envs).  Source ids may
+ *               repeat (broadcast).  Destination ids must be pairwise distinct — NOT checked: an env named twice receives an
+ *               unspecified mixture of its sources.  A pair with either id outside its handle is skipped whole, before any access,
+ *               and counted (rsx_task_transfer_errors).  n == 0 succeeds without a launch.
+ *   dst != src  one launch; holds no host state, never synchronises, capturable on any handle (a captured launch keeps BOTH handles'
+ *               buffer pointers: neither may be destroyed while the graph is replayed).
+ *   dst == src  any map is defined, as if every read happened before every write (swaps, permutations, resampling under the identity
+ *               destination): a gather launch into a staging buffer of n records owned by the handle, then a scatter launch.  The
+ *               buffer only grows; a call that has to grow it synchronises `stream`, and inside a stream capture such a call is
+ *               refused (RSX_ERR_STATE: make one eager call of that size first, as with a new view of rsx_render_open).  Handles that
+ *               never make a same-handle transfer allocate nothing.
+ * The caller orders earlier work of both handles before `stream`.  Refusals (nothing is enqueued): RSX_ERR_ARG for a null handle,
+ * n < 0, n beyond num_envs of a NULL side, handles on different devices or handles that differ in simulator kind, task, team sizes,
+ * field type, time step, max_episode_steps, physics model or in whether rsx_physics_enable was called; RSX_ERR_STATE when either
+ * handle has no task attached or has not been reset yet.  Seeds and env_id_base may differ. */
+int rsx_task_transfer(rsx_sim* dst, rsx_sim* src, const int32_t* dst_ids_dev, const int32_t* src_ids_dev, int n, void* stream);
+/* pairs skipped by transfers INTO `dst` since the last read (read and cleared; synchronises `stream`). */
+int rsx_task_transfer_errors(rsx_sim* dst, int64_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,7 @@ SYMBOLS = (
     "rsx_physics_randomize", "rsx_physics_errors",
     "rsx_trace_load", "rsx_trace_eval",
     "rsx_render_view_reference", "rsx_render_size", "rsx_render_field", "rsx_render_open", "rsx_render", "rsx_render_errors",
+    "rsx_task_transfer", "rsx_task_transfer_errors",
 )
 
 
@@ -163,6 +164,8 @@ def load():
     lib.rsx_render_open.argtypes = [vp, C.POINTER(RenderView), vp]
     lib.rsx_render.argtypes = [vp, vp, ip, ip, vp, vp]
     lib.rsx_render_errors.argtypes = [vp, C.POINTER(C.c_int64), vp]
+    lib.rsx_task_transfer.argtypes = [vp, vp, vp, vp, ip, vp]
+    lib.rsx_task_transfer_errors.argtypes = [vp, C.POINTER(C.c_int64), vp]
     if lib.rsx_abi_version() != 6:
         raise RsxError("librsx_hip.so ABI version mismatch")
     _lib = lib
@@ -587,6 +590,23 @@ class Sim:
         """frames whose env id was out of range since the last call (they show the bare field)"""
         n = C.c_int64(0)
         _chk(self._lib.rsx_render_errors(self._h, C.byref(n), self._stream(stream)))
+        return int(n.value)
+
+    # ---- transfer of running episodes (include/rsx.h: rsx_task_transfer) ----
+    def task_transfer(self, src, dst_ids_ptr=None, src_ids_ptr=None, n=0, stream=None):
+        """one launch (two when ``src is self``): env ``src_ids[i]`` of ``src`` is copied into env ``dst_ids[i]`` of this handle for
+        ``i < n`` — state, episode bookkeeping, noise state, observations, flags, per-env physics; metrics, step counter and random
+        keys stay this handle's.  ``*_ids_ptr``: device addresses of ``n`` int32 ids, or None = envs 0..n-1.  Destination ids must
+        be distinct; pairs with an id out of range are skipped and counted (``task_transfer_errors``).  Plain ints go straight to
+        ctypes."""
+        rc = self._lib.rsx_task_transfer(self._h, src._h, dst_ids_ptr, src_ids_ptr, int(n), stream)
+        if rc:
+            _chk(rc)
+
+    def task_transfer_errors(self, stream=None):
+        """pairs skipped by transfers into this handle since the last call (an id out of range); synchronises"""
+        n = C.c_int64(0)
+        _chk(self._lib.rsx_task_transfer_errors(self._h, C.byref(n), self._stream(stream)))
         return int(n.value)
 
     def metrics_fold(self, stream=None):

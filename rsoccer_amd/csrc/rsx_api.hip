@@ -139,6 +139,10 @@ struct rsx_sim {
     std::vector<RenderSlot> render_views;
     int render_cur = -1;
     uint32_t* d_render_err = nullptr;
+    // rsx_task_transfer with dst == src: staging records (the per-env arrays once more, addressed by the pair index).  Growing only; a
+    // buffer that was outgrown stays allocated until rsx_destroy (a captured same-handle transfer holds its pointer in the graph)
+    std::vector<char*> xfer_stage;            // every staging allocation; the last one is current
+    int xfer_cap = 0;                         // records the current one holds
     int tick_slots_alloc = 0;                 // slots allocated (the largest grid any layout of this batch could launch): rsx_task_enable_capture and
                                               // rsx_task_checkpoint_load write ALL of them, so that no grid ever reads a slot nobody has set
 };
@@ -387,6 +391,8 @@ void free_all(rsx_sim* h) {
     h->render_views.clear(); h->render_cur = -1;
     if (h->d_render_err) (void)hipFree(h->d_render_err);
     h->d_render_err = nullptr;
+    for (char* p : h->xfer_stage) (void)hipFree(p);
+    h->xfer_stage.clear(); h->xfer_cap = 0;
     if (h->arena_sim) (void)hipFree(h->arena_sim);
     if (h->arena_task) (void)hipFree(h->arena_task);
     h->arena_sim = h->arena_task = nullptr;
@@ -1504,6 +1510,100 @@ int rsx_render_errors(rsx_sim* h, int64_t* out, void* stream) {
     uint32_t v = 0;
     HIP_TRY(hipMemcpyAsync(&v, h->d_render_err, sizeof(v), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemsetAsync(h->d_render_err, 0, sizeof(uint32_t), s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *out = (int64_t)v;
+    return RSX_OK;
+}
+
+// ---- transfer of running episodes between envs and handles ----
+// the count of skipped pairs lives in a spare word of the task arena's metrics block (metrics[8] | ... | step-counter slots from
+// TICK_SLOT_WORD0), zeroed by rsx_task_attach / rsx_task_reseed: a cross-handle transfer allocates nothing
+constexpr int XFER_ERR_WORD = 20;
+static_assert(XFER_ERR_WORD >= 2 * RSX_METRICS && XFER_ERR_WORD != TICK_ERR_WORD && XFER_ERR_WORD < TICK_SLOT_WORD0, "spare word of the metrics block");
+
+static XferSide xfer_side_of(const rsx_sim* h) {
+    return XferSide{h->d_state, h->d_aux, h->d_phys ? phys_raw(h->d_phys) : nullptr, h->d_obs, h->d_final_obs, h->d_flags,
+                    h->P.row_stride, h->P.num_envs};
+}
+
+int rsx_task_transfer(rsx_sim* dst, rsx_sim* src, const int32_t* dst_ids_dev, const int32_t* src_ids_dev, int n, void* stream) {
+    if (!src) return fail(RSX_ERR_ARG, "null handle");
+    RSX_ENTER_TASK(dst);
+    if (src->P.task == RSX_TASK_NONE) return fail(RSX_ERR_STATE, "no task attached to the source (rsx_task_attach)");
+    if (!dst->task_ready || !src->task_ready)
+        return fail(RSX_ERR_STATE, "rsx_task_reset / rsx_task_reset_to must come before rsx_task_transfer, on both handles");
+    if (src->device != dst->device) return fail(RSX_ERR_ARG, "the handles live on different devices");
+    const Params &D = dst->P, &S = src->P;
+    if (D.kind != S.kind || D.task != S.task || D.n_blue != S.n_blue || D.n_yellow != S.n_yellow)
+        return fail(RSX_ERR_ARG, "the handles differ in simulator kind, task or team sizes");
+    if (dst->field_type != src->field_type || dst->time_step_ms != src->time_step_ms)
+        return fail(RSX_ERR_ARG, "the handles differ in field type or time step");
+    if (D.max_steps != S.max_steps) return fail(RSX_ERR_ARG, "the handles differ in max_episode_steps (TimeLimit)");
+    if ((dst->d_phys != nullptr) != (src->d_phys != nullptr))
+        return fail(RSX_ERR_ARG, "per-env physics is enabled on one handle only (rsx_physics_enable)");
+    if (n < 0) return fail(RSX_ERR_ARG, "n must be >= 0");
+    if ((!dst_ids_dev && n > D.num_envs) || (!src_ids_dev && n > S.num_envs))
+        return fail(RSX_ERR_ARG, "n exceeds num_envs of a side without an id array (NULL = envs 0..n-1)");
+    if (n == 0) return RSX_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const int SR = D.state_dim + X_ROWS, AR = aux_rows(D.n_robots), PR = dst->d_phys ? NPHYS + NCOEF : 0, OD = D.obs_dim;
+    const int pot_row = D.task == RSX_TASK_VSS_V0 ? SR + ROW_PREV_POT : -1;
+    uint32_t* const err = tick_words(dst) + XFER_ERR_WORD;
+    // (the placement cache of either handle needs no invalidation: an entry is tagged with the episode id it was made for and is a
+    // pure function of (seed, global env id, episode) — a tag that no longer matches takes the inline path, one that matches by
+    // coincidence holds the right placement)
+    if (dst != src) {
+        launch_transfer(XFER_DIRECT, xfer_side_of(dst), xfer_side_of(src), D.num_envs, S.num_envs, dst_ids_dev, src_ids_dev, n, err,
+                        SR, AR, PR, OD, pot_row, D.hl_goal, D.inv_len_cm, s);
+        HIP_TRY(launch_status());
+        return RSX_OK;
+    }
+    // same handle: every read before every write — gather the n records into the staging buffer, then scatter them
+    rsx_sim* const h = dst;
+    if (n > h->xfer_cap) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
+        else if (cs != hipStreamCaptureStatusNone)
+            return fail(RSX_ERR_STATE, "a same-handle rsx_task_transfer whose staging buffer has to grow cannot be captured: make one eager call with n = " +
+                                       std::to_string(n) + " (or more) before the capture");
+        HIP_TRY(hipStreamSynchronize(s));
+        char* p = nullptr;
+        const size_t cap = (size_t)n;
+        const size_t bytes = 3 * align_up((size_t)std::max(SR, std::max(AR, NPHYS + NCOEF)) * cap * sizeof(float)) +
+                             2 * align_up(cap * OD * sizeof(float)) + align_up(2 * cap);
+        HIP_TRY(hipMalloc((void**)&p, bytes));
+        h->xfer_stage.push_back(p);
+        h->xfer_cap = n;
+    }
+    XferSide st{};
+    {
+        char* p = h->xfer_stage.back();
+        const size_t cap = (size_t)h->xfer_cap;
+        const size_t rows_b = align_up((size_t)std::max(SR, std::max(AR, NPHYS + NCOEF)) * cap * sizeof(float));
+        st.state = (float*)p; p += rows_b;
+        st.aux = (float*)p; p += rows_b;
+        st.phys = (float*)p; p += rows_b;
+        st.obs = (float*)p; p += align_up(cap * OD * sizeof(float));
+        st.final_obs = (float*)p; p += align_up(cap * OD * sizeof(float));
+        st.flags = (uint8_t*)p;
+        st.stride = h->xfer_cap; st.flag_pitch = h->xfer_cap;
+    }
+    launch_transfer(XFER_GATHER, st, xfer_side_of(h), D.num_envs, D.num_envs, dst_ids_dev, src_ids_dev, n, err, SR, AR, PR, OD, pot_row,
+                    D.hl_goal, D.inv_len_cm, s);
+    launch_transfer(XFER_SCATTER, xfer_side_of(h), st, D.num_envs, D.num_envs, dst_ids_dev, src_ids_dev, n, err, SR, AR, PR, OD, -1,
+                    D.hl_goal, D.inv_len_cm, s);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
+int rsx_task_transfer_errors(rsx_sim* dst, int64_t* out, void* stream) {
+    RSX_ENTER(dst);
+    if (dst->P.task == RSX_TASK_NONE) return fail(RSX_ERR_STATE, "no task attached (rsx_task_attach)");
+    if (!out) return fail(RSX_ERR_ARG, "out is null");
+    hipStream_t s = (hipStream_t)stream;
+    uint32_t v = 0;
+    HIP_TRY(hipMemcpyAsync(&v, tick_words(dst) + XFER_ERR_WORD, sizeof(v), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemsetAsync(tick_words(dst) + XFER_ERR_WORD, 0, sizeof(uint32_t), s));
     HIP_TRY(hipStreamSynchronize(s));
     *out = (int64_t)v;
     return RSX_OK;

@@ -46,5 +46,15 @@ void render_field_host(const rsx_render_view& v, int W, int H, uint8_t* out_hwc)
 RenderGeom render_geom(const rsx_render_view& v, int W, int H);
 void launch_render(const RenderGeom& g, const float* state, int num_envs, int row_stride, int kind, int n_blue, int n_yellow,
                    const uint8_t* tpl, uint32_t* err, const int32_t* env_ids, int n, int channels_first, uint8_t* out, hipStream_t s);
+// rsx_xfer.hip: transfer of running episodes between envs and handles (rsx_task_transfer).  XferSide: the per-env arrays of a handle,
+// or of a staging buffer of the same shape (phys: the parameter rows, the coefficient rows behind them; flags: terminated bytes,
+// truncated bytes flag_pitch further).  mode: XFER_DIRECT handle -> handle; XFER_GATHER handle -> staging (record i = pair i),
+// XFER_SCATTER staging -> handle.  dst_envs / src_envs: envs of the two handles (pairs with an id outside are skipped, and counted in
+// *err by the DIRECT and GATHER launches); pot_row: VSS-v0's previous-potential row, recomputed from the source handle's ball, or -1
+struct XferSide { float *state, *aux, *phys, *obs, *final_obs; uint8_t* flags; int stride, flag_pitch; };
+enum : int { XFER_DIRECT = 0, XFER_GATHER = 1, XFER_SCATTER = 2 };
+void launch_transfer(int mode, const XferSide& dst, const XferSide& src, int dst_envs, int src_envs, const int32_t* dst_ids,
+                     const int32_t* src_ids, int n, uint32_t* err, int state_rows, int aux_rows, int phys_rows, int obs_dim, int pot_row,
+                     float hl_goal, float inv_len_cm, hipStream_t s);
 
 }  // namespace rsx

@@ -1,4 +1,7 @@
 """Fused batched tasks (one kernel launch per ``step()``)."""
+import functools
+import inspect
+
 import numpy as np
 
 from rsoccer_amd import _lib
@@ -15,6 +18,26 @@ def batched_space(single, n):
     low = np.broadcast_to(single.low, (n,) + tuple(single.shape)).copy()
     high = np.broadcast_to(single.high, (n,) + tuple(single.shape)).copy()
     return gym.spaces.Box(low=low, high=high, shape=(n,) + tuple(single.shape), dtype=single.dtype)
+
+
+def _records_ctor_kwargs(init):
+    """wraps an ``__init__`` so that the OUTERMOST constructor call leaves its arguments, by name, in ``self._ctor_kw`` — what
+    ``fork()`` builds its sibling from, whatever keywords a subclass adds"""
+    sig = inspect.signature(init)
+
+    @functools.wraps(init)
+    def wrapped(self, *args, **kw):
+        if "_ctor_kw" not in self.__dict__:
+            bound = sig.bind(self, *args, **kw)
+            rec = {}
+            for name, val in list(bound.arguments.items())[1:]:
+                if sig.parameters[name].kind is inspect.Parameter.VAR_KEYWORD:
+                    rec.update(val)
+                else:
+                    rec[name] = val
+            self._ctor_kw = rec
+        return init(self, *args, **kw)
+    return wrapped
 
 
 class VecFusedEnv(RenderMixin):
@@ -39,6 +62,7 @@ class VecFusedEnv(RenderMixin):
     INFO_KEYS = ()
     TIME_STEP = 0.025
 
+    @_records_ctor_kwargs
     def __init__(self, num_envs, device=0, seed=0, env_id_base=0, max_episode_steps=None,
                  field_type=None, physics=None, physics_ranges=None):
         import torch
@@ -67,6 +91,11 @@ class VecFusedEnv(RenderMixin):
         # gymnasium.vector convention: action_space / observation_space describe the batch, single_* one env
         self.action_space = batched_space(self.single_action_space, self.num_envs)
         self.observation_space = batched_space(self.single_observation_space, self.num_envs)
+
+    def __init_subclass__(cls, **kw):
+        super().__init_subclass__(**kw)
+        if "__init__" in cls.__dict__:
+            cls.__init__ = _records_ctor_kwargs(cls.__dict__["__init__"])
 
     # ---- gym-like surface ----
     def _stream(self):
@@ -307,6 +336,87 @@ class VecFusedEnv(RenderMixin):
         self.sim.task_restore(blob, self._stream())
         t = self._t
         return t["obs"], self._info()
+
+    # ---- branching: episodes copied between envs and between handles (include/rsx.h: rsx_task_transfer) ----
+    def _env_ids(self, ids, num_envs, what, is_dst):
+        """ids of one side as an int32 device tensor (None = the identity map).  Device int tensors are used as they are; host
+        values (numpy, lists, bool masks) are checked: range on both sides, duplicates on the destination side"""
+        torch = self._torch
+        if ids is None:
+            return None
+        if isinstance(ids, torch.Tensor) and ids.is_cuda and ids.dtype != torch.bool:
+            if ids.dtype.is_floating_point or ids.dim() != 1:
+                raise ValueError(f"{what} must be a 1-d integer tensor")
+            if ids.device != self.device or ids.dtype != torch.int32 or not ids.is_contiguous():
+                ids = ids.to(device=self.device, dtype=torch.int32).contiguous()
+            return ids
+        a = ids.cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)
+        if a.dtype == bool:
+            if a.shape != (num_envs,):
+                raise ValueError(f"a bool mask for {what} must have shape ({num_envs},), got {a.shape}")
+            a = np.nonzero(a)[0]
+        elif a.size and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"{what} must hold integers or a bool mask")
+        a = a.astype(np.int64).reshape(-1)
+        if a.size and (a.min() < 0 or a.max() >= num_envs):
+            raise ValueError(f"{what} holds an env id outside [0, {num_envs})")
+        if is_dst and np.unique(a).size != a.size:
+            raise ValueError(f"{what} names an env twice: destination ids must be distinct")
+        return torch.from_numpy(a.astype(np.int32)).to(self.device)
+
+    def copy_envs_from(self, src, src_ids=None, dst_ids=None):
+        """Copy running episodes on the device: env ``src_ids[i]`` of ``src`` (another env of the same class and configuration, or
+        ``self``) becomes env ``dst_ids[i]`` of ``self`` — simulator state, episode bookkeeping (step count, episode id, cumulative
+        info terms, OU noise), ``obs`` / ``final_obs``, flags and per-env physics values; ``None`` on a side = envs ``0..n-1``.  Stream-
+        ordered, no host copy (``rsx_task_transfer``).  Metrics, the step counter and the random keys stay ``self``'s: the copied
+        episode continues under ``self``'s noise streams.
+
+        Ids: int tensors on the device are used as they are (out-of-range pairs are skipped and counted by
+        ``sim.task_transfer_errors()``; destination ids must be distinct, which is NOT checked there — a duplicated destination
+        receives an unspecified mixture); numpy arrays, lists and bool masks are converted, and checked: ``ValueError`` for an id
+        out of range or a duplicated destination.  Source ids may repeat (broadcast).  With ``src is self`` any map works (swaps,
+        permutations, resampling), as if every read happened before every write.  Returns ``self``'s ``obs`` view."""
+        if not isinstance(src, VecFusedEnv):
+            raise TypeError("src must be a fused vector env (hook-written envs keep their task state in Python)")
+        s_ids = self._env_ids(src_ids, src.num_envs, "src_ids", False)
+        d_ids = self._env_ids(dst_ids, self.num_envs, "dst_ids", True)
+        if s_ids is not None and d_ids is not None:
+            if s_ids.numel() != d_ids.numel():
+                raise ValueError(f"src_ids and dst_ids differ in length ({s_ids.numel()} and {d_ids.numel()})")
+            n = s_ids.numel()
+        elif s_ids is not None or d_ids is not None:
+            n = (s_ids if s_ids is not None else d_ids).numel()
+            other = self.num_envs if d_ids is None else src.num_envs
+            if n > other:
+                raise ValueError(f"{n} ids against the identity map of a side with {other} envs")
+        else:
+            if src.num_envs != self.num_envs:
+                raise ValueError("give src_ids or dst_ids to copy between envs of different num_envs")
+            n = self.num_envs
+        self._keep_xfer = (s_ids, d_ids)   # alive until the launch has consumed them
+        self.sim.task_transfer(src.sim, None if d_ids is None else d_ids.data_ptr(), None if s_ids is None else s_ids.data_ptr(),
+                               n, self._stream())
+        return self._t["obs"]
+
+    def fork(self, num_envs=None, seed=None):
+        """A new env of ``self``'s class and constructor configuration (device, ``env_id_base``, ``max_episode_steps``, field, team
+        sizes, per-env physics on or off with ``self``'s randomisation ranges) with ``num_envs`` envs (default: as many) and ``seed``
+        (default: the same), already reset: ready to receive ``copy_envs_from`` — a device-resident bank of states when it is never
+        stepped (``lookahead`` works on it), or a second population."""
+        kw = dict(self._ctor_kw)
+        kw["num_envs"] = self.num_envs if num_envs is None else int(num_envs)
+        if seed is not None:
+            kw["seed"] = int(seed)
+        kw.pop("physics", None)          # per-env values belong to the envs; they travel with copy_envs_from
+        kw.pop("physics_ranges", None)
+        if self._physics:
+            kw["physics"] = {}
+            ranges = dict(getattr(self, "_ranges", {}))
+            if ranges:
+                kw["physics_ranges"] = ranges
+        env = type(self)(**kw)
+        env.reset()
+        return env
 
     def metrics(self):
         """Counters accumulated on device since construction (synchronises the stream)."""
