@@ -1,0 +1,533 @@
+// rsx_api_task.hip — the fused tasks of the C-ABI (include/rsx.h: rsx_task_*, rsx_read_metrics): attach, reseed, capture, tick,
+// layout, view, reset, step, rollout, lookahead, metrics, checkpoint and transfer.  Host code only.
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+
+#include "rsx_handle.hpp"
+#include "rsx_math.hpp"
+
+using namespace rsx;
+
+// largest batch whose single-step launches carry placement-helper workgroups (rsx_kernels.hpp: placement_helper): where a
+// launch is as long as its slowest wave and half of the SIMDs are idle anyway
+#ifndef RSX_PCACHE_MAX_ENVS
+#define RSX_PCACHE_MAX_ENVS 16384
+#endif
+
+namespace {
+
+// workgroups of the handle's lane-group launches, and the placement helpers behind them in a single-step launch of a handle
+// with a placement cache (rsx_task_attach: 8 lanes per env, exact robot count): one per 64 envs; none with per-env physics
+int grid_for(const rsx_sim* h) { return lane_grid(h->L, h->P.num_envs); }
+int helpers_for(const rsx_sim* h, int mode) { return mode == MODE_STEP && h->d_pcache && !h->d_phys ? (h->P.num_envs + 63) / 64 : 0; }
+
+// The layout of one launch of the handle's task kernels (the plan of rsx_task_attach); what is not a step runs on the lane-group kernels.
+// step_grid and the dispatch read it and nothing else: the grid a launch gets is the grid the tick slots are kept in sync by (step_tick)
+Layout stepping_layout(const rsx_sim* h, int mode) { return mode == MODE_STEP ? h->plan.step : mode == MODE_ROLLOUT ? h->plan.rollout : Layout::Lanes; }
+int step_grid(const rsx_sim* h, int mode) {
+    switch (stepping_layout(h, mode)) {
+        case Layout::Epl: return epl_grid(h->P.num_envs);
+        case Layout::Quad: return ssl_quad_grid(h->P.num_envs);
+        default: return grid_for(h) + helpers_for(h, mode);   // (LanesBig: 32 lanes per env, no helpers)
+    }
+}
+void launch_task_of(const rsx_sim* h, const float* actions, int n_steps, int mode, hipStream_t s) {
+    const Buffers b = buffers_of(h, mode == MODE_STEP ? actions : nullptr);   // only a single step reads fed actions
+    const bool rollout = mode == MODE_ROLLOUT;
+    switch (stepping_layout(h, mode)) {
+        case Layout::Epl:
+            if (h->P.task == RSX_TASK_VSS_V0) launch_vss_epl(rollout, h->P, b, n_steps, s); else launch_ssl_epl(h->P.task, rollout, h->P, b, n_steps, s);
+            break;
+        case Layout::Quad: launch_ssl_quad(h->P, b, n_steps, s); break;
+        case Layout::LanesBig: launch_scrimmage_big(rollout, h->P, b, n_steps, s); break;
+        case Layout::Lanes:
+            if (h->d_phys) launch_task_phys(h->P, b, h->L, h->NR, h->d_phys, n_steps, mode, s);
+            else launch_task(h->P, b, h->L, h->NR, helpers_for(h, mode), n_steps, mode, s);
+            break;
+    }
+}
+bool rollout_as_steps(const rsx_sim* h) { return h->plan.rollout_as_steps || (h->tick_dev && h->plan.step == Layout::Quad); }   // (device-keyed four-lane handle: one grid for all launches)
+
+}  // namespace
+
+void rsx::plan_stepping(rsx_sim* h) {
+    const Params& P = h->P;
+    h->plan = plan_layout(LayoutQuery{P.task, P.kind, h->L, h->NR, P.n_blue, P.num_envs, P.row_stride, P.state_dim, P.obs_dim, P.n_sub,
+                                      h->d_phys != nullptr, std::getenv("RSX_LAYOUT")});
+    h->tick_slots = step_grid(h, MODE_STEP);
+}
+
+extern "C" {
+
+int rsx_task_attach(rsx_sim* h, int task, uint64_t seed, uint64_t env_id_base, int max_episode_steps) {
+    RSX_ENTER(h);
+    if (h->P.task != RSX_TASK_NONE) return fail(RSX_ERR_STATE, "a task is already attached");
+    // global env ids are 32-bit words of the Philox counter: the whole range of this handle has to fit
+    if (env_id_base > 0xFFFFFFFFull || env_id_base + (uint64_t)h->P.num_envs > 0x100000000ull)
+        return fail(RSX_ERR_ARG, "env_id_base + num_envs exceeds 2^32 (global env ids are 32-bit)");
+    Params P = h->P;
+    if (derive_task(task, seed, env_id_base, max_episode_steps, h->M, P))
+        return fail(RSX_ERR_ARG, "task does not match the simulator (VSS_V0: VSS, n_blue >= 1; STATIC_DEFENDERS: SSL 1vN; DRIBBLING: SSL 1v4; CONTESTED: SSL 1v1; PASS_ENDURANCE: SSL 2v0; SCRIMMAGE: SSL)");
+    if (P.obs_dim > 64) return fail(RSX_ERR_ARG, "observation wider than 64 floats is not supported");
+    if (task >= RSX_TASK_SSL_DRIBBLING && task <= RSX_TASK_SSL_PASS_ENDURANCE && h->L != 8)
+        return fail(RSX_ERR_ARG, "this task runs with 8 lanes per env only (unset RSX_LANES_PER_ENV)");
+    const size_t B = (size_t)P.num_envs, S = (size_t)P.row_stride;
+    const size_t n_aux = align_up((size_t)aux_rows(P.n_robots) * S * sizeof(float));
+    if (n_aux >= ((size_t)1 << 32) || B * (size_t)P.obs_dim * sizeof(float) >= ((size_t)1 << 32))
+        return fail(RSX_ERR_ARG, "num_envs too large for a fused task: the per-env scalar arena or the observation array would reach 4 GB (see rsx.h, limits)");
+    const size_t n_obs = align_up(B * P.obs_dim * sizeof(float));
+    const size_t n_flags = align_up(3 * B);   // terminated | truncated | the env mask of rsx_task_reset_to (read by the MODE_REFRESH launch only)
+    const size_t n_act = align_up(B * h->M.act_dim * sizeof(float));
+    // metrics[8] | error word | (256 bytes in) one step-counter slot per workgroup of the largest stepping launch any layout
+    // of this batch could use (rsx_kernels.hpp: step_tick; only the first tick_slots are kept in sync)
+    const size_t n_met = align_up((size_t)TICK_SLOT_WORD0 * 4 + ((size_t)grid_for(h) + (B + 63) / 64) * sizeof(uint32_t));
+    const size_t n_slots = align_up((size_t)MSLOTS * RSX_METRICS * sizeof(unsigned long long));
+    // placement cache: static defenders 1v6 (short episodes: several resetting waves per launch) at latency-bound batches
+    const bool pc = !std::getenv("RSX_NO_PCACHE") && h->L == 8 && P.num_envs <= RSX_PCACHE_MAX_ENVS && P.n_sub > 0 &&
+                    task == RSX_TASK_SSL_STATIC_DEFENDERS && h->NR == 7;
+    const size_t n_pc = pc ? align_up((size_t)2 * (3 * (P.n_robots + 1) + 1) * B * sizeof(float)) : 0;
+    const size_t n_pcs = pc && std::getenv("RSX_PCACHE_STATS") ? align_up(2 * sizeof(unsigned long long)) : 0;
+    const size_t total = n_aux + 2 * n_obs + n_flags + n_act + n_met + n_slots + n_pc + n_pcs;
+    HIP_TRY(hipMalloc((void**)&h->arena_task, total));
+    HIP_TRY(hipMemset(h->arena_task, 0, total));
+    h->arena_task_bytes = total; h->pcache_bytes = n_pc;
+    char* p = h->arena_task;
+    h->d_aux = (float*)p; p += n_aux;
+    h->d_obs = (float*)p; p += n_obs;
+    h->d_final_obs = (float*)p; p += n_obs;
+    h->d_flags = (uint8_t*)p; p += n_flags;
+    h->d_actions = (float*)p; p += n_act;
+    h->d_metrics = (unsigned long long*)p; p += n_met;
+    h->d_mslots = (unsigned long long*)p; p += n_slots;
+    if (n_pc) {
+        h->d_pcache = (float*)p; p += n_pc;
+        HIP_TRY(hipMemset(h->d_pcache, 0xFF, n_pc));   // tags 0xFFFFFFFF: no entry is valid yet
+    }
+    if (n_pcs) h->d_pcstats = (unsigned long long*)p;
+    // episode ids start at 0xFFFFFFFF so that the first reset() opens episode 0
+    HIP_TRY(hipMemset(h->d_aux + (size_t)ROW_EPISODE * S, 0xFF, B * sizeof(uint32_t)));
+    h->P = P;
+    plan_stepping(h);
+    h->task_ready = false;
+    h->tick_dev = false;
+    h->tick_slots_alloc = std::max(h->tick_slots, grid_for(h) + (P.num_envs + 63) / 64);
+    HIP_TRY(hipDeviceSynchronize());   // null-stream memsets done before any caller stream steps
+    return RSX_OK;
+}
+
+int rsx_task_reseed(rsx_sim* h, uint64_t seed, void* stream) {
+    RSX_ENTER_TASK(h);
+    hipStream_t s = (hipStream_t)stream;
+    if (stream_is_capturing(s)) return fail(RSX_ERR_STATE, "rsx_task_reseed changes host state (seed, step counter) and cannot be captured");
+    // what rsx_task_attach leaves behind, with the new key: every per-env buffer and counter cleared, episode ids at 0xFFFFFFFF,
+    // placement cache empty, step counter 0 (device-keyed handles: every slot), no episode open
+    HIP_TRY(hipMemsetAsync(h->arena_task, 0, h->arena_task_bytes, s));
+    if (h->d_pcache) HIP_TRY(hipMemsetAsync(h->d_pcache, 0xFF, h->pcache_bytes, s));
+    HIP_TRY(hipMemsetAsync(h->d_aux + (size_t)ROW_EPISODE * h->P.row_stride, 0xFF, (size_t)h->P.num_envs * sizeof(uint32_t), s));
+    h->P.key0 = (uint32_t)seed; h->P.key1 = (uint32_t)(seed >> 32);
+    h->tick = 0; h->P.tick_base = 0;
+    h->task_ready = false;
+    return RSX_OK;
+}
+
+int rsx_task_enable_capture(rsx_sim* h, void* stream) {
+    RSX_ENTER_TASK(h);
+    // The one place where the thread's pending HIP error is dropped: the usual way to get here is a capture attempt that this library
+    // refused (host-keyed handle) and that the caller's framework then aborted — which leaves `invalid argument` in the slot for the
+    // NEXT capture to trip over (torch.cuda.graph does).  A set-up call, not a stepping path; rsx.h says so.
+    (void)hipGetLastError();
+    if (h->tick_dev) return RSX_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (stream_is_capturing(s))
+        return fail(RSX_ERR_STATE, "rsx_task_enable_capture must be called BEFORE the capture begins (it writes the step counter once; a captured write would reset it on every replay)");
+    launch_tick_fill(tick_slot0(h), 0, h->tick_slots_alloc, h->tick, 0, s);
+    HIP_TRY(launch_status());
+    h->tick_dev = true;
+    h->host_state_cache = false; h->host_state_valid = false;   // a replayed graph changes the state without passing through this API
+    return RSX_OK;
+}
+
+int rsx_task_tick(rsx_sim* h, uint32_t* out, void* stream) {
+    RSX_ENTER(h);
+    if (!out) return fail(RSX_ERR_ARG, "out is null");
+    if (h->P.task == RSX_TASK_NONE) return fail(RSX_ERR_STATE, "no task attached (rsx_task_attach)");
+    if (!h->tick_dev) { *out = h->tick; return RSX_OK; }
+    uint32_t w[2] = {0, 0};   // slot 0, error word
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemcpyAsync(&w[0], tick_slot0(h), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&w[1], tick_words(h) + TICK_ERR_WORD, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *out = w[0];
+    h->tick = w[0];
+    if (w[1]) return fail(RSX_ERR_STATE, "step counter exhausted: a launch that would have wrapped it was refused on the device (a handle takes at most 2^32 - 1 fused steps)");
+    return RSX_OK;
+}
+
+int rsx_task_placement_cache_stats(rsx_sim* h, int64_t out[2], void* stream) {
+    RSX_ENTER_TASK(h);
+    if (!out) return fail(RSX_ERR_ARG, "out is null");
+    out[0] = out[1] = -1;   // -1: no cache on this handle, or the counters are off (RSX_PCACHE_STATS=1 before rsx_task_attach)
+    if (!h->d_pcstats) return RSX_OK;
+    HIP_TRY(hipMemcpyAsync(out, h->d_pcstats, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return RSX_OK;
+}
+
+int rsx_task_layout(rsx_sim* h, char* out, size_t n) {
+    if (!h || !out || n == 0) return fail(RSX_ERR_ARG, "null argument");
+    if (h->P.task == RSX_TASK_NONE) return fail(RSX_ERR_STATE, "no task attached (rsx_task_attach)");
+    const Layout lay = h->plan.step;
+    const char* name = lay == Layout::Epl ? "one-lane-per-env" : lay == Layout::Quad ? "four-lanes-per-env" : lay == Layout::LanesBig ? "32-lanes-per-env-large-batch"
+                     : h->L == 8 ? "8-lanes-per-env" : h->L == 16 ? "16-lanes-per-env" : h->L == 32 ? "32-lanes-per-env" : "64-lanes-per-env";
+    std::snprintf(out, n, "%s", name);
+    return RSX_OK;
+}
+
+int rsx_task_view_get(rsx_sim* h, rsx_task_view* out) {
+    if (!h || !out) return fail(RSX_ERR_ARG, "null argument");
+    if (h->P.task == RSX_TASK_NONE) return fail(RSX_ERR_STATE, "no task attached (rsx_task_attach)");
+    const size_t B = (size_t)h->P.num_envs;
+    out->task = h->P.task; out->obs_dim = h->P.obs_dim; out->act_dim = h->M.act_dim;
+    out->info_dim = h->M.info_dim; out->max_episode_steps = h->P.max_steps;
+    const size_t S = (size_t)h->P.row_stride;
+    out->obs = h->d_obs; out->reward = h->d_aux + (size_t)ROW_REWARD * S;
+    out->terminated = h->d_flags; out->truncated = h->d_flags + B;
+    out->info = h->d_aux + (size_t)ROW_INFO * S; out->final_obs = h->d_final_obs;
+    out->steps = (int32_t*)(h->d_aux + (size_t)ROW_STEPS * S); out->actions = h->d_actions;
+    out->metrics = (int64_t*)h->d_metrics; out->row_stride = h->P.row_stride;
+    return RSX_OK;
+}
+
+int rsx_task_reset(rsx_sim* h, void* stream) {
+    RSX_ENTER_TASK(h);
+    launch_task_of(h, nullptr, 1, MODE_RESET, (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    h->task_ready = true;
+    return RSX_OK;
+}
+
+int rsx_task_reset_to(rsx_sim* h, const double* ball, const double* blue, const double* yellow,
+                      const uint8_t* env_mask, void* stream) {
+    RSX_ENTER_TASK(h);
+    if (int rc = rsx_reset(h, ball, blue, yellow, env_mask, stream)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t B = (size_t)h->P.num_envs;
+    // the kernel takes the env mask through the third row of the flags array: `terminated` / `truncated` of the envs the mask leaves
+    // alone stay what their last step made them (until round 6 the mask travelled through the `truncated` row, which was cleared
+    // afterwards — for EVERY env: found by tests/test_gpu_api_fuzz.py)
+    if (env_mask) HIP_TRY(hipMemcpyAsync(h->d_flags + 2 * B, env_mask, B, hipMemcpyHostToDevice, s));
+    else HIP_TRY(hipMemsetAsync(h->d_flags + 2 * B, 1, B, s));
+    launch_task_of(h, nullptr, 1, MODE_REFRESH, s);
+    HIP_TRY(launch_status());
+    HIP_TRY(hipStreamSynchronize(s));   // the host mask / placement arrays may be reused by the caller
+    h->task_ready = true;
+    return RSX_OK;
+}
+
+// The handle's step counter keys the per-step random draws and is one 32-bit word of the Philox counter: a handle that
+// has taken 2^32 - 1 fused steps refuses further ones instead of silently replaying its random streams.
+// Host-keyed handles (the default) check that here and bake the count into the launch — which is why they refuse to be
+// captured: a replayed graph would step with one tick for ever.  Device-keyed handles (rsx_task_enable_capture) pass
+// RSX_TICK_DEV instead: the kernels read, check and advance the counter themselves (rsx_kernels.hpp: step_tick).
+static int step_prologue(rsx_sim* h, hipStream_t s, uint64_t n, int* flags) {
+    *flags = 0;
+    if (h->tick_dev) { *flags = RSX_TICK_DEV; return RSX_OK; }
+    if (stream_is_capturing(s))
+        return fail(RSX_ERR_STATE, "this stream is being captured, and the handle's step counter (the key of its per-step random draws) is still a host-side "
+                                   "launch argument: a replayed graph would repeat one random stream. Call rsx_task_enable_capture(h, stream) once, before the capture begins");
+    if ((uint64_t)h->tick + n > 0xFFFFFFFFull)
+        return fail(RSX_ERR_STATE, "step counter exhausted: a handle takes at most 2^32 - 1 fused steps (it keys the per-step random draws); attach a fresh handle with another seed");
+    return RSX_OK;
+}
+// device-keyed handles: slots the launch did not cover (a grid without the placement helpers) follow slot 0
+static void tick_resync(const rsx_sim* h, int mode, hipStream_t s) {
+    if (h->tick_dev) launch_tick_fill(tick_slot0(h), step_grid(h, mode), h->tick_slots, 0u, 1, s);
+}
+
+static int single_steps(rsx_sim* h, const float* actions_dev, int n, hipStream_t s, const char* where) {   // n single-step launches, tick by tick
+    int fl = 0;
+    if (int rc = step_prologue(h, s, (uint64_t)n, &fl)) return rc;
+    for (int i = 0; i < n; ++i) { h->P.tick_base = h->tick++; launch_task_of(h, actions_dev, 1 | fl, MODE_STEP, s); }
+    HIP_TRY(launch_status());
+    return debug_finite(h, s, where);
+}
+
+int rsx_task_step(rsx_sim* h, const float* actions_dev, void* stream) {
+    RSX_ENTER_TASK(h);
+    RSX_NEED_RESET(h);
+    return single_steps(h, actions_dev, 1, (hipStream_t)stream, "rsx_task_step");
+}
+
+int rsx_task_step_n(rsx_sim* h, int n, void* stream) {
+    RSX_ENTER_TASK(h);
+    RSX_NEED_RESET(h);
+    if (n < 1) return fail(RSX_ERR_ARG, "n must be >= 1");
+    return single_steps(h, nullptr, n, (hipStream_t)stream, "rsx_task_step_n");
+}
+
+int rsx_task_rollout(rsx_sim* h, int n, void* stream) {
+    RSX_ENTER_TASK(h);
+    RSX_NEED_RESET(h);
+    if (n < 0 || n > RSX_N_STEPS_MASK) return fail(RSX_ERR_ARG, "n must be in 0 .. 2^30 - 1");  // 0 = load + store only (profiling)
+    if (n >= 1 && rollout_as_steps(h)) return single_steps(h, nullptr, n, (hipStream_t)stream, "rsx_task_rollout");   // 11v11 at large batches (rsx_layout.hpp)
+    int fl = 0;
+    if (int rc = step_prologue(h, (hipStream_t)stream, (uint64_t)n, &fl)) return rc;
+    h->P.tick_base = h->tick; h->tick += (uint32_t)n;
+    launch_task_of(h, nullptr, n | fl, MODE_ROLLOUT, (hipStream_t)stream);
+    tick_resync(h, MODE_ROLLOUT, (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return debug_finite(h, (hipStream_t)stream, "rsx_task_rollout");
+}
+
+int rsx_task_lookahead(rsx_sim* h, const float* actions_dev, int n_candidates, int horizon, float gamma, float* returns_dev,
+                       int32_t* steps_dev, uint8_t* flags_dev, float* last_obs_dev, void* stream) {
+    RSX_ENTER(h);   // (not RSX_ENTER_TASK: nothing the handle owns changes, the host's copy of the state included)
+    if (h->P.task == RSX_TASK_NONE) return fail(RSX_ERR_STATE, "no task attached (rsx_task_attach)");
+    RSX_NEED_RESET(h);
+    if (n_candidates < 1 || horizon < 1) return fail(RSX_ERR_ARG, "n_candidates and horizon must be >= 1");
+    if (!actions_dev || !returns_dev || !steps_dev || !flags_dev) return fail(RSX_ERR_ARG, "actions_dev, returns_dev, steps_dev and flags_dev must not be null");
+    if (!std::isfinite(gamma)) return fail(RSX_ERR_ARG, "gamma must be finite");
+    if (h->L > 32) return fail(RSX_ERR_ARG, "rsx_task_lookahead has no 64-lanes-per-env kernels (unset RSX_LANES_PER_ENV)");
+    if (lookahead_grid(h->L, h->P.num_envs, n_candidates) > 0x7FFFFFFFll)
+        return fail(RSX_ERR_ARG, "num_envs x n_candidates exceeds the launch limit (2^31 - 1 workgroups): split the candidates over several calls");
+    int fl = 0;
+    if (int rc = step_prologue(h, (hipStream_t)stream, (uint64_t)horizon, &fl)) return rc;   // capture of a host-keyed handle, counter limit
+    Params P = h->P;
+    P.tick_base = h->tick;   // the tick the next step would take; not advanced
+    launch_task_lookahead(P, h->L, h->NR, h->d_state, h->d_aux, h->tick_dev ? tick_slot0(h) : nullptr, h->d_phys,
+                          actions_dev, n_candidates, horizon, gamma, returns_dev, steps_dev, flags_dev, last_obs_dev, (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
+// ---- task checkpoint: everything a fused run needs to continue bit-identically ----
+namespace {
+struct CkptHeader {
+    uint64_t magic;            // "RSXCKPT2"
+    int32_t abi, kind, field_rows, task, n_blue, n_yellow, num_envs, state_rows, aux_rows, obs_dim;
+    int32_t field_type, time_step_ms, max_steps, model;   // model: RSX_PHYSICS_MODEL of the saving library
+    uint32_t key0, key1, env_id_base, tick;
+    uint64_t state_bytes, aux_bytes, obs_bytes, flag_bytes;
+    int64_t metrics[RSX_METRICS];
+};
+constexpr uint64_t CKPT_MAGIC = 0x3254504B43585352ull;   // "RSXCKPT2", little endian
+// model word of a physics-enabled handle's blob: a section follows the others — the physics header (ranges), the parameter rows
+// and the coefficient rows (dense, like the rest); a blob of either kind is refused by a handle of the other
+constexpr int32_t CKPT_MODEL_PHYS = 1 << 16;
+size_t ckpt_phys_bytes(const CkptHeader& k) {
+    return (k.model & CKPT_MODEL_PHYS) ? sizeof(PhysHeader) + (size_t)(NPHYS + NCOEF) * (size_t)k.num_envs * sizeof(float) : 0;
+}
+CkptHeader ckpt_header(const rsx_sim* h) {
+    CkptHeader k{};
+    const size_t B = (size_t)h->P.num_envs;
+    k.magic = CKPT_MAGIC; k.abi = RSX_ABI_VERSION; k.kind = h->P.kind; k.field_rows = h->M.rs; k.task = h->P.task;
+    k.n_blue = h->P.n_blue; k.n_yellow = h->P.n_yellow; k.num_envs = h->P.num_envs;
+    k.state_rows = state_rows(h); k.aux_rows = aux_rows(h->P.n_robots); k.obs_dim = h->P.obs_dim;
+    k.field_type = h->field_type; k.time_step_ms = h->time_step_ms; k.max_steps = h->P.max_steps; k.model = RSX_PHYSICS_MODEL | (h->d_phys ? CKPT_MODEL_PHYS : 0);
+    k.key0 = h->P.key0; k.key1 = h->P.key1; k.env_id_base = h->P.env_id_base; k.tick = h->tick;
+    k.state_bytes = (uint64_t)k.state_rows * B * sizeof(float);
+    k.aux_bytes = (uint64_t)k.aux_rows * B * sizeof(float);
+    k.obs_bytes = (uint64_t)B * k.obs_dim * sizeof(float);
+    k.flag_bytes = 2 * B;
+    return k;
+}
+size_t ckpt_size(const CkptHeader& k) { return sizeof(CkptHeader) + k.state_bytes + k.aux_bytes + 2 * k.obs_bytes + k.flag_bytes + ckpt_phys_bytes(k); }
+}  // namespace
+
+int rsx_task_checkpoint_size(rsx_sim* h, size_t* bytes) {
+    if (!h || !bytes) return fail(RSX_ERR_ARG, "null argument");
+    if (h->P.task == RSX_TASK_NONE) return fail(RSX_ERR_STATE, "no task attached (rsx_task_attach)");
+    *bytes = ckpt_size(ckpt_header(h));
+    return RSX_OK;
+}
+
+int rsx_task_checkpoint_save(rsx_sim* h, void* blob, size_t bytes, void* stream) {
+    RSX_ENTER_TASK(h);
+    if (!blob) return fail(RSX_ERR_ARG, "blob is null");
+    CkptHeader k = ckpt_header(h);
+    if (bytes < ckpt_size(k)) return fail(RSX_ERR_ARG, "blob is smaller than rsx_task_checkpoint_size");
+    hipStream_t s = (hipStream_t)stream;
+    launch_fold_metrics(h->d_metrics, h->d_mslots, s);
+    HIP_TRY(launch_status());
+    char* p = (char*)blob + sizeof(CkptHeader);
+    // (the blob's rows are dense — B floats — whatever the row pad of this handle: it restores into any layout)
+    const size_t rowb = (size_t)h->P.num_envs * sizeof(float), pitch = (size_t)h->P.row_stride * sizeof(float);
+    HIP_TRY(hipMemcpy2DAsync(p, rowb, h->d_state, pitch, rowb, (size_t)k.state_rows, hipMemcpyDeviceToHost, s)); p += k.state_bytes;
+    HIP_TRY(hipMemcpy2DAsync(p, rowb, h->d_aux, pitch, rowb, (size_t)k.aux_rows, hipMemcpyDeviceToHost, s)); p += k.aux_bytes;
+    HIP_TRY(hipMemcpyAsync(p, h->d_obs, k.obs_bytes, hipMemcpyDeviceToHost, s)); p += k.obs_bytes;
+    HIP_TRY(hipMemcpyAsync(p, h->d_final_obs, k.obs_bytes, hipMemcpyDeviceToHost, s)); p += k.obs_bytes;
+    HIP_TRY(hipMemcpyAsync(p, h->d_flags, k.flag_bytes, hipMemcpyDeviceToHost, s));
+    if (h->d_phys) {
+        p += k.flag_bytes;
+        HIP_TRY(hipMemcpyAsync(p, h->d_phys, sizeof(PhysHeader), hipMemcpyDeviceToHost, s)); p += sizeof(PhysHeader);
+        HIP_TRY(hipMemcpy2DAsync(p, rowb, phys_raw(h->d_phys), pitch, rowb, (size_t)(NPHYS + NCOEF), hipMemcpyDeviceToHost, s));   // raw rows, then the coefficient rows
+    }
+    HIP_TRY(hipMemcpyAsync(k.metrics, h->d_metrics, sizeof(k.metrics), hipMemcpyDeviceToHost, s));
+    if (h->tick_dev)   // device-keyed handle: the step counter is slot 0 of the per-workgroup slots (all equal between launches)
+        HIP_TRY(hipMemcpyAsync(&k.tick, tick_slot0(h), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h->tick_dev) h->tick = k.tick;
+    std::memcpy(blob, &k, sizeof(k));
+    if (h->P.task == RSX_TASK_VSS_V0) {
+        // The task scalar of VSS-v0 (previous ball potential, vss_gym.py:256-283) is a function of the ball position
+        // the next step starts from; the one-lane-per-env kernel recomputes it instead of keeping the row up to date.
+        // The blob always carries the value, so that it restores into either kernel layout.  Same float expression
+        // as the kernels' (rsx_math.hpp: vss_ball_potential).
+        const size_t B = (size_t)h->P.num_envs;
+        const float* st = reinterpret_cast<const float*>((const char*)blob + sizeof(CkptHeader));
+        float* aux = reinterpret_cast<float*>((char*)blob + sizeof(CkptHeader) + k.state_bytes);
+        for (size_t e = 0; e < B; ++e) aux[(size_t)ROW_PREV_POT * B + e] = vss_ball_potential(st[e], st[B + e], h->P.hl_goal, h->P.inv_len_cm);
+    }
+    return RSX_OK;
+}
+
+int rsx_task_checkpoint_load(rsx_sim* h, const void* blob, size_t bytes, void* stream) {
+    RSX_ENTER_TASK(h);
+    if (!blob || bytes < sizeof(CkptHeader)) return fail(RSX_ERR_ARG, "blob is null or truncated");
+    CkptHeader k;
+    std::memcpy(&k, blob, sizeof(k));
+    CkptHeader want = ckpt_header(h);
+    if (k.magic != CKPT_MAGIC || k.abi != want.abi) return fail(RSX_ERR_ARG, "not a checkpoint of this library version");
+    if ((k.model & CKPT_MODEL_PHYS) != (want.model & CKPT_MODEL_PHYS))
+        return fail(RSX_ERR_ARG, "the checkpoint was taken from a handle with per-env physics on / off and this one has it off / on (rsx_physics_enable)");
+    if (k.model != want.model) return fail(RSX_ERR_ARG, "the checkpoint was taken under another version of the physics model (RSX_PHYSICS_MODEL)");
+    if (k.kind != want.kind || k.task != want.task || k.n_blue != want.n_blue || k.n_yellow != want.n_yellow ||
+        k.num_envs != want.num_envs || k.state_rows != want.state_rows || k.aux_rows != want.aux_rows || k.obs_dim != want.obs_dim)
+        return fail(RSX_ERR_ARG, "the checkpoint was taken from a different configuration (simulator kind, team sizes, batch or task)");
+    if (k.field_type != want.field_type || k.time_step_ms != want.time_step_ms || k.field_rows != want.field_rows)
+        return fail(RSX_ERR_ARG, "the checkpoint was taken with another field type or time step");
+    if (k.max_steps != want.max_steps)
+        return fail(RSX_ERR_ARG, "the checkpoint was taken with another max_episode_steps (TimeLimit)");
+    if (k.key0 != want.key0 || k.key1 != want.key1 || k.env_id_base != want.env_id_base)
+        return fail(RSX_ERR_ARG, "the checkpoint was taken with another seed or env_id_base: attach the task with the same ones");
+    // the section sizes follow from the configuration checked above; they are used for pointer arithmetic and as copy lengths below,
+    // so a header that disagrees (a damaged file) is refused instead of being trusted
+    if (k.state_bytes != want.state_bytes || k.aux_bytes != want.aux_bytes || k.obs_bytes != want.obs_bytes || k.flag_bytes != want.flag_bytes)
+        return fail(RSX_ERR_ARG, "the checkpoint header is damaged (section sizes do not match its configuration)");
+    if (bytes < ckpt_size(k)) return fail(RSX_ERR_ARG, "blob is truncated");
+    hipStream_t s = (hipStream_t)stream;
+    const char* p = (const char*)blob + sizeof(CkptHeader);
+    h->host_state_valid = false;
+    const size_t rowb = (size_t)h->P.num_envs * sizeof(float), pitch = (size_t)h->P.row_stride * sizeof(float);
+    HIP_TRY(hipMemcpy2DAsync(h->d_state, pitch, p, rowb, rowb, (size_t)k.state_rows, hipMemcpyHostToDevice, s)); p += k.state_bytes;
+    HIP_TRY(hipMemcpy2DAsync(h->d_aux, pitch, p, rowb, rowb, (size_t)k.aux_rows, hipMemcpyHostToDevice, s)); p += k.aux_bytes;
+    HIP_TRY(hipMemcpyAsync(h->d_obs, p, k.obs_bytes, hipMemcpyHostToDevice, s)); p += k.obs_bytes;
+    HIP_TRY(hipMemcpyAsync(h->d_final_obs, p, k.obs_bytes, hipMemcpyHostToDevice, s)); p += k.obs_bytes;
+    HIP_TRY(hipMemcpyAsync(h->d_flags, p, k.flag_bytes, hipMemcpyHostToDevice, s));
+    if (h->d_phys) {   // ranges and mask of the blob, this handle's error word
+        p += k.flag_bytes;
+        PhysHeader hd;
+        std::memcpy(&hd, p, sizeof(hd)); p += sizeof(PhysHeader);
+        if (hd.kind != h->P.kind || hd.ts_ms != h->time_step_ms) return fail(RSX_ERR_ARG, "the checkpoint's physics section is damaged");
+        launch_phys_ranges(h->d_phys, hd.lo, hd.hi, hd.mask, s);
+        HIP_TRY(launch_status());
+        HIP_TRY(hipMemcpy2DAsync(phys_raw(h->d_phys), pitch, p, rowb, rowb, (size_t)(NPHYS + NCOEF), hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(hipMemsetAsync(h->d_mslots, 0, (size_t)MSLOTS * RSX_METRICS * sizeof(unsigned long long), s));
+    HIP_TRY(hipMemcpyAsync(h->d_metrics, k.metrics, sizeof(k.metrics), hipMemcpyHostToDevice, s));
+    if (h->tick_dev) {   // device-keyed handle: every slot takes the blob's step counter; a refused-launch mark is cleared with it
+        launch_tick_fill(tick_slot0(h), 0, h->tick_slots_alloc, k.tick, 0, s);
+        HIP_TRY(launch_status());
+        HIP_TRY(hipMemsetAsync(tick_words(h) + TICK_ERR_WORD, 0, sizeof(uint32_t), s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    h->tick = k.tick;
+    h->task_ready = true;
+    return RSX_OK;
+}
+
+int rsx_metrics_fold(rsx_sim* h, void* stream) {
+    RSX_ENTER_TASK(h);
+    launch_fold_metrics(h->d_metrics, h->d_mslots, (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
+int rsx_read_metrics(rsx_sim* h, int64_t out[RSX_METRICS], void* stream) {
+    RSX_ENTER_TASK(h);
+    if (!out) return fail(RSX_ERR_ARG, "out is null");
+    hipStream_t s = (hipStream_t)stream;
+    launch_fold_metrics(h->d_metrics, h->d_mslots, s);
+    HIP_TRY(launch_status());
+    HIP_TRY(hipMemcpyAsync(out, h->d_metrics, RSX_METRICS * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    uint32_t refused = 0;
+    if (h->tick_dev) HIP_TRY(hipMemcpyAsync(&refused, tick_words(h) + TICK_ERR_WORD, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (refused) return fail(RSX_ERR_STATE, "step counter exhausted: stepping launches of this device-keyed handle were refused on the device (out[] is valid; a handle takes at most 2^32 - 1 fused steps)");
+    return RSX_OK;
+}
+
+// ---- transfer of running episodes between envs and handles ----
+// the count of skipped pairs lives in a spare word of the task arena's metrics block (metrics[8] | ... | step-counter slots from
+// TICK_SLOT_WORD0), zeroed by rsx_task_attach / rsx_task_reseed: a cross-handle transfer allocates nothing
+constexpr int XFER_ERR_WORD = 20;
+static_assert(XFER_ERR_WORD >= 2 * RSX_METRICS && XFER_ERR_WORD != TICK_ERR_WORD && XFER_ERR_WORD < TICK_SLOT_WORD0, "spare word of the metrics block");
+
+static XferSide xfer_side_of(const rsx_sim* h) {
+    return XferSide{h->d_state, h->d_aux, h->d_phys ? phys_raw(h->d_phys) : nullptr, h->d_obs, h->d_final_obs, h->d_flags,
+                    h->P.row_stride, h->P.num_envs};
+}
+
+int rsx_task_transfer(rsx_sim* dst, rsx_sim* src, const int32_t* dst_ids_dev, const int32_t* src_ids_dev, int n, void* stream) {
+    if (!src) return fail(RSX_ERR_ARG, "null handle");
+    RSX_ENTER_TASK(dst);
+    if (src->P.task == RSX_TASK_NONE) return fail(RSX_ERR_STATE, "no task attached to the source (rsx_task_attach)");
+    if (!dst->task_ready || !src->task_ready)
+        return fail(RSX_ERR_STATE, "rsx_task_reset / rsx_task_reset_to must come before rsx_task_transfer, on both handles");
+    if (src->device != dst->device) return fail(RSX_ERR_ARG, "the handles live on different devices");
+    const Params &D = dst->P, &S = src->P;
+    if (D.kind != S.kind || D.task != S.task || D.n_blue != S.n_blue || D.n_yellow != S.n_yellow)
+        return fail(RSX_ERR_ARG, "the handles differ in simulator kind, task or team sizes");
+    if (dst->field_type != src->field_type || dst->time_step_ms != src->time_step_ms)
+        return fail(RSX_ERR_ARG, "the handles differ in field type or time step");
+    if (D.max_steps != S.max_steps) return fail(RSX_ERR_ARG, "the handles differ in max_episode_steps (TimeLimit)");
+    if ((dst->d_phys != nullptr) != (src->d_phys != nullptr))
+        return fail(RSX_ERR_ARG, "per-env physics is enabled on one handle only (rsx_physics_enable)");
+    if (n < 0) return fail(RSX_ERR_ARG, "n must be >= 0");
+    if ((!dst_ids_dev && n > D.num_envs) || (!src_ids_dev && n > S.num_envs))
+        return fail(RSX_ERR_ARG, "n exceeds num_envs of a side without an id array (NULL = envs 0..n-1)");
+    if (n == 0) return RSX_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const int SR = state_rows(dst), AR = aux_rows(D.n_robots), PR = dst->d_phys ? NPHYS + NCOEF : 0, OD = D.obs_dim;
+    const int pot_row = D.task == RSX_TASK_VSS_V0 ? SR + ROW_PREV_POT : -1;
+    uint32_t* const err = tick_words(dst) + XFER_ERR_WORD;
+    // (the placement cache of either handle needs no invalidation: an entry is tagged with the episode id it was made for and is a
+    // pure function of (seed, global env id, episode) — a tag that no longer matches takes the inline path, one that matches by
+    // coincidence holds the right placement)
+    if (dst != src) {
+        launch_transfer(XFER_DIRECT, xfer_side_of(dst), xfer_side_of(src), D.num_envs, S.num_envs, dst_ids_dev, src_ids_dev, n, err,
+                        SR, AR, PR, OD, pot_row, D.hl_goal, D.inv_len_cm, s);
+        HIP_TRY(launch_status());
+        return RSX_OK;
+    }
+    // same handle: every read before every write — gather the n records into the staging buffer, then scatter them
+    rsx_sim* const h = dst;
+    if (n > h->xfer_cap) {
+        if (stream_is_capturing(s))
+            return fail(RSX_ERR_STATE, "a same-handle rsx_task_transfer whose staging buffer has to grow cannot be captured: make one eager call with n = " +
+                                       std::to_string(n) + " (or more) before the capture");
+        HIP_TRY(hipStreamSynchronize(s));
+        char* p = nullptr;
+        HIP_TRY(hipMalloc((void**)&p, carve_xfer_stage(nullptr, (size_t)n, SR, AR, OD)));
+        h->xfer_stage.push_back(p);
+        h->xfer_cap = n;
+    }
+    XferSide st{};
+    carve_xfer_stage(h->xfer_stage.back(), (size_t)h->xfer_cap, SR, AR, OD, &st);
+    launch_transfer(XFER_GATHER, st, xfer_side_of(h), D.num_envs, D.num_envs, dst_ids_dev, src_ids_dev, n, err, SR, AR, PR, OD, pot_row,
+                    D.hl_goal, D.inv_len_cm, s);
+    launch_transfer(XFER_SCATTER, xfer_side_of(h), st, D.num_envs, D.num_envs, dst_ids_dev, src_ids_dev, n, err, SR, AR, PR, OD, -1,
+                    D.hl_goal, D.inv_len_cm, s);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
+int rsx_task_transfer_errors(rsx_sim* dst, int64_t* out, void* stream) {
+    RSX_ENTER(dst);
+    if (dst->P.task == RSX_TASK_NONE) return fail(RSX_ERR_STATE, "no task attached (rsx_task_attach)");
+    if (!out) return fail(RSX_ERR_ARG, "out is null");
+    return read_and_clear_word(tick_words(dst) + XFER_ERR_WORD, out, (hipStream_t)stream);
+}
+
+}  // extern "C"

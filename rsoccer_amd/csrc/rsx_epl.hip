@@ -1,6 +1,6 @@
 // rsx_epl.hip — the one-lane-per-env kernels (VSS-v0 and the four SSL tasks) in their own translation unit:
 // built with the compiler's default machine scheduler and explicit occupancy targets per entry point, while
-// rsx_api.hip is built with -amdgpu-sched-strategy=max-ilp, which suits the short 8-lanes-per-env kernels at
+// rsx_lanes.hip is built with -amdgpu-sched-strategy=max-ilp, which suits the short 8-lanes-per-env kernels at
 // small batches but costs these a wave of occupancy.
 #include <hip/hip_runtime.h>
 

@@ -157,10 +157,7 @@ __device__ __forceinline__ void vss_epl_body(RSX_HOT_ARGS, const Params& P_, con
             // the 8-lane kernel keeps in memory — 8 bytes per env-step less traffic for ~40 instructions
             // (later steps of a multi-step launch carry it in a register)
             const float bx = ball.x, by = ball.y;
-            float dx_d = (P.hl_goal + bx) * 100.0f, dx_a = (P.hl_goal - bx) * 100.0f, dy = by * 100.0f;
-            float dy2 = 2.0f * (dy * dy);
-            float dist_1 = -sqrtf(dx_a * dx_a + dy2), dist_2 = sqrtf(dx_d * dx_d + dy2);
-            prev_pot = ((dist_1 + dist_2) * P.inv_len_cm - 1.0f) * 0.5f;
+            prev_pot = vss_ball_potential(bx, by, P.hl_goal, P.inv_len_cm);
             if (STEP) asm volatile("" : "+v"(prev_pot));   // computed HERE: one value across the physics, not the two coordinates it is made of
         }
         // ---- actions -> commands (vss_gym.py:119-142,235-254) ----
@@ -286,6 +283,7 @@ __device__ __forceinline__ void vss_epl_body(RSX_HOT_ARGS, const Params& P_, con
             if (bx > P.half_len) { info[0] += 1.0f; info[4] += 1.0f; reward = 10.0f; term = 1; }
             else if (bx < -P.half_len) { info[0] -= 1.0f; info[5] += 1.0f; reward = -10.0f; term = 1; }
             else {
+                // rsx_math.hpp: vss_ball_potential, spelled out (a call here changes this kernel's instruction stream)
                 float dx_d = (P.hl_goal + bx) * 100.0f, dx_a = (P.hl_goal - bx) * 100.0f, dy = by * 100.0f;
                 float dy2 = 2.0f * (dy * dy);
                 float dist_1 = -sqrtf(dx_a * dx_a + dy2), dist_2 = sqrtf(dx_d * dx_d + dy2);

@@ -48,29 +48,7 @@
 
 namespace rsx {
 
-// rows of the per-env scalar arena `aux` ([rows][B], 4 bytes each)
-constexpr int ROW_REWARD = 0, ROW_PREV_POT = 1, ROW_EP_RET = 2, ROW_STEPS = 3, ROW_EPISODE = 4,
-              ROW_INFO = 5 /* 10 rows */, ROW_OU = 15 /* 2*N rows */;
-// ROW_PREV_POT is the per-episode task scalar: previous ball potential (VSS-v0), checkpoint
-// counter (dribbling), stalled-step counter (pass endurance)
-__host__ __device__ constexpr int aux_rows(int n_robots) { return ROW_OU + 2 * n_robots; }
-
-struct Buffers {
-    float* state;          // [state_dim+X_ROWS][B]
-    float* aux;            // [aux_rows][B]   reward, prev_pot, ep_ret, steps, episode, info, ou
-    float* obs;            // [B][obs_dim]
-    float* final_obs;      // [B][obs_dim]
-    uint8_t* flags;        // [3][B]          terminated, truncated, env mask of reset_to (MODE_REFRESH)
-    const float* cmds;     // [N*C][B]        (raw simulator path)
-    const float* actions;  // [B][act_dim] or nullptr = random
-    unsigned long long* metrics;  // [RSX_METRICS]
-    unsigned long long* mslots;   // [MSLOTS][RSX_METRICS]: per-block-group partial sums of the episode counters (see metric_slot)
-    float* pcache;                // placement cache (see placement_helper): [2][3 * (N + 1) + 1][B], or nullptr
-    unsigned long long* pcstats;  // [2] resets served from the cache / placed inline (nullptr unless RSX_PCACHE_STATS=1)
-#ifdef RSX_TIMING
-    unsigned long long* dbg;      // [8][gridDim] s_memtime stamps (development builds only)
-#endif
-};
+// (the rows of the per-env scalar arena `aux` and the launch argument block `Buffers`: rsx_params.hpp)
 
 // (Observation values go straight from the lane that owns them to the row in HBM — scattered 4-byte stores inside the tile's contiguous
 // run of rows — not through an LDS staging area + a coalesced copy-out: measured, VSS-v0 4096 envs 10.01 -> 9.74 us per step,
@@ -100,7 +78,7 @@ struct Shared {
 
 // Addresses into the [rows][B] arrays on the hot paths: a uniform base pointer (scalar registers) + ONE 32-bit BYTE offset per
 // lane — the global_load / global_store "saddr" form, no 64-bit vector multiply-adds and shifts per access.  The host refuses
-// batches whose arrays would reach 4 GB (rsx_api.hip: RSX_ERR_ARG at create / attach).
+// batches whose arrays would reach 4 GB (rsx_create / rsx_task_attach: RSX_ERR_ARG).
 typedef uint32_t ix_t;
 __device__ __forceinline__ float& at_byte(float* base, const ix_t off) { return *reinterpret_cast<float*>(reinterpret_cast<char*>(base) + off); }
 __device__ __forceinline__ const float& at_byte(const float* base, const ix_t off) { return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + off); }
@@ -794,7 +772,7 @@ __global__ __launch_bounds__(64) void sim_step_phys_kernel(RSX_HOT_ARGS, const P
 // (pass endurance, contested possession) that was the whole step time (605 us instead of 82 us).  The step
 // kernels therefore add into one of MSLOTS 64-byte lines, picked by block id, and fold_metrics_kernel
 // (rsx_read_metrics / rsx_metrics_fold) adds the lines into metrics[] and clears them.
-constexpr int MSLOTS = 256;
+// (MSLOTS: rsx_params.hpp)
 __device__ __forceinline__ unsigned long long* metric_slot(const Buffers& b) {
     return b.mslots + (size_t)(blockIdx.x & (MSLOTS - 1)) * RSX_METRICS;
 }
@@ -809,14 +787,11 @@ __device__ __forceinline__ unsigned long long* metric_slot(const Buffers& b) {
 // and writes slot b + n back; launches of a handle are stream-ordered, nobody else touches that slot, so this needs no
 // atomic and cannot race with late-starting workgroups of the same launch (a single shared word could: a workgroup
 // that starts after another one finished would read the next launch's tick).  All slots of a handle hold the same
-// value between launches (the host re-syncs the slots a smaller grid did not cover, rsx_api.hip: tick_resync).
+// value between launches (the host re-syncs the slots a smaller grid did not cover, rsx_api_task.hip: tick_resync).
 // A counter about to wrap refuses the launch: every workgroup sees the same value, sets the error word and returns
 // before touching any state (rsx.h: "checked, never wrapped").
 // ---------------------------------------------------------------------------------------------
-constexpr int RSX_TICK_DEV = 1 << 30;        // flag bit of the n_steps kernel argument
-constexpr int RSX_N_STEPS_MASK = RSX_TICK_DEV - 1;
-constexpr int TICK_ERR_WORD = 18;            // uint32 index behind metrics[0]: bytes 72..75
-constexpr int TICK_SLOT_WORD0 = 64;          // uint32 index of slot 0: 256 bytes behind metrics[0]
+// (RSX_TICK_DEV, RSX_N_STEPS_MASK, TICK_ERR_WORD, TICK_SLOT_WORD0: rsx_params.hpp)
 struct StepTick { uint32_t t; bool ok; };
 __device__ __forceinline__ StepTick step_tick(const bool dev, const Params& P, const Buffers& bufs, const uint32_t n) {
     if (!dev) return StepTick{P.tick_base, true};
@@ -956,10 +931,7 @@ __device__ __forceinline__ void task_reward(const Params& P, const float* xr, co
         if (bx > P.half_len) { info[0] += 1.0f; info[4] += 1.0f; reward = 10.0f; term = 1; }
         else if (bx < -P.half_len) { info[0] -= 1.0f; info[5] += 1.0f; reward = -10.0f; term = 1; }
         else {
-            float dx_d = (P.hl_goal + bx) * 100.0f, dx_a = (P.hl_goal - bx) * 100.0f, dy = by * 100.0f;
-            float dy2 = 2.0f * (dy * dy);
-            float dist_1 = -sqrtf(dx_a * dx_a + dy2), dist_2 = sqrtf(dx_d * dx_d + dy2);
-            float pot = ((dist_1 + dist_2) * P.inv_len_cm - 1.0f) * 0.5f;
+            float pot = vss_ball_potential(bx, by, P.hl_goal, P.inv_len_cm);
             float grad = 0.0f;
             if (!first_step) grad = clampf((pot - prev_pot) * 3.0f * P.inv_dt, -5.0f, 5.0f);
             prev_pot = pot;
@@ -1366,7 +1338,7 @@ __device__ __forceinline__ void placement_helper(const Params& P, const Buffers&
 //   MODE_RESET   reset() with random placement
 //   MODE_REFRESH open a new episode on the state already in the buffers for the envs flagged in
 //                the third row of the flags array (reset_to); their observations recomputed, state untouched
-constexpr int MODE_STEP = 0, MODE_RESET = 1, MODE_REFRESH = 2, MODE_ROLLOUT = 3;
+// (the constants: rsx_params.hpp)
 
 #ifndef RSX_TASK_KERNEL_ATTR
 #define RSX_TASK_KERNEL_ATTR   // (rsx_big.hip sets an occupancy target for its build of this kernel)

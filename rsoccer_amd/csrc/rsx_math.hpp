@@ -111,6 +111,15 @@ __device__ __forceinline__ float atan2_f32(float y, float x) {
     return y > 0.0f ? 1.5707963267948966f : (y < 0.0f ? -1.5707963267948966f : 0.0f);
 }
 
+// VSS-v0's ball potential (vss_gym.py:256-283) of a ball at (bx, by): the ONE expression of the step kernels, of checkpoint save (host),
+// transfer and lookahead, which must agree bit for bit (-ffp-contract=off; sqrtf is correctly rounded on both sides)
+__host__ __device__ __forceinline__ float vss_ball_potential(float bx, float by, float hl_goal, float inv_len_cm) {
+    float dx_d = (hl_goal + bx) * 100.0f, dx_a = (hl_goal - bx) * 100.0f, dy = by * 100.0f;
+    float dy2 = 2.0f * (dy * dy);
+    float dist_1 = -sqrtf(dx_a * dx_a + dy2), dist_2 = sqrtf(dx_d * dx_d + dy2);
+    return ((dist_1 + dist_2) * inv_len_cm - 1.0f) * 0.5f;
+}
+
 // Philox4x32 (Salmon, Moraes, Dror, Shaw — SC'11).  counter = (global env id, episode,
 // tick, domain), key = (seed lo, seed hi): a draw depends only on WHAT it is for, never on the
 // thread that computes it, so results are invariant to batch size, batch position and sharding.

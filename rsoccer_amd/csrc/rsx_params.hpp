@@ -339,4 +339,59 @@ inline int derive_task(int task, uint64_t seed, uint64_t env_id_base, int max_st
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// what the host and the kernels share about a launch (no kernel code: host units include this header alone)
+// ---------------------------------------------------------------------------------------------
+// rows of the per-env scalar arena `aux` ([rows][B], 4 bytes each)
+constexpr int ROW_REWARD = 0, ROW_PREV_POT = 1, ROW_EP_RET = 2, ROW_STEPS = 3, ROW_EPISODE = 4,
+              ROW_INFO = 5 /* 10 rows */, ROW_OU = 15 /* 2*N rows */;
+// ROW_PREV_POT is the per-episode task scalar: previous ball potential (VSS-v0), checkpoint
+// counter (dribbling), stalled-step counter (pass endurance)
+constexpr int aux_rows(int n_robots) { return ROW_OU + 2 * n_robots; }
+
+struct Buffers {
+    float* state;          // [state_dim+X_ROWS][B]
+    float* aux;            // [aux_rows][B]   reward, prev_pot, ep_ret, steps, episode, info, ou
+    float* obs;            // [B][obs_dim]
+    float* final_obs;      // [B][obs_dim]
+    uint8_t* flags;        // [3][B]          terminated, truncated, env mask of reset_to (MODE_REFRESH)
+    const float* cmds;     // [N*C][B]        (raw simulator path)
+    const float* actions;  // [B][act_dim] or nullptr = random
+    unsigned long long* metrics;  // [RSX_METRICS]
+    unsigned long long* mslots;   // [MSLOTS][RSX_METRICS]: per-block-group partial sums of the episode counters (see metric_slot)
+    float* pcache;                // placement cache (see placement_helper): [2][3 * (N + 1) + 1][B], or nullptr
+    unsigned long long* pcstats;  // [2] resets served from the cache / placed inline (nullptr unless RSX_PCACHE_STATS=1)
+#ifdef RSX_TIMING
+    unsigned long long* dbg;      // [8][gridDim] s_memtime stamps (development builds only)
+#endif
+};
+
+// partial episode counters: lines of the metrics fold (rsx_kernels.hpp: metric_slot)
+constexpr int MSLOTS = 256;
+// the step counter of a device-keyed handle (rsx_kernels.hpp: step_tick)
+constexpr int RSX_TICK_DEV = 1 << 30;        // flag bit of the n_steps kernel argument
+constexpr int RSX_N_STEPS_MASK = RSX_TICK_DEV - 1;
+constexpr int TICK_ERR_WORD = 18;            // uint32 index behind metrics[0]: bytes 72..75
+constexpr int TICK_SLOT_WORD0 = 64;          // uint32 index of slot 0: 256 bytes behind metrics[0]
+// launch modes of the fused task kernels (rsx_kernels.hpp: task_step_kernel)
+constexpr int MODE_STEP = 0, MODE_RESET = 1, MODE_REFRESH = 2, MODE_ROLLOUT = 3;
+
+// ---- grids -------------------------------------------------------------------------------------------------------------
+// workgroups of a launch over `tiles` 64-lane tiles: a multiple of 8, an equal share for each XCD (rsx_kernels.hpp: tile_of_block)
+inline int tile_grid(const int tiles) { return ((tiles + 7) / 8) * 8; }
+inline int lane_grid(const int L, const int num_envs) { const int G = 64 / L; return tile_grid((num_envs + G - 1) / G); }
+inline int env_grid(const int num_envs) { return tile_grid((num_envs + 63) / 64); }   // one lane per env: 64 envs per tile
+
+// ---- the variant policy ------------------------------------------------------------------------------------------------
+// The common team sizes get the robot count as a template constant (pair loops unrolled); anything else runs the generic
+// variant of its lane-group width.  Returns NR.
+inline int specialised_robots(const int kind, const int n_robots, const int n_blue, const int L) {
+    if (kind == RSX_KIND_VSS && n_robots == 6 && (L == 8 || L == 16) && n_blue == 3) return 6;   // 16: RSX_LANES_PER_ENV=16 (four envs per wave)
+    if (kind == RSX_KIND_VSS && n_robots == 10 && L == 16 && n_blue == 5) return 10;             // 5v5 field
+    if (kind == RSX_KIND_SSL && n_robots == 7 && (L == 8 || L == 16)) return 7;
+    if (kind == RSX_KIND_SSL && n_robots == 12 && L == 16) return 12;                            // 6v6 (field_type 0, ssl/README.md:4)
+    if (kind == RSX_KIND_SSL && n_robots == 22 && L == 32) return 22;
+    return 0;
+}
+
 }  // namespace rsx

@@ -1,8 +1,8 @@
 // rsx_phys.hip — the per-env physics kernels of librsx_hip.so (include/rsx.h: rsx_physics_*), in a translation unit of their own
-// so that the instantiations of the existing kernels in rsx_api.hip stay exactly what they were.
+// so that the instantiations of the existing kernels in rsx_lanes.hip stay exactly what they were.
 //
 // A physics-enabled handle always steps with the lane-group kernels (task_step_phys_kernel / sim_step_phys_kernel,
-// rsx_kernels.hpp): the same variants rsx_api.hip picks for a handle's team sizes and lanes per env, never the one-lane-per-env,
+// rsx_kernels.hpp): the same variants rsx_lanes.hip picks for a handle's team sizes and lanes per env, never the one-lane-per-env,
 // four-lanes-per-env or large-batch builds.
 #include <hip/hip_runtime.h>
 

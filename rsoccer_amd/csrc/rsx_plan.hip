@@ -119,10 +119,7 @@ __global__ __launch_bounds__(64) void task_lookahead_kernel(const float* __restr
         // expression on the same floats as task_reward's.  The one-lane-per-env step kernels recompute it the same way and do NOT keep
         // ROW_PREV_POT up to date (rsx_epl.hpp; rsx_task_checkpoint_save patches the row for the same reason), so the row is not read
         // here on any layout.  (The first step of an episode ignores the value.)
-        const float dx_d = (P.hl_goal + o.x) * 100.0f, dx_a = (P.hl_goal - o.x) * 100.0f, dy = o.y * 100.0f;
-        const float dy2 = 2.0f * (dy * dy);
-        const float dist_1 = -sqrtf(dx_a * dx_a + dy2), dist_2 = sqrtf(dx_d * dx_d + dy2);
-        prev_pot = ((dist_1 + dist_2) * P.inv_len_cm - 1.0f) * 0.5f;
+        prev_pot = vss_ball_potential(o.x, o.y, P.hl_goal, P.inv_len_cm);
     }
 
     // per-pair results, held by every lane of the pair (the ball lane's copy is the one that counts)

@@ -12,6 +12,22 @@ namespace rsx {
 struct Params;
 struct Buffers;
 
+// rsx_lanes.hip: the lane-group kernels (8 / 16 / 32 / 64 lanes per env) of a handle with `L` lanes per env and kernels specialised for
+// `NR` robots (rsx_params.hpp: specialised_robots; 0 = generic), `helpers` placement-helper workgroups behind the lane_grid tiles; and the utility kernels
+// of the C-ABI (count of non-finite floats, metrics fold, device-side teleport, wire format <-> device layout, tick slots [from, to) :=
+// value or := slot 0)
+void launch_sim(const Params& P, const Buffers& b, int L, int NR, float* state_out, int rand_tick, hipStream_t s);
+void launch_task(const Params& P, const Buffers& b, int L, int NR, int helpers, int n_steps, int mode, hipStream_t s);
+void launch_count_nonfinite(const float* p, size_t n, unsigned long long* out, hipStream_t s);
+void launch_fold_metrics(unsigned long long* metrics, unsigned long long* slots, hipStream_t s);
+void launch_reset_dev(float* st, const float* ball, const float* blue, const float* yellow, const uint8_t* mask, int B, int S, int rows,
+                      int rs, int nb, int ny, float r_ball, hipStream_t s);
+void launch_wire_cmds_in(const double* wire, float* cmds, unsigned B, unsigned NC, unsigned S, hipStream_t s);
+void launch_wire_state_out(const float* st, double* wire, unsigned B, unsigned rows, unsigned S, hipStream_t s);
+void launch_tick_fill(uint32_t* slots, int from, int to, uint32_t value, int copy, hipStream_t s);
+#ifdef RSX_TIMING
+inline unsigned long long* g_dbg = nullptr;   // development builds: where the kernels' time stamps go (rsx_lanes.hip: rsx_dbg_set)
+#endif
 // rsx_epl.hip: the one-lane-per-env kernels (large batches) and the four-lanes-per-env kernel of the SSL 11v11 scrimmage task
 // (single-step launches, n_steps = 1 | flags); *_grid: workgroups of those launches (the host sizes the per-workgroup tick slots
 // from these: rsx_kernels.hpp, step_tick)

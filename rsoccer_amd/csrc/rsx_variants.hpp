@@ -12,7 +12,7 @@
 // guards keep a branch that can never be taken for this KIND / TASK from instantiating a kernel of its own.
 //
 // Not here: the choice of LAYOUT for a handle (one lane per env, four lanes per env, the large-batch build, placement helpers,
-// the per-env physics route) — rsx_api.hip decides that in front of these tables.
+// the per-env physics route) — rsx_layout.hpp decides that (plan_layout), and rsx_api_task.hip dispatches on it in front of these tables.
 #pragma once
 #include <type_traits>
 #include <utility>
@@ -24,23 +24,7 @@ namespace rsx {
 
 template <int V> using int_c = std::integral_constant<int, V>;
 
-// ---- grids -------------------------------------------------------------------------------------------------------------
-// workgroups of a launch over `tiles` 64-lane tiles: a multiple of 8, an equal share for each XCD (rsx_kernels.hpp: tile_of_block)
-inline int tile_grid(const int tiles) { return ((tiles + 7) / 8) * 8; }
-inline int lane_grid(const int L, const int num_envs) { const int G = 64 / L; return tile_grid((num_envs + G - 1) / G); }
-inline int env_grid(const int num_envs) { return tile_grid((num_envs + 63) / 64); }   // one lane per env: 64 envs per tile
-
-// ---- the variant policy ------------------------------------------------------------------------------------------------
-// The common team sizes get the robot count as a template constant (pair loops unrolled); anything else runs the generic
-// variant of its lane-group width.  Returns NR.
-inline int specialised_robots(const int kind, const int n_robots, const int n_blue, const int L) {
-    if (kind == RSX_KIND_VSS && n_robots == 6 && (L == 8 || L == 16) && n_blue == 3) return 6;   // 16: RSX_LANES_PER_ENV=16 (four envs per wave)
-    if (kind == RSX_KIND_VSS && n_robots == 10 && L == 16 && n_blue == 5) return 10;             // 5v5 field
-    if (kind == RSX_KIND_SSL && n_robots == 7 && (L == 8 || L == 16)) return 7;
-    if (kind == RSX_KIND_SSL && n_robots == 12 && L == 16) return 12;                            // 6v6 (field_type 0, ssl/README.md:4)
-    if (kind == RSX_KIND_SSL && n_robots == 22 && L == 32) return 22;
-    return 0;
-}
+// (grids of a launch and the variant policy, specialised_robots: rsx_params.hpp — the host units need them without the kernels)
 
 // the generic variant of a lane-group width
 template <int MAX_L, typename F>
@@ -105,8 +89,7 @@ void with_mode(const int mode, F&& f) {
         default: f(int_c<MODE_REFRESH>{}); break;
     }
 }
-// ... and what a launch of that mode is given: only a single step reads fed actions, only the stepping modes a step count
-inline const float* mode_actions(const int mode, const float* actions) { return mode == MODE_STEP ? actions : nullptr; }
+// ... and what a launch of that mode is given: only the stepping modes a step count
 inline int mode_steps(const int mode, const int n_steps) { return mode == MODE_STEP || mode == MODE_ROLLOUT ? n_steps : 1; }
 
 // ---- launches ----------------------------------------------------------------------------------------------------------

@@ -20,7 +20,7 @@
 // The one row that is not copied: VSS-v0's previous ball potential (ROW_PREV_POT).  The one-lane-per-env VSS kernel derives it from
 // the ball position and never stores it (rsx_epl.hpp), so the row of a source stepped by that kernel is stale; the destination may be
 // stepped by a lane-group kernel, which reads it.  The launch that reads a HANDLE (DIRECT, GATHER) therefore recomputes it from the
-// source's ball position, with the float expression of the step kernels and of rsx_task_checkpoint_save (-ffp-contract=off).  No
+// source's ball position (rsx_math.hpp: vss_ball_potential, the expression of the step kernels and of rsx_task_checkpoint_save).  No
 // other layout leaves a row stale: the one-lane-per-env SSL kernels and the four-lane kernel store every row they change, and the
 // rows they skip (VSS-v0: the goal counters and the ball's height rows off a terminal step / a chip) hold the value they would write.
 #include <hip/hip_runtime.h>
@@ -29,6 +29,7 @@
 
 #include "rsx.h"
 #include "rsx_launch.hpp"
+#include "rsx_math.hpp"
 #include "rsx_units.hpp"
 
 namespace rsx {
@@ -92,10 +93,7 @@ __global__ __launch_bounds__(TPB) void transfer_kernel(const XferArgs a) {
         if (MODE != XFER_SCATTER && a.pot_row >= r0 && a.pot_row < r0 + RPS) {
             // vss_gym.py:256-283 as the step kernels evaluate it (rsx_epl.hpp, rsx_task_step_body.inc)
             const float bx = a.s.state[so], by = a.s.state[(uint32_t)a.s.stride + so];
-            const float dx_d = (a.hl_goal + bx) * 100.0f, dx_a = (a.hl_goal - bx) * 100.0f, dy = by * 100.0f;
-            const float dy2 = 2.0f * (dy * dy);
-            const float dist_1 = -sqrtf(dx_a * dx_a + dy2), dist_2 = sqrtf(dx_d * dx_d + dy2);
-            const uint32_t pot = __float_as_uint(((dist_1 + dist_2) * a.inv_len_cm - 1.0f) * 0.5f);
+            const uint32_t pot = __float_as_uint(vss_ball_potential(bx, by, a.hl_goal, a.inv_len_cm));
 #pragma unroll
             for (int k = 0; k < RPS; ++k) v[k] = r0 + k == a.pot_row ? pot : v[k];
         }

@@ -534,3 +534,29 @@ def test_make_vec_builds_the_fused_env_of_every_registered_id():
     env = rsoccer_amd.make_vec("VSS-v0", 8, max_episode_steps=5)
     assert env.max_episode_steps == 5
     env.close()
+
+
+def test_layout_names_at_thresholds(monkeypatch):
+    """rsx_task_layout at each task's automatic threshold and 64 envs below it names what tests/test_layout_plan.py's table says
+    (attach only: no reset, no step); and enabling per-env physics on a one-lane-per-env handle puts it on the lane-group kernels."""
+    from rsoccer_amd import _lib as L
+    from test_layout_plan import TASKS
+    monkeypatch.setenv("RSX_NO_WIRE_PATH", "1")   # no large pinned wire buffers
+    monkeypatch.delenv("RSX_LAYOUT", raising=False)
+    for name, kind, field_type, nb, ny, task, threshold, at, below in TASKS:
+        for B, want in ((threshold, at), (threshold - 64, below)):
+            sim = L.Sim(kind, field_type, nb, ny, 25, B)
+            try:
+                sim.task_attach(task, 0, 0, 0)
+                assert sim.task_layout() == want, (name, B)
+            finally:
+                sim.close()
+    monkeypatch.setenv("RSX_LAYOUT", "epl")
+    sim = L.Sim(L.KIND_VSS, 0, 3, 3, 25, 64)
+    try:
+        sim.task_attach(L.TASK_VSS_V0, 0, 0, 0)
+        assert sim.task_layout() == "one-lane-per-env"
+        sim.physics_enable()
+        assert sim.task_layout() == "8-lanes-per-env"
+    finally:
+        sim.close()

@@ -9,9 +9,13 @@ rm -rf $src; mkdir -p $src/csrc $src/include
 for f in $(git ls-tree --name-only $ref rsoccer_amd/csrc/); do git show $ref:$f > $src/csrc/$(basename $f); done
 git show $ref:include/rsx.h > $src/include/rsx.h
 C="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -Wno-unused-value -mllvm -amdgpu-kernarg-preload-count=12 -I$src/include -I$src/csrc $* -c"
-hipcc $C -mllvm -amdgpu-sched-strategy=max-ilp -o /tmp/_rsx_${name}_api.o $src/csrc/rsx_api.hip &
-hipcc $C -fno-slp-vectorize -o /tmp/_rsx_${name}_epl.o $src/csrc/rsx_epl.hip &
-hipcc $C -fno-slp-vectorize -o /tmp/_rsx_${name}_big.o $src/csrc/rsx_big.hip &
+# the units of the ref and their flags: the ref's own __graft_entry__.HIP_UNITS (no second copy of that table here)
+git show $ref:__graft_entry__.py > $src/units_of_ref.py
+objs=
+while read -r unit flags; do
+    hipcc $C $flags -o /tmp/_rsx_${name}_${unit%.hip}.o $src/csrc/$unit &
+    objs="$objs /tmp/_rsx_${name}_${unit%.hip}.o"
+done < <(python -c "import sys; sys.path.insert(0, '$src'); import units_of_ref as g; [print(u, *f) for u, f in g.HIP_UNITS]")
 wait
-hipcc --offload-arch=gfx950 -fPIC -shared -o tools/_dev/librsx_${name}.so /tmp/_rsx_${name}_api.o /tmp/_rsx_${name}_epl.o /tmp/_rsx_${name}_big.o
+hipcc --offload-arch=gfx950 -fPIC -shared -o tools/_dev/librsx_${name}.so $objs
 echo built tools/_dev/librsx_${name}.so

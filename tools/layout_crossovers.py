@@ -1,5 +1,5 @@
 """Development: every registered task over the mid-range batch sizes, lane-group kernels against the one-lane-per-env kernels
-(RSX_LAYOUT=lanes / epl) - where rsx_api.hip switches layouts.  python tools/layout_crossovers.py"""
+(RSX_LAYOUT=lanes / epl) - where rsx_layout.hpp switches layouts.  python tools/layout_crossovers.py"""
 import sys, os, time, subprocess
 CHILD = r'''
 import sys, os, time
