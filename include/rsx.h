@@ -363,6 +363,59 @@ int rsx_task_tick(rsx_sim* h, uint32_t* out, void* stream);
 int rsx_task_lookahead(rsx_sim* h, const float* actions_dev, int n_candidates, int horizon, float gamma,
                        float* returns_dev, int32_t* steps_dev, uint8_t* flags_dev, float* last_obs_dev, void* stream);
 
+/* ---- planning with candidates drawn on the device (additive extension of ABI 6) ---------------------------------------------
+ * The candidates of random shooting / CEM / MPPI carry no information that has to live in memory: each is a plan mean plus noise.
+ * Here the noise is a counter-based draw like every other random number of the engine, recomputed where it is needed, so the caller
+ * exchanges only [num_envs][H][act_dim] plans and [num_envs][K] returns with the engine; one planning iteration is two launches
+ * (rsx_task_lookahead_sampled, rsx_plan_update).
+ *
+ * The sampler — ONE definition for the three calls below.  For global env id g = env_id_base + e, candidate k in [0, K), step t in
+ * [0, H) and action component i in [0, act_dim) (act_dim as rsx_task_view reports it; scrimmage: 4 N, robot b owns 4 b .. 4 b + 3):
+ *     a[e][k][t][i] = clamp(mean[e][t][i] + sigma * eps(g, k, tick, t / hold, i), -1, 1)      for k >= 1
+ *     a[e][0][t][i] = clamp(mean[e][t][i], -1, 1)                                              (candidate 0: the unperturbed plan)
+ *   mean   [num_envs][H][act_dim] f32 device memory, dense; NULL = all zeros.
+ *   hold   >= 1: one drawn perturbation serves `hold` consecutive steps (segment s = t / hold, integer; H need not be a multiple).
+ *   tick   the handle's step counter as rsx_task_lookahead reads it (host-keyed handles: the host's count; device-keyed handles: read
+ *          on the device), never advanced: calls between the same two steps see the same candidates, after a step fresh ones, and a
+ *          captured call draws new noise on every replay.
+ *   eps    blocks of four standard normals.  Block q = s * ceil(act_dim / 4) + (i >> 2) is
+ *              philox4x32-7(counter = (g, k, tick, 6 | q << 8), key = (sample_seed lo, sample_seed hi))
+ *          whose words (x, y) and (z, w) each go through the Box-Muller of the engine's OU noise in float32: u1 = ((w0 >> 8) + 1) *
+ *          2^-24, ang = ((w1 >> 8) * 2^-24 - 0.5) * 2 pi, rad = sqrt(-2 ln u1) -> (rad cos ang, rad sin ang).  The four normals are
+ *          those of the first pair, then of the second; component i takes normal i & 3.  q must fit in 24 bits.
+ *   sample_seed  independent of the handle's seed: several refinement passes at one tick use different noise by passing different seeds. */
+typedef struct rsx_plan_sampler {
+    uint64_t sample_seed;
+    float sigma;    /* >= 0, finite */
+    int32_t hold;   /* >= 1 */
+} rsx_plan_sampler;
+
+/* rsx_task_lookahead with each candidate's actions produced by the sampler instead of loaded.  Outputs (returns_dev, steps_dev,
+ * flags_dev, last_obs_dev or NULL) and guarantees are rsx_task_lookahead's: exact (bit for bit rsx_task_lookahead of the actions
+ * rsx_plan_candidates writes, hence `horizon` rsx_task_step calls with them), a pair stops at its env's first episode end, no side
+ * effects (the handle is left exactly as it was), stream-ordered, never synchronises; on a device-keyed handle a launch that would pass
+ * the counter limit simulates nothing.  Refusals (nothing is enqueued): those of rsx_task_lookahead, and RSX_ERR_ARG for a null
+ * `s`, hold < 1, a negative or non-finite sigma, or ceil(horizon / hold) * ceil(act_dim / 4) > 2^24. */
+int rsx_task_lookahead_sampled(rsx_sim* h, const float* mean_dev, const rsx_plan_sampler* s, int n_candidates, int horizon, float gamma,
+                               float* returns_dev, int32_t* steps_dev, uint8_t* flags_dev, float* last_obs_dev, void* stream);
+/* Writes the very floats rsx_task_lookahead_sampled uses, for the same handle state: for tests, debugging and callers who want a
+ * sequence's neighbours.  Same refusals (the checks on the lookahead's own outputs and lane width apart); the handle is not touched. */
+int rsx_plan_candidates(rsx_sim* h, const float* mean_dev, const rsx_plan_sampler* s, int n_candidates, int horizon,
+                        float* actions_out_dev /* [num_envs][K][H][act_dim] */, void* stream);
+/* Folds returns_dev [num_envs][n_candidates] (finite) into a new plan without reading a candidate tensor: the candidates are drawn again.
+ *   best_dev      [num_envs] int32, or NULL: the index of the largest return, the lowest such index on ties.
+ *   temperature   == 0: new_mean[e] = a[e][best[e]], copied bit for bit (random shooting).
+ *                 >  0: w_k = exp((R_k - R_best) / temperature), new_mean[e][t][i] = sum_k w_k a[e][k][t][i] / sum_k w_k (MPPI).
+ *   new_mean_dev  [num_envs][H][act_dim] f32.  It may be mean_dev itself (in place: every element is read and written by the same
+ *                 thread); any other overlap of the two arrays is refused.
+ * The arithmetic is fixed, so the same call gives the same bits: weights in float32, sums over k = 0, 1, ..., K - 1 accumulated in
+ * float64 by one thread per (env, step, block of four components), one division, one rounding; no atomics.
+ * Reads the step counter the way the other two calls do, so lookahead_sampled -> update with no step in between agree on the
+ * candidates, on host-keyed and device-keyed handles, eager or replayed.  Refusals as rsx_plan_candidates, and RSX_ERR_ARG for a
+ * negative or non-finite temperature or a null returns_dev / new_mean_dev. */
+int rsx_plan_update(rsx_sim* h, const float* mean_dev, const rsx_plan_sampler* s, int n_candidates, int horizon,
+                    const float* returns_dev, float temperature, float* new_mean_dev, int32_t* best_dev, void* stream);
+
 /* Debugging aid: number of non-finite floats in the state rows and, with a task attached, in the
  * observations, rewards and info rows.  Synchronises `stream`.  With RSX_DEBUG_FINITE=1 in the
  * environment every stepping call (rsx_step_dev, rsx_task_step, rsx_task_step_n, rsx_task_rollout)

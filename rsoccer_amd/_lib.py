@@ -50,11 +50,17 @@ SYMBOLS = (
     "rsx_trace_load", "rsx_trace_eval",
     "rsx_render_view_reference", "rsx_render_size", "rsx_render_field", "rsx_render_open", "rsx_render", "rsx_render_errors",
     "rsx_task_transfer", "rsx_task_transfer_errors",
+    "rsx_task_lookahead_sampled", "rsx_plan_candidates", "rsx_plan_update",
 )
 
 
 class RsxError(RuntimeError):
     pass
+
+
+class PlanSampler(C.Structure):
+    """rsx_plan_sampler (include/rsx.h): the noise of sampled planning candidates"""
+    _fields_ = [("sample_seed", C.c_uint64), ("sigma", C.c_float), ("hold", C.c_int32)]
 
 
 class DevView(C.Structure):
@@ -149,6 +155,9 @@ def load():
     lib.rsx_task_tick.argtypes = [vp, C.POINTER(C.c_uint32), vp]
     lib.rsx_drop_pending_hip_error.argtypes = []
     lib.rsx_task_lookahead.argtypes = [vp, vp, ip, ip, C.c_float, vp, vp, vp, vp, vp]
+    lib.rsx_task_lookahead_sampled.argtypes = [vp, vp, C.POINTER(PlanSampler), ip, ip, C.c_float, vp, vp, vp, vp, vp]
+    lib.rsx_plan_candidates.argtypes = [vp, vp, C.POINTER(PlanSampler), ip, ip, vp, vp]
+    lib.rsx_plan_update.argtypes = [vp, vp, C.POINTER(PlanSampler), ip, ip, vp, C.c_float, vp, vp, vp]
     lib.rsx_physics_defaults.argtypes = [ip, vp]
     lib.rsx_physics_derive.argtypes = [ip, ip, vp, vp]
     lib.rsx_physics_enable.argtypes = [vp, vp]
@@ -461,6 +470,30 @@ class Sim:
         straight to ctypes."""
         rc = self._lib.rsx_task_lookahead(self._h, actions_ptr, int(n_candidates), int(horizon), float(gamma), returns_ptr, steps_ptr,
                                           flags_ptr, last_obs_ptr, stream)
+        if rc:
+            _chk(rc)
+
+    def task_lookahead_sampled(self, mean_ptr, sampler, n_candidates, horizon, gamma, returns_ptr, steps_ptr, flags_ptr, last_obs_ptr=None,
+                               stream=None):
+        """rsx_task_lookahead_sampled: rsx_task_lookahead with the candidates drawn on the device around the plan ``mean``
+        ([B][H][act_dim] f32 device address or None = zeros) by ``sampler`` (a PlanSampler, or None to pass NULL)."""
+        rc = self._lib.rsx_task_lookahead_sampled(self._h, mean_ptr, None if sampler is None else C.byref(sampler), int(n_candidates),
+                                                  int(horizon), float(gamma), returns_ptr, steps_ptr, flags_ptr, last_obs_ptr, stream)
+        if rc:
+            _chk(rc)
+
+    def plan_candidates(self, mean_ptr, sampler, n_candidates, horizon, out_ptr, stream=None):
+        """rsx_plan_candidates: the actions rsx_task_lookahead_sampled uses, written to out [B][K][H][act_dim] f32"""
+        rc = self._lib.rsx_plan_candidates(self._h, mean_ptr, None if sampler is None else C.byref(sampler), int(n_candidates), int(horizon),
+                                           out_ptr, stream)
+        if rc:
+            _chk(rc)
+
+    def plan_update(self, mean_ptr, sampler, n_candidates, horizon, returns_ptr, temperature, new_mean_ptr, best_ptr=None, stream=None):
+        """rsx_plan_update: fold returns [B][K] into new_mean [B][H][act_dim] (temperature 0: the best candidate; > 0: the
+        softmax-weighted mean) by drawing the candidates again; best [B] i32 or None"""
+        rc = self._lib.rsx_plan_update(self._h, mean_ptr, None if sampler is None else C.byref(sampler), int(n_candidates), int(horizon),
+                                       returns_ptr, float(temperature), new_mean_ptr, best_ptr, stream)
         if rc:
             _chk(rc)
 

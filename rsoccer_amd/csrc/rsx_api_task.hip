@@ -1,11 +1,12 @@
 // rsx_api_task.hip — the fused tasks of the C-ABI (include/rsx.h: rsx_task_*, rsx_read_metrics): attach, reseed, capture, tick,
-// layout, view, reset, step, rollout, lookahead, metrics, checkpoint and transfer.  Host code only.
+// layout, view, reset, step, rollout, lookahead, sampled planning, metrics, checkpoint and transfer.  Host code only.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 
 #include "rsx_handle.hpp"
 #include "rsx_math.hpp"
+#include "rsx_plan_common.hpp"
 
 using namespace rsx;
 
@@ -297,6 +298,79 @@ int rsx_task_lookahead(rsx_sim* h, const float* actions_dev, int n_candidates, i
     P.tick_base = h->tick;   // the tick the next step would take; not advanced
     launch_task_lookahead(P, h->L, h->NR, h->d_state, h->d_aux, h->tick_dev ? tick_slot0(h) : nullptr, h->d_phys,
                           actions_dev, n_candidates, horizon, gamma, returns_dev, steps_dev, flags_dev, last_obs_dev, (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
+// ---- planning with candidates drawn on the device (rsx.h: rsx_plan_sampler) ----
+// what the three calls check alike; on success S is the sampler as the kernels take it and P the handle's parameters with the step
+// counter the next step would take (not advanced).  n_steps: what the counter limit is checked against (0: the call simulates nothing)
+static int plan_prologue(rsx_sim* h, const rsx_plan_sampler* s, int n_candidates, int horizon, int n_steps, hipStream_t stream, Params* P,
+                         PlanSampler* S) {
+    if (h->P.task == RSX_TASK_NONE) return fail(RSX_ERR_STATE, "no task attached (rsx_task_attach)");
+    RSX_NEED_RESET(h);
+    if (n_candidates < 1 || horizon < 1) return fail(RSX_ERR_ARG, "n_candidates and horizon must be >= 1");
+    if (!s) return fail(RSX_ERR_ARG, "the sampler (rsx_plan_sampler) must not be null");
+    if (s->hold < 1) return fail(RSX_ERR_ARG, "hold must be >= 1");
+    if (!std::isfinite(s->sigma) || s->sigma < 0.0f) return fail(RSX_ERR_ARG, "sigma must be finite and >= 0");
+    const int nblk = (h->M.act_dim + 3) / 4;
+    if ((long long)((horizon + s->hold - 1) / s->hold) * (long long)nblk > (1ll << 24))
+        return fail(RSX_ERR_ARG, "too many noise blocks: ceil(horizon / hold) * ceil(act_dim / 4) must fit in 24 bits");
+    int fl = 0;
+    if (int rc = step_prologue(h, stream, (uint64_t)n_steps, &fl)) return rc;   // capture of a host-keyed handle, counter limit
+    *P = h->P;
+    P->tick_base = h->tick;
+    *S = PlanSampler{(uint32_t)s->sample_seed, (uint32_t)(s->sample_seed >> 32), s->sigma, s->hold, nblk};
+    return RSX_OK;
+}
+
+int rsx_task_lookahead_sampled(rsx_sim* h, const float* mean_dev, const rsx_plan_sampler* s, int n_candidates, int horizon, float gamma,
+                               float* returns_dev, int32_t* steps_dev, uint8_t* flags_dev, float* last_obs_dev, void* stream) {
+    RSX_ENTER(h);   // (as rsx_task_lookahead: nothing the handle owns changes)
+    if (!returns_dev || !steps_dev || !flags_dev) return fail(RSX_ERR_ARG, "returns_dev, steps_dev and flags_dev must not be null");
+    if (!std::isfinite(gamma)) return fail(RSX_ERR_ARG, "gamma must be finite");
+    if (h->L > 32) return fail(RSX_ERR_ARG, "rsx_task_lookahead_sampled has no 64-lanes-per-env kernels (unset RSX_LANES_PER_ENV)");
+    if (lookahead_grid(h->L, h->P.num_envs, n_candidates > 0 ? n_candidates : 1) > 0x7FFFFFFFll)
+        return fail(RSX_ERR_ARG, "num_envs x n_candidates exceeds the launch limit (2^31 - 1 workgroups): split the candidates over several calls");
+    Params P; PlanSampler S;
+    if (int rc = plan_prologue(h, s, n_candidates, horizon, horizon, (hipStream_t)stream, &P, &S)) return rc;
+    launch_task_lookahead_sampled(P, h->L, h->NR, h->d_state, h->d_aux, h->tick_dev ? tick_slot0(h) : nullptr, h->d_phys, mean_dev, S,
+                                  n_candidates, horizon, gamma, returns_dev, steps_dev, flags_dev, last_obs_dev, (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
+int rsx_plan_candidates(rsx_sim* h, const float* mean_dev, const rsx_plan_sampler* s, int n_candidates, int horizon, float* actions_out_dev,
+                        void* stream) {
+    RSX_ENTER(h);
+    if (!actions_out_dev) return fail(RSX_ERR_ARG, "actions_out_dev must not be null");
+    Params P; PlanSampler S;
+    if (int rc = plan_prologue(h, s, n_candidates, horizon, 0, (hipStream_t)stream, &P, &S)) return rc;
+    if (plan_flat_grid(P.num_envs, n_candidates, horizon, S.nblk) > 0x7FFFFFFFll)
+        return fail(RSX_ERR_ARG, "num_envs x n_candidates x horizon exceeds the launch limit: split the candidates over several calls");
+    launch_plan_candidates(P, h->tick_dev ? tick_slot0(h) : nullptr, mean_dev, S, n_candidates, horizon, h->M.act_dim, actions_out_dev,
+                           (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
+int rsx_plan_update(rsx_sim* h, const float* mean_dev, const rsx_plan_sampler* s, int n_candidates, int horizon, const float* returns_dev,
+                    float temperature, float* new_mean_dev, int32_t* best_dev, void* stream) {
+    RSX_ENTER(h);
+    if (!returns_dev || !new_mean_dev) return fail(RSX_ERR_ARG, "returns_dev and new_mean_dev must not be null");
+    if (!std::isfinite(temperature) || temperature < 0.0f) return fail(RSX_ERR_ARG, "temperature must be finite and >= 0");
+    Params P; PlanSampler S;
+    if (int rc = plan_prologue(h, s, n_candidates, horizon, 0, (hipStream_t)stream, &P, &S)) return rc;
+    if (plan_flat_grid(P.num_envs, 1, horizon, S.nblk) > 0x7FFFFFFFll)
+        return fail(RSX_ERR_ARG, "num_envs x horizon exceeds the launch limit");
+    // in place is safe (every element is read and written by one thread); any other overlap of the two plans is not
+    if (mean_dev && mean_dev != new_mean_dev) {
+        const size_t bytes = (size_t)P.num_envs * (size_t)horizon * (size_t)h->M.act_dim * sizeof(float);
+        const char *a = (const char*)mean_dev, *b = (const char*)new_mean_dev;
+        if (a < b + bytes && b < a + bytes) return fail(RSX_ERR_ARG, "new_mean_dev overlaps mean_dev: pass the same pointer (in place) or disjoint arrays");
+    }
+    launch_plan_update(P, h->tick_dev ? tick_slot0(h) : nullptr, mean_dev, S, n_candidates, horizon, h->M.act_dim, returns_dev, temperature,
+                       new_mean_dev, best_dev, (hipStream_t)stream);
     HIP_TRY(launch_status());
     return RSX_OK;
 }

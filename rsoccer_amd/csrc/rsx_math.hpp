@@ -150,6 +150,9 @@ __device__ __forceinline__ u32x4 philox4x32(uint32_t c0, uint32_t c1, uint32_t c
 constexpr uint32_t DOM_ACT = 1u, DOM_PLACE = 3u, DOM_RAW = 4u;   // RAW: rsx_step_dev_random, counter (env, tick, robot, RAW)
 // PHYS: the per-env physics parameters redrawn at an episode start (rsx_physics_randomize), counter (env, episode, parameter, PHYS)
 constexpr uint32_t DOM_PHYS = 5u;
+// PLAN: the perturbations of sampled planning candidates (rsx_plan_common.hpp), counter (env, candidate, tick, PLAN | block << 8), keyed
+// by the call's sample_seed, not the handle's seed
+constexpr uint32_t DOM_PLAN = 6u;
 
 // 24-bit uniform in [0, 1)
 __device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * 5.9604644775390625e-08f; }

@@ -54,6 +54,18 @@ long long lookahead_grid(int L, int num_envs, int n_candidates);
 void launch_task_lookahead(const Params& P, int L, int NR, const float* state, const float* aux, const uint32_t* ticks, const float* phys,
                            const float* actions, int n_candidates, int horizon, float gamma, float* returns, int32_t* steps,
                            uint8_t* flags, float* last_obs, hipStream_t s);
+// rsx_plan_sampled.hip: the same with candidates drawn on the device (rsx_task_lookahead_sampled), those candidates written out
+// (rsx_plan_candidates) and returns folded into a new plan (rsx_plan_update).  PlanSampler: rsx_plan_common.hpp; mean: [num_envs][H][act_dim]
+// or nullptr = zeros; plan_flat_grid: workgroups of the two elementwise launches (n_candidates = 1 for the update)
+struct PlanSampler;
+void launch_task_lookahead_sampled(const Params& P, int L, int NR, const float* state, const float* aux, const uint32_t* ticks, const float* phys,
+                                   const float* mean, const PlanSampler& S, int n_candidates, int horizon, float gamma, float* returns,
+                                   int32_t* steps, uint8_t* flags, float* last_obs, hipStream_t s);
+long long plan_flat_grid(int num_envs, int n_candidates, int horizon, int nblk);
+void launch_plan_candidates(const Params& P, const uint32_t* ticks, const float* mean, const PlanSampler& S, int n_candidates, int horizon,
+                            int act_dim, float* out, hipStream_t s);
+void launch_plan_update(const Params& P, const uint32_t* ticks, const float* mean, const PlanSampler& S, int n_candidates, int horizon,
+                        int act_dim, const float* returns, float temperature, float* new_mean, int32_t* best, hipStream_t s);
 // rsx_render.hip: batched rgb frames (rsx_render_*).  render_check_view: nullptr when the view is valid (and the frame size), else the
 // message; render_field_host: the static field image [H][W][3]; RenderGeom: what the kernel needs of a view, in float32
 struct RenderGeom { int W, H; float s, cx, cy, r, rb; int square; };

@@ -73,6 +73,7 @@ class VecFusedEnv(RenderMixin):
         self.sim = _lib.Sim(self.KIND, ft, self.N_BLUE, self.N_YELLOW, int(self.TIME_STEP * 1000),
                             self.num_envs, int(device))
         self.sim.task_attach(self.TASK, int(seed), int(env_id_base), int(max_episode_steps or 0))
+        self._seed = int(seed)   # (what plan() derives its default noise key from; follows reset(seed=...))
         # per-env physics: only when asked for (an env built without these keywords steps with the compiled-in constants)
         self._physics = physics is not None or physics_ranges is not None
         if self._physics:
@@ -124,6 +125,7 @@ class VecFusedEnv(RenderMixin):
         (``rsx_task_reseed``; env ``i`` keeps its global id ``env_id_base + i``, which distinguishes the envs' streams)."""
         if seed is not None:
             self.sim.task_reseed(int(seed), self._stream())
+            self._seed = int(seed)
         self.sim.task_reset(self._stream())
         return self._t["obs"], {}
 
@@ -198,6 +200,101 @@ class VecFusedEnv(RenderMixin):
         out = {"return": ret, "steps": steps, "terminated": (flags & 1).bool(), "truncated": (flags & 2).bool()}
         if return_obs:
             out["last_obs"] = obs
+        return out
+
+    # ---- planning with candidates drawn on the device (include/rsx.h: rsx_plan_sampler) ----
+    def _plan_sampler(self, sigma, hold, seed, iteration):
+        """the rsx_plan_sampler of a call: ``sample_seed`` is a 64-bit mix (splitmix64) of ``seed`` (default: the env's) and
+        ``iteration``, so refinement passes at one step use different noise and two envs built alike use the same"""
+        sigma, hold = float(sigma), int(hold)
+        if not np.isfinite(sigma) or sigma < 0:
+            raise ValueError("sigma must be finite and >= 0")
+        if hold < 1:
+            raise ValueError("hold must be >= 1")
+        m = (1 << 64) - 1
+        z = ((self._seed if seed is None else int(seed)) + 0x9E3779B97F4A7C15 * (int(iteration) + 1)) & m
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+        return _lib.PlanSampler(z ^ (z >> 31), sigma, hold)
+
+    def _plan_mean(self, mean, horizon):
+        """(device tensor or None, H) of a ``mean=`` / ``horizon=`` argument pair, shapes checked on the INPUT as lookahead() does"""
+        torch = self._torch
+        if mean is None:
+            if horizon is None or int(horizon) < 1:
+                raise ValueError("without a mean, horizon= must be given and >= 1")
+            return None, int(horizon)
+        shape = tuple(np.shape(mean))
+        if len(shape) != 3 or shape[0] != self.num_envs or shape[2] != self.sim.act_dim or shape[1] < 1:
+            raise ValueError(f"mean must be [{self.num_envs}, H >= 1, {self.sim.act_dim}], got {shape}")
+        if horizon is not None and int(horizon) != shape[1]:
+            raise ValueError(f"horizon={horizon} does not match mean's {shape[1]} steps")
+        if isinstance(mean, torch.Tensor):
+            m = mean
+            if m.device != self.device or m.dtype != torch.float32 or not m.is_contiguous():
+                m = m.to(device=self.device, dtype=torch.float32).contiguous()
+        else:
+            m = torch.from_numpy(np.ascontiguousarray(mean, dtype=np.float32)).to(self.device)
+        return m, int(shape[1])
+
+    def plan(self, mean=None, horizon=None, K=64, sigma=0.5, hold=1, temperature=0.0, gamma=1.0, seed=None, iteration=0,
+             return_obs=False):
+        """One iteration of random shooting / MPPI from where every env stands now, in two launches and without a candidate tensor
+        (``rsx_task_lookahead_sampled``, ``rsx_plan_update``).
+
+        ``K`` candidate sequences per env are drawn ON THE DEVICE around the plan ``mean`` ``[num_envs, H, act_dim]`` (``None``: zeros,
+        with ``horizon=H``): candidate 0 is ``clamp(mean)``, candidate ``k >= 1`` is ``clamp(mean + sigma * noise)`` with one normal draw
+        held for ``hold`` steps.  The noise is keyed by (``seed`` — default: the env's —, ``iteration``, global env id, candidate, the
+        env's step counter): two calls between the same two steps see the same candidates unless ``iteration`` differs (refinement
+        passes), after a ``step()`` they are fresh, and a captured call draws new noise on every replay.  The candidates are scored
+        exactly as ``lookahead()`` scores them, then folded into the new plan: ``temperature == 0`` takes the best candidate,
+        ``temperature > 0`` the mean weighted by ``exp((return - best return) / temperature)``.
+
+        Returns a dict of fresh device tensors: ``action`` ``[num_envs, act_dim]`` (step 0 of the new plan: what to execute), ``mean``
+        ``[num_envs, H, act_dim]`` (the new plan; shift it by one step for a warm start), ``return`` / ``steps`` / ``terminated`` /
+        ``truncated`` ``[num_envs, K]`` as ``lookahead()``, ``best`` ``[num_envs]`` int32 (first index of the largest return), and with
+        ``return_obs=True`` ``last_obs``.  The env is left exactly as it was.  Capturable after ``enable_graph_capture()``."""
+        torch = self._torch
+        m, H = self._plan_mean(mean, horizon)
+        K, gamma, temperature = int(K), float(gamma), float(temperature)
+        if K < 1:
+            raise ValueError("K must be >= 1")
+        if not np.isfinite(gamma):
+            raise ValueError("gamma must be finite")
+        if not np.isfinite(temperature) or temperature < 0:
+            raise ValueError("temperature must be finite and >= 0")
+        smp = self._plan_sampler(sigma, hold, seed, iteration)
+        B, dev = self.num_envs, self.device
+        ret = torch.empty((B, K), dtype=torch.float32, device=dev)
+        steps = torch.empty((B, K), dtype=torch.int32, device=dev)
+        flags = torch.empty((B, K), dtype=torch.uint8, device=dev)
+        obs = torch.empty((B, K, self.sim.obs_dim), dtype=torch.float32, device=dev) if return_obs else None
+        new = torch.empty((B, H, self.sim.act_dim), dtype=torch.float32, device=dev)
+        best = torch.empty((B,), dtype=torch.int32, device=dev)
+        mp = None if m is None else m.data_ptr()
+        st = self._stream()
+        self.sim.task_lookahead_sampled(mp, smp, K, H, gamma, ret.data_ptr(), steps.data_ptr(), flags.data_ptr(),
+                                        obs.data_ptr() if return_obs else None, st)
+        self.sim.plan_update(mp, smp, K, H, ret.data_ptr(), temperature, new.data_ptr(), best.data_ptr(), st)
+        self._keep_plan = m   # alive until the launches have consumed it
+        out = {"action": new[:, 0], "mean": new, "return": ret, "steps": steps, "terminated": (flags & 1).bool(),
+               "truncated": (flags & 2).bool(), "best": best}
+        if return_obs:
+            out["last_obs"] = obs
+        return out
+
+    def plan_candidates(self, mean=None, horizon=None, K=64, sigma=0.5, hold=1, seed=None, iteration=0):
+        """The candidates ``plan()`` with the same arguments scores at this step, written out: ``[num_envs, K, H, act_dim]`` float32
+        (``rsx_plan_candidates``; for tests, debugging and callers who want a sequence's neighbours)."""
+        torch = self._torch
+        m, H = self._plan_mean(mean, horizon)
+        K = int(K)
+        if K < 1:
+            raise ValueError("K must be >= 1")
+        smp = self._plan_sampler(sigma, hold, seed, iteration)
+        out = torch.empty((self.num_envs, K, H, self.sim.act_dim), dtype=torch.float32, device=self.device)
+        self.sim.plan_candidates(None if m is None else m.data_ptr(), smp, K, H, out.data_ptr(), self._stream())
+        self._keep_plan = m
         return out
 
     # ---- per-env physics / domain randomisation (include/rsx.h: rsx_physics_*; docs/PHYSICS.md section 3) ----
