@@ -184,7 +184,7 @@ int rsx_create(rsx_sim** out, int kind, int field_type, int n_blue, int n_yellow
     const size_t B = (size_t)num_envs, S = (size_t)h->P.row_stride;
     const size_t sbytes = state_bytes(h);
     const size_t cbytes = (size_t)h->P.n_robots * h->M.cmd_dim * S * sizeof(float);
-    if (sbytes >= ((size_t)1 << 32)) {   // the kernels address a row of the state with a 32-bit byte offset (rsx_kernels.hpp: at_byte)
+    if (sbytes >= ((size_t)1 << 32)) {   // the kernels address a row of the state with a 32-bit byte offset (rsx_lane_map.hpp: at_byte)
         free_all(h); delete h;
         return fail(RSX_ERR_ARG, "num_envs too large: the state array would reach 4 GB (see rsx.h, limits)");
     }

@@ -10,7 +10,7 @@
 
 using namespace rsx;
 
-// largest batch whose single-step launches carry placement-helper workgroups (rsx_kernels.hpp: placement_helper): where a
+// largest batch whose single-step launches carry placement-helper workgroups (rsx_placement.hpp: placement_helper): where a
 // launch is as long as its slowest wave and half of the SIMDs are idle anyway
 #ifndef RSX_PCACHE_MAX_ENVS
 #define RSX_PCACHE_MAX_ENVS 16384
@@ -81,7 +81,7 @@ int rsx_task_attach(rsx_sim* h, int task, uint64_t seed, uint64_t env_id_base, i
     const size_t n_flags = align_up(3 * B);   // terminated | truncated | the env mask of rsx_task_reset_to (read by the MODE_REFRESH launch only)
     const size_t n_act = align_up(B * h->M.act_dim * sizeof(float));
     // metrics[8] | error word | (256 bytes in) one step-counter slot per workgroup of the largest stepping launch any layout
-    // of this batch could use (rsx_kernels.hpp: step_tick; only the first tick_slots are kept in sync)
+    // of this batch could use (rsx_hot_args.hpp: step_tick; only the first tick_slots are kept in sync)
     const size_t n_met = align_up((size_t)TICK_SLOT_WORD0 * 4 + ((size_t)grid_for(h) + (B + 63) / 64) * sizeof(uint32_t));
     const size_t n_slots = align_up((size_t)MSLOTS * RSX_METRICS * sizeof(unsigned long long));
     // placement cache: static defenders 1v6 (short episodes: several resetting waves per launch) at latency-bound batches
@@ -230,7 +230,7 @@ int rsx_task_reset_to(rsx_sim* h, const double* ball, const double* blue, const 
 // has taken 2^32 - 1 fused steps refuses further ones instead of silently replaying its random streams.
 // Host-keyed handles (the default) check that here and bake the count into the launch — which is why they refuse to be
 // captured: a replayed graph would step with one tick for ever.  Device-keyed handles (rsx_task_enable_capture) pass
-// RSX_TICK_DEV instead: the kernels read, check and advance the counter themselves (rsx_kernels.hpp: step_tick).
+// RSX_TICK_DEV instead: the kernels read, check and advance the counter themselves (rsx_hot_args.hpp: step_tick).
 static int step_prologue(rsx_sim* h, hipStream_t s, uint64_t n, int* flags) {
     *flags = 0;
     if (h->tick_dev) { *flags = RSX_TICK_DEV; return RSX_OK; }

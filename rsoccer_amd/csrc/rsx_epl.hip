@@ -16,7 +16,7 @@ namespace rsx {
 
 // development knob: RSX_EPL_LDS_PAD=<bytes> of dynamic LDS per workgroup limit the waves per CU (occupancy
 // sensitivity measurements); 0 in production
-// tile order of a single-step launch: alternates with the step counter (tile_of_block_zigzag, rsx_kernels.hpp);
+// tile order of a single-step launch: alternates with the step counter (tile_of_block_zigzag, rsx_hot_args.hpp);
 // RSX_EPL_ZIGZAG=0 keeps one direction (development A/B)
 // (device-keyed launches — n_steps carries RSX_TICK_DEV — cannot be told the parity: a negative `per` asks the kernel to alternate)
 static int step_per_xcd(const Params& P, const int grid, const int n_steps) {

@@ -68,7 +68,7 @@ __device__ __forceinline__ void vss_epl_body(RSX_HOT_ARGS, const Params& P_, con
     const int n_steps = MODE == MODE_ROLLOUT ? (hp_n_steps & RSX_N_STEPS_MASK) : 1;
     __shared__ EplShared sh;
     const int lane = threadIdx.x;
-    // step counter of this launch (rsx_kernels.hpp: step_tick).  Device-keyed launches also pick the tile direction here
+    // step counter of this launch (rsx_hot_args.hpp: step_tick).  Device-keyed launches also pick the tile direction here
     // (the host cannot: it does not know the tick's parity), host-keyed ones get it as the sign of hp_per_xcd
     const bool tick_dev = (hp_n_steps & RSX_TICK_DEV) != 0;
     const StepTick tk = step_tick(tick_dev, P, bufs, (uint32_t)n_steps);

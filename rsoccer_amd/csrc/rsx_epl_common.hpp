@@ -2,7 +2,11 @@
 // besides the per-body arithmetic of rsx_body.hpp: how a lane addresses its env's column of the SoA arrays, how the
 // touching pairs of an env are enumerated and walked, where the contact sums live, how an observation row goes out.
 #pragma once
-#include "rsx_kernels.hpp"
+#include "rsx_math.hpp"
+#include "rsx_params.hpp"
+#include "rsx_body.hpp"
+#include "rsx_hot_args.hpp"
+#include "rsx_task.hpp"
 
 namespace rsx {
 

@@ -5,8 +5,8 @@
 // Same path, same buffers, same arithmetic as task_step_kernel<SSL, 8, TASK, N, ...>
 // (reference: ssl/ssl_hw_challenge/{static_defenders,dribbling,contested_possession,pass_endurance}.py
 // around robosim.SSL.step, rsim.py:155,158); the task arithmetic itself (agent commands, observation,
-// reward / termination, placement) is the SAME code: ssl_agent_commands, write_obs_nb, task_reward and
-// place_env of rsx_kernels.hpp.  Other mapping: lane = env, a wave owns 64 envs and walks the bodies of each
+// reward / termination, placement) is the SAME code: ssl_agent_commands, write_obs_nb, task_reward (rsx_task.hpp)
+// and place_env (rsx_placement.hpp).  Other mapping: lane = env, a wave owns 64 envs and walks the bodies of each
 // one after the other.  The 8-lane layout runs its ball lane and its robot lanes one after the other and tests
 // every robot pair from both sides; at scale that kernel is VALU-bound.  Results are bit-identical:
 // every body sums its partners in index order (robot-robot pairs first, then the ball), the ball sums the robots'
@@ -20,6 +20,9 @@
 // (infrared and four wheel speeds are outputs: written every step, read only when the step has no physics).
 #pragma once
 #include "rsx_epl_common.hpp"
+#include "rsx_state_io.hpp"    // wheel_speeds
+#include "rsx_contact.hpp"     // BallOverride
+#include "rsx_placement.hpp"   // place_env
 
 #ifndef RSX_SD_STEP_WAVES
 #define RSX_SD_STEP_WAVES 4   // waves per SIMD the LEAN 1v6 single-step kernel is compiled for (128 VGPRs, no scratch: 262 144 envs 51 -> 47 us)
@@ -65,7 +68,7 @@ void ssl_epl_kernel(RSX_HOT_ARGS, const Params P_, const Buffers bufs_) {
     const int n_steps = MODE == MODE_ROLLOUT ? (hp_n_steps & RSX_N_STEPS_MASK) : 1;
     __shared__ SeplShared<N> sh;
     const int lane = threadIdx.x;
-    const bool tick_dev = (hp_n_steps & RSX_TICK_DEV) != 0;   // step counter of this launch: rsx_kernels.hpp, step_tick
+    const bool tick_dev = (hp_n_steps & RSX_TICK_DEV) != 0;   // step counter of this launch: rsx_hot_args.hpp, step_tick
     const StepTick tk = step_tick(tick_dev, P, bufs, (uint32_t)n_steps);
     if (__builtin_expect(!tk.ok, 0)) return;
     const int tile = tile_of_block_zigzag(zigzag_per(tick_dev, tk.t, hp_per_xcd));
@@ -182,7 +185,7 @@ void ssl_epl_kernel(RSX_HOT_ARGS, const Params P_, const Buffers bufs_) {
 
             if (sub == 0) RSX_STAMP(4);
             // B: contacts.  One bit per touching robot pair (exact integer form of 0 < d2 < thr, see
-            // rsx_kernels.hpp), one bit per robot whose centre is near enough to the ball for a mouth,
+            // rsx_contact.hpp), one bit per robot whose centre is near enough to the ball for a mouth,
             // circle or infrared contact; a second sweep over the corrected snapshot where a pair was deep.
             const bool ball_low = ball.z < K::robot_h;
             constexpr uint32_t T_RR = __builtin_bit_cast(uint32_t, K::rs_rr2) - 1u;

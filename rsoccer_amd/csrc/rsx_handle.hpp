@@ -33,7 +33,7 @@ struct rsx_sim {
     uint8_t* d_flags = nullptr;
     unsigned long long* d_metrics = nullptr;
     unsigned long long* d_mslots = nullptr;   // [MSLOTS][RSX_METRICS] partial episode counters (metric_slot)
-    float* d_pcache = nullptr;                // placement cache of the latency-bound batches (rsx_kernels.hpp: placement_helper), or null
+    float* d_pcache = nullptr;                // placement cache of the latency-bound batches (rsx_placement.hpp: placement_helper), or null
     unsigned long long* d_pcstats = nullptr;  // [2] cache hits / inline placements (RSX_PCACHE_STATS=1)
     unsigned long long* d_check = nullptr;   // rsx_check_finite counter
     // host-format path: pinned staging; rsx_step() brings the new state back with its own
@@ -58,7 +58,7 @@ struct rsx_sim {
     size_t arena_task_bytes = 0, pcache_bytes = 0;   // sizes of arena_task and of the placement cache inside it (rsx_task_reseed re-initialises them)
     uint32_t tick = 0;                        // fused steps taken since attach (key of the per-step draws); stale once tick_dev is set
     // rsx_task_enable_capture: the step counter lives in device memory (one slot per workgroup behind the metrics vector,
-    // rsx_kernels.hpp: step_tick) so that captured stepping launches advance it when a graph replays them
+    // rsx_hot_args.hpp: step_tick) so that captured stepping launches advance it when a graph replays them
     bool tick_dev = false;
     int tick_slots = 0;                       // workgroups of the handle's per-step launches: the slots every stepping call keeps in sync
     float* d_phys = nullptr;                  // rsx_physics_enable: the per-env physics block (rsx_phys.hpp: PhysHeader, rows), or null

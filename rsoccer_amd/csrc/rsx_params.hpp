@@ -366,9 +366,9 @@ struct Buffers {
 #endif
 };
 
-// partial episode counters: lines of the metrics fold (rsx_kernels.hpp: metric_slot)
+// partial episode counters: lines of the metrics fold (rsx_hot_args.hpp: metric_slot)
 constexpr int MSLOTS = 256;
-// the step counter of a device-keyed handle (rsx_kernels.hpp: step_tick)
+// the step counter of a device-keyed handle (rsx_hot_args.hpp: step_tick)
 constexpr int RSX_TICK_DEV = 1 << 30;        // flag bit of the n_steps kernel argument
 constexpr int RSX_N_STEPS_MASK = RSX_TICK_DEV - 1;
 constexpr int TICK_ERR_WORD = 18;            // uint32 index behind metrics[0]: bytes 72..75
@@ -377,7 +377,7 @@ constexpr int TICK_SLOT_WORD0 = 64;          // uint32 index of slot 0: 256 byte
 constexpr int MODE_STEP = 0, MODE_RESET = 1, MODE_REFRESH = 2, MODE_ROLLOUT = 3;
 
 // ---- grids -------------------------------------------------------------------------------------------------------------
-// workgroups of a launch over `tiles` 64-lane tiles: a multiple of 8, an equal share for each XCD (rsx_kernels.hpp: tile_of_block)
+// workgroups of a launch over `tiles` 64-lane tiles: a multiple of 8, an equal share for each XCD (rsx_hot_args.hpp: tile_of_block)
 inline int tile_grid(const int tiles) { return ((tiles + 7) / 8) * 8; }
 inline int lane_grid(const int L, const int num_envs) { const int G = 64 / L; return tile_grid((num_envs + G - 1) / G); }
 inline int env_grid(const int num_envs) { return tile_grid((num_envs + 63) / 64); }   // one lane per env: 64 envs per tile

@@ -7,7 +7,8 @@
 // its own outputs: the handle is left exactly as it was.
 //
 // The body is the `mode == 0` branch of rsx_task_step_body.inc built from the same device functions (load_raw, interpret_body,
-// draw_for_step, vss_wheel, ssl_agent_commands, robot_targets, physics, wheel_speeds, write_obs, task_reward), the way
+// draw_for_step, physics, write_obs, task_reward) and the same three text fragments (rsx_step_commands.inc: actions -> commands,
+// rsx_step_wire.inc, rsx_step_xr.inc: what the reward lane needs from the robots), the way
 // trace_eval_phys_kernel (rsx_sysid.hip) was built from the raw step: between two steps the lane's record goes through the same
 // wire-format round trip (heading in degrees, rate through deg/s, sin / cos re-derived from the stored heading, ball height through
 // r_ball + z) that a store and a reload apply, so a pair's rewards, flags and observations are bit for bit those of `horizon`

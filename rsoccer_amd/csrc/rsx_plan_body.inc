@@ -1,5 +1,6 @@
 // rsx_plan_body.inc — the per-pair loop of the lookahead kernels (rsx_plan.hip: task_lookahead_kernel, rsx_plan_sampled.hip:
-// task_lookahead_sampled_kernel), included as the kernel's body the way rsx_task_step_body.inc is.  The including kernel names
+// task_lookahead_sampled_kernel), included as the kernel's body the way rsx_task_step_body.inc is; the pieces of a step that
+// both state (rsx_step_commands.inc, rsx_step_wire.inc, rsx_step_xr.inc) are included by both.  The including kernel names
 // KIND, TASK, L, NR and PHYS as template parameters and returns, steps_out, flags_out, last_obs, per_xcd, P, A (PlanArgs) and phys as
 // arguments.  Where a step's action comes from is the includer's: two macros, expanded inside the body's scope (e, b, k, pair, N,
 // AD, step_floats, tick0, A are visible):
@@ -23,11 +24,7 @@
     const int N = NR ? NR : P.n_robots;
     const bool live = e < P.num_envs;
     const uint32_t env_id = P.env_id_base + (uint32_t)e;
-    constexpr int OD_C = NR == 0 ? 0
-        : TASK == RSX_TASK_VSS_V0 ? 4 + 6 * NR
-        : TASK == RSX_TASK_SSL_STATIC_DEFENDERS ? 4 + 8 + 2 * (NR - 1)
-        : TASK == RSX_TASK_SSL_SCRIMMAGE ? 2 + 2 * NR
-        : TASK == RSX_TASK_SSL_DRIBBLING ? 21 : TASK == RSX_TASK_SSL_CONTESTED ? 14 : 16;
+    constexpr int OD_C = obs_dim_c<TASK, NR>();
     const int OD = OD_C ? OD_C : P.obs_dim;
 #define auxe(ROW) at_byte(A.aux, (ix_t)(ROW) * ((ix_t)4 * (ix_t)P.row_stride) + (ix_t)4 * (ix_t)e)   // row ROW of this env in the scalar arena
     const size_t pair = (size_t)e * (size_t)A.n_cand + (size_t)k;   // row of this pair in every output
@@ -65,6 +62,7 @@
     // N * act_dim floats there)
     const bool commands = TASK == RSX_TASK_SSL_SCRIMMAGE ? is_robot : (is_robot && b == 0);
     const size_t step_floats = TASK == RSX_TASK_SSL_SCRIMMAGE ? (size_t)N * AD : (size_t)AD;
+    constexpr bool fed = true;   // every step's action is a candidate's: the shared fragments and draw_for_step never draw the agent's
     RSX_PLAN_ACT_SETUP
     float act[AD];
 #pragma unroll
@@ -107,60 +105,15 @@
 
         // ---- actions -> commands ----
         float q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        const StepDraw dr = draw_for_step<KIND, TASK>(P, env_id, t, b, is_robot, true);
-        if (TASK == RSX_TASK_VSS_V0) {
-            if (is_robot) {
-                float a0, a1;
-                if (b == 0) { a0 = act[0]; a1 = act[1]; }
-                else {
-                    ou0 = (ou0 + P.ou_theta_dt * (0.0f - ou0)) + P.ou_sig_sqdt * dr.v[0];
-                    ou1 = (ou1 + P.ou_theta_dt * (0.0f - ou1)) + P.ou_sig_sqdt * dr.v[1];
-                    a0 = ou0; a1 = ou1;
-                }
-                q[0] = vss_wheel(a0); q[1] = vss_wheel(a1);
-            }
-        } else if (TASK == RSX_TASK_SSL_SCRIMMAGE) {
-            if (is_robot) {
-                q[1] = act[0] * T::max_v; q[2] = act[1] * T::max_v; q[3] = act[2] * 10.0f;
-                q[5] = act[3] > 0.9f ? 5.0f : 0.0f;
-            }
-        } else {
-            if (is_robot && b == 0) {
-                float a[5] = {0, 0, 0, 0, 0};
-#pragma unroll
-                for (int i = 0; i < AD; ++i) a[i] = act[i];
-                ssl_agent_commands<TASK>(a, o.s, o.c, q);
-            }
-            if (TASK == RSX_TASK_SSL_PASS_ENDURANCE && is_robot && b == 1) q[7] = 1.0f;
-        }
-        if (is_robot) robot_targets<KIND>(P, o, q);
+        const StepDraw dr = draw_for_step<KIND, TASK>(P, env_id, t, b, is_robot, fed);
+#include "rsx_step_commands.inc"
 
         // ---- physics ----
         physics<KIND, L, NR>(P, o, b, g, alive, sh, cf);
 
         // ---- wire-format values, reward ----
-        if (is_robot) {
-            od = o.th; wd = o.om * K::rad2deg;
-            if (KIND == RSX_KIND_SSL) wheel_speeds<KIND>(P, o, wheels);
-            o.om = wd * K::deg2rad;
-            sincos_f32(o.th * K::deg2rad, o.s, o.c);
-        } else if (is_ball) {
-            o.z = (K::r_ball + o.z) - K::r_ball;
-        }
-        if (is_robot && b == 0) {
-            float* xr = sh.x0[g];
-            xr[0] = o.x; xr[1] = o.y;
-            if (TASK == RSX_TASK_VSS_V0) { xr[2] = o.vx; xr[3] = o.vy; xr[4] = q[0]; xr[5] = q[1]; }
-            else if (TASK == RSX_TASK_SSL_STATIC_DEFENDERS || TASK == RSX_TASK_SSL_CONTESTED) {
-                xr[6] = lastx; xr[7] = lasty;
-                xr[8] = wheels[0]; xr[9] = wheels[1]; xr[10] = wheels[2]; xr[11] = wheels[3];
-            }
-        } else if (is_robot) {
-            float* xr = sh.x0[g];
-            if (TASK == RSX_TASK_SSL_DRIBBLING) xr[1 + b] = (fabsf(o.vx) > 0.05f || fabsf(o.vy) > 0.05f) ? 1.0f : 0.0f;
-            if (TASK == RSX_TASK_SSL_CONTESTED && b == 1) xr[2] = (fabsf(o.vx) > 0.1f || fabsf(o.vy) > 0.1f) ? 1.0f : 0.0f;
-            if (TASK == RSX_TASK_SSL_PASS_ENDURANCE && b == 1) { xr[2] = o.x; xr[3] = o.y; xr[4] = o.ir ? 1.0f : 0.0f; }
-        }
+#include "rsx_step_wire.inc"
+#include "rsx_step_xr.inc"
         wave_sync();
         float reward = 0.0f; int term = 0;
         if (is_ball) {

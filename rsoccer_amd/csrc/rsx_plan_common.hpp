@@ -31,7 +31,7 @@ struct PlanSampler {
     int hold, nblk;
 };
 
-// two standard normals from two Philox words: the Box-Muller of draw_for_step's OU branch (rsx_kernels.hpp), same expressions
+// two standard normals from two Philox words: the Box-Muller of draw_for_step's OU branch (rsx_task.hpp), same expressions
 __device__ __forceinline__ void plan_normal_pair(const uint32_t w0, const uint32_t w1, float& n0, float& n1) {
     float u1 = (float)((w0 >> 8) + 1u) * 5.9604644775390625e-08f;
     float ang = (u01(w1) - 0.5f) * 6.283185307179586f;

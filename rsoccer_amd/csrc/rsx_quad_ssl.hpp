@@ -15,7 +15,13 @@
 // partners in index order (robots, then the ball), the ball sums the robots' records in robot order, draws use the same
 // Philox counters (tests/test_gpu_parity.py::test_quad_layout_is_bit_identical).
 #pragma once
-#include "rsx_kernels.hpp"
+#include "rsx_math.hpp"
+#include "rsx_params.hpp"
+#include "rsx_body.hpp"
+#include "rsx_hot_args.hpp"
+#include "rsx_state_io.hpp"   // wheel_speeds
+#include "rsx_contact.hpp"    // BallOverride
+#include "rsx_task.hpp"
 
 #ifndef RSX_QUAD_WAVES
 #define RSX_QUAD_WAVES 3   // waves per SIMD the kernel is compiled for
@@ -80,7 +86,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RSX_QUAD_WAV
     const int q = lane >> 2;           // env of the wave
     const int p = lane & 3;            // which quarter of the robots
     const bool bl = p == 3;            // the ball's lane (reward, termination, episode bookkeeping of the env)
-    const bool tick_dev = (hp_n_steps & RSX_TICK_DEV) != 0;   // step counter of this launch: rsx_kernels.hpp, step_tick
+    const bool tick_dev = (hp_n_steps & RSX_TICK_DEV) != 0;   // step counter of this launch: rsx_hot_args.hpp, step_tick
     const StepTick tk = step_tick(tick_dev, P, bufs, 1u);
     if (__builtin_expect(!tk.ok, 0)) return;
     const int tile = tile_of_block_zigzag(zigzag_per(tick_dev, tk.t, hp_per_xcd));
@@ -349,7 +355,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RSX_QUAD_WAV
                         const float wj = sh.W[j][q];
                         const float dx = oj.x - r[i].x, dy = oj.y - r[i].y;
                         const float d2 = fma_(dx, dx, dy * dy);
-                        if (d2 > 0.0f) {   // (0: two robots in one place are not a contact, rsx_kernels.hpp)
+                        if (d2 > 0.0f) {   // (0: two robots in one place are not a contact, rsx_contact.hpp)
                             hit = true;
                             contact_response<KIND>(P, r[i], oj, d2, K::rs_rr, K::ope_rr, K::w_rr, K::kt_rr, K::mu_rr, 0.0f,
                                                    fma_(wj, K::r_robot, r[i].om * K::r_robot), K::beta, K::pen2, true, v2w, avx, avy, apx, apy, unused, deep, wallp);
@@ -478,9 +484,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RSX_QUAD_WAV
         }
     }
 
-    {   // what the rest of the step reads of the parameter block: fetched from the kernarg segment here instead of parked in VGPR lanes across the physics (like the SSL lane-group kernels, rsx_kernels.hpp)
+    {   // what the rest of the step reads of the parameter block: fetched from the kernarg segment here instead of parked in VGPR lanes across the physics (like the SSL lane-group kernels, rsx_task_step_body.inc)
         typedef const __attribute__((address_space(4))) uint32_t* kw_t;
-        constexpr size_t KOFF = RSX_PARAMS_KERNARG_OFFSET;   // rsx_kernels.hpp, tied to RSX_HOT_ARGS by a static_assert
+        constexpr size_t KOFF = RSX_PARAMS_KERNARG_OFFSET;   // rsx_hot_args.hpp, tied to RSX_HOT_ARGS by a static_assert
         kw_t pk = (kw_t)__builtin_amdgcn_kernarg_segment_ptr() + KOFF / 4;
         asm volatile("" : "+s"(pk));
         struct Words { uint32_t w[sizeof(Params) / 4]; } raww;

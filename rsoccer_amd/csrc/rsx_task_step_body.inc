@@ -1,7 +1,8 @@
 // rsx_task_step_body.inc — the body of task_step_kernel and task_step_phys_kernel (rsx_kernels.hpp), included into both.
 // Textual inclusion, not a shared device function: the literal kernels then compile to (nearly) the instructions they had
 // before the per-env variant existed (an inlined body function moved registers and instructions around: -2 % on the VSS-v0
-// headline).  Expects PHYS (constexpr bool) and `phys` (the physics block, or nullptr) in scope.
+// headline).  Expects PHYS (constexpr bool) and `phys` (the physics block, or nullptr) in scope.  What a step shares with the lookahead
+// (rsx_plan_body.inc) is text of its own, for the same reason: rsx_step_commands.inc, rsx_step_wire.inc, rsx_step_xr.inc.
     // A multi-step launch is short of SGPRs, not of start-up latency: there the preloaded copies
     // are left dead and everything is fetched from the kernarg segment when it is needed.
     constexpr bool HOT = MODE != MODE_ROLLOUT;
@@ -49,19 +50,10 @@
     const size_t B = (size_t)P.num_envs;
     const uint32_t env_id = P.env_id_base + (uint32_t)e;
     // observation width: a compile-time constant when the team sizes are (lets the copy-out unroll)
-    constexpr int OD_C = NR == 0 ? 0
-        : TASK == RSX_TASK_VSS_V0 ? 4 + 6 * NR                // equal teams: 4 + 7*nb + 5*ny (vss_gym.py:64-67): 40 for 3v3, 64 for 5v5
-        : TASK == RSX_TASK_SSL_STATIC_DEFENDERS ? 4 + 8 + 2 * (NR - 1)
-        : TASK == RSX_TASK_SSL_SCRIMMAGE ? 2 + 2 * NR
-        : TASK == RSX_TASK_SSL_DRIBBLING ? 21 : TASK == RSX_TASK_SSL_CONTESTED ? 14 : 16;
+    constexpr int OD_C = obs_dim_c<TASK, NR>();
     const int OD = OD_C ? OD_C : P.obs_dim;
 #define auxe(ROW) at_byte(bufs.aux, (ix_t)(ROW) * ((ix_t)4 * (ix_t)P.row_stride) + (ix_t)4 * (ix_t)e)   // row ROW of this env in the scalar arena
 
-#ifdef RSX_TIMING
-#define RSX_STAMP(i) do { if (lane == 0) bufs.dbg[(size_t)(i) * gridDim.x + blockIdx.x] = __builtin_readcyclecounter(); } while (0)
-#else
-#define RSX_STAMP(i) do {} while (0)
-#endif
 #ifdef RSX_TIMING
     if (lane == 0) { sh.dbg = bufs.dbg; bufs.dbg[(size_t)13 * gridDim.x + blockIdx.x] = __builtin_amdgcn_s_memrealtime(); }  // 100 MHz, chip-wide
 #endif
@@ -200,37 +192,7 @@
             // ---- actions -> commands ----
             float q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
             const StepDraw dr = MODE == MODE_STEP ? pre : draw_for_step<KIND, TASK>(P, env_id, t, b, is_robot, fed);
-            if (TASK == RSX_TASK_VSS_V0) {
-                if (is_robot) {
-                    float a0, a1;
-                    if (b == 0) {   // the agent: fed action or the step's uniform draw
-                        if (fed) { a0 = act[0]; a1 = act[1]; }
-                        else { a0 = dr.v[0]; a1 = dr.v[1]; }
-                    } else {  // Ornstein-Uhlenbeck noise, Utils/Utils.py:14-21, on the step's two normals
-                        ou0 = (ou0 + P.ou_theta_dt * (0.0f - ou0)) + P.ou_sig_sqdt * dr.v[0];
-                        ou1 = (ou1 + P.ou_theta_dt * (0.0f - ou1)) + P.ou_sig_sqdt * dr.v[1];
-                        a0 = ou0; a1 = ou1;
-                    }
-                    q[0] = vss_wheel(a0); q[1] = vss_wheel(a1);
-                }
-            } else if (TASK == RSX_TASK_SSL_SCRIMMAGE) {  // every robot: (v_x, v_y, v_theta, kick), block b of the step
-                if (is_robot) {
-                    float a[4];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) a[i] = fed ? act[i] : dr.v[i];
-                    q[1] = a[0] * T::max_v; q[2] = a[1] * T::max_v; q[3] = a[2] * 10.0f;
-                    q[5] = a[3] > 0.9f ? 5.0f : 0.0f;
-                }
-            } else {  // the SSL tasks: only blue 0 is driven by the agent
-                if (is_robot && b == 0) {
-                    float a[5] = {0, 0, 0, 0, 0};
-#pragma unroll
-                    for (int i = 0; i < AD; ++i) a[i] = fed ? act[i] : dr.v[i];
-                    ssl_agent_commands<TASK>(a, o.s, o.c, q);
-                }
-                if (TASK == RSX_TASK_SSL_PASS_ENDURANCE && is_robot && b == 1) q[7] = 1.0f;  // receiver: dribbler on
-            }
-            if (is_robot) robot_targets<KIND>(P, o, q);
+#include "rsx_step_commands.inc"
 
             // ---- physics ----
             RSX_STAMP(2);
@@ -253,34 +215,9 @@
             }
 
             // ---- wire-format values, observation, reward ----
-            if (is_robot) {
-                od = o.th; wd = o.om * K::rad2deg;
-                if (KIND == RSX_KIND_SSL) wheel_speeds<KIND>(P, o, wheels);
-                // omega lives in HBM as deg/s: keep the lane's copy equal to what a reload gives.
-                o.om = wd * K::deg2rad;
-                // the sub-steps carried (c, s) by small rotations; re-derive them exactly from the
-                // stored heading: this is what the observation reports and what a reload (the next
-                // launch, or the next step of a multi-step launch) starts from
-                sincos_f32(o.th * K::deg2rad, o.s, o.c);
-            } else if (is_ball) {
-                o.z = (K::r_ball + o.z) - K::r_ball;  // height goes through the wire format too
-            }
+#include "rsx_step_wire.inc"
             write_obs<KIND, TASK>(P, bufs.obs + (size_t)e * OD, b, is_robot, is_ball, o.x, o.y, o.vx, o.vy, o.s, o.c, wd, o.ir, obs_ts);
-            // what the reward lane (the ball's) needs from the robots' lanes
-            if (is_robot && b == 0) {
-                float* xr = sh.x0[g];
-                xr[0] = o.x; xr[1] = o.y;
-                if (TASK == RSX_TASK_VSS_V0) { xr[2] = o.vx; xr[3] = o.vy; xr[4] = q[0]; xr[5] = q[1]; }
-                else if (TASK == RSX_TASK_SSL_STATIC_DEFENDERS || TASK == RSX_TASK_SSL_CONTESTED) {
-                    xr[6] = lastx; xr[7] = lasty;
-                    xr[8] = wheels[0]; xr[9] = wheels[1]; xr[10] = wheels[2]; xr[11] = wheels[3];
-                }
-            } else if (is_robot) {
-                float* xr = sh.x0[g];
-                if (TASK == RSX_TASK_SSL_DRIBBLING) xr[1 + b] = (fabsf(o.vx) > 0.05f || fabsf(o.vy) > 0.05f) ? 1.0f : 0.0f;
-                if (TASK == RSX_TASK_SSL_CONTESTED && b == 1) xr[2] = (fabsf(o.vx) > 0.1f || fabsf(o.vy) > 0.1f) ? 1.0f : 0.0f;
-                if (TASK == RSX_TASK_SSL_PASS_ENDURANCE && b == 1) { xr[2] = o.x; xr[3] = o.y; xr[4] = o.ir ? 1.0f : 0.0f; }
-            }
+#include "rsx_step_xr.inc"   // what the reward lane (the ball's) needs from the robots' lanes -> sh.x0[g]
             wave_sync();
             if (is_ball) {
                 const float* xr = sh.x0[g];

@@ -30,7 +30,7 @@ inline unsigned long long* g_dbg = nullptr;   // development builds: where the k
 #endif
 // rsx_epl.hip: the one-lane-per-env kernels (large batches) and the four-lanes-per-env kernel of the SSL 11v11 scrimmage task
 // (single-step launches, n_steps = 1 | flags); *_grid: workgroups of those launches (the host sizes the per-workgroup tick slots
-// from these: rsx_kernels.hpp, step_tick)
+// from these: rsx_hot_args.hpp, step_tick)
 void launch_vss_epl(bool rollout, const Params& P, const Buffers& b, int n_steps, hipStream_t s);
 void launch_ssl_epl(int task, bool rollout, const Params& P, const Buffers& b, int n_steps, hipStream_t s);
 void launch_ssl_quad(const Params& P, const Buffers& b, int n_steps, hipStream_t s);

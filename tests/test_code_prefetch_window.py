@@ -1,5 +1,5 @@
 """The VSS single-step kernels touch the 8 KB of their own code behind an `s_getpc_b64` with one data load (64 lanes x 128 bytes: every
-launch starts with a cold instruction cache, rsx_kernels.hpp: CODE_PF).  A data load from the text segment must stay inside mapped
+launch starts with a cold instruction cache, rsx_task_step_body.inc: CODE_PF).  A data load from the text segment must stay inside mapped
 memory: this test takes the device code objects out of librsx_hip.so and checks, for every kernel that carries the load, that the
 window [pc, pc + 8 KB) ends inside the code object's .text section — wherever the linker happened to put the kernel."""
 import os

@@ -971,7 +971,7 @@ def test_api_errors_are_reported_not_crashed():
 @pytest.mark.parametrize("task,kind,ft,nb,ny,max_steps", [(2, 1, 2, 1, 6, 9), (2, 1, 2, 1, 6, 6), (2, 1, 2, 1, 6, 1)])
 def test_placement_cache_serves_resets_bit_identically(oracle_mod, monkeypatch, task, kind, ft, nb, ny, max_steps):
     """Latency-bound batches: helper workgroups of every step launch compute each env's next placement ahead of time
-    (rsx_kernels.hpp: placement_helper) and the resetting wave copies it.  Same poses as the inline placement — the run
+    (rsx_placement.hpp: placement_helper) and the resetting wave copies it.  Same poses as the inline placement — the run
     equals the oracle's bit for bit — and the cache really is what served them (counters); an episode length of one
     step (a reset in every launch: the entry is never ready in time) falls back to the inline path, also bit-exact."""
     import torch

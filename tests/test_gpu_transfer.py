@@ -372,7 +372,7 @@ def test_captured_transfer_and_step_replays_like_the_eager_calls():
 # ---- 7. composition with lookahead ----
 def test_broadcast_then_lookahead_returns_the_source_row_for_every_env():
     """SSLStaticDefenders: with fed actions nothing in an episode depends on the env id — the defenders stand still (no OU noise),
-    the only per-step draw (rsx_kernels.hpp: draw_for_step) is the random action that a candidate's action replaces, and a pair stops
+    the only per-step draw (rsx_task.hpp: draw_for_step) is the random action that a candidate's action replaces, and a pair stops
     at its episode end, before any placement — so every env that holds env j's episode scores the candidates as env j did."""
     import torch
     from rsoccer_amd import vec

@@ -49,7 +49,7 @@ def _reps(torch, fn, window, least=3):
 def bytes_per_env(env):
     """what one transferred env reads (and writes): state rows, scalar arena, obs and final_obs rows, two flag bytes, physics rows"""
     sim = env.sim
-    rows = (sim.state_dim + 2) + (15 + 2 * sim.n_robots) + (32 if env._physics else 0)   # rsx_kernels.hpp: aux_rows
+    rows = (sim.state_dim + 2) + (15 + 2 * sim.n_robots) + (32 if env._physics else 0)   # rsx_params.hpp: aux_rows
     return 4 * rows + 2 * 4 * sim.obs_dim + 2
 
 
