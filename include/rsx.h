@@ -416,6 +416,54 @@ int rsx_plan_candidates(rsx_sim* h, const float* mean_dev, const rsx_plan_sample
 int rsx_plan_update(rsx_sim* h, const float* mean_dev, const rsx_plan_sampler* s, int n_candidates, int horizon,
                     const float* returns_dev, float temperature, float* new_mean_dev, int32_t* best_dev, void* stream);
 
+/* ---- closed-loop lookahead: MLP policies inside the lookahead launch (additive extension of ABI 6) -----------------------------
+ * rsx_task_lookahead with a policy as the action source: pair (e, k) is env e under policy k, and the action of a simulated step is
+ * the policy's answer to the observation the pair itself just produced:  a_t = pi_k(obs_t);  obs_{t+1}, r_t = step(a_t).  With
+ * horizon = max_episode_steps straight after rsx_task_reset one launch scores whole episodes of K parameter vectors from the same B
+ * start states against the same future draws (evolution strategies, CEM over parameters, paired evaluation of checkpoints).
+ *
+ * The policy is a small MLP, the same for all envs: */
+#define RSX_ACT_RELU 0   /* max(x, 0) */
+#define RSX_ACT_TANH 1   /* one float32 tanh (fixed operation order, |result| <= 1, absolute error about 1e-7) */
+#define RSX_ACT_CLIP 2   /* clamp to [-1, 1] */
+typedef struct rsx_policy_mlp {
+    int32_t n_hidden_layers;  /* 1 or 2 */
+    int32_t hidden;           /* 32 or 64 units per hidden layer */
+    int32_t hidden_act;       /* RSX_ACT_RELU | RSX_ACT_TANH */
+    int32_t out_act;          /* RSX_ACT_CLIP (clamp to [-1, 1]) | RSX_ACT_TANH */
+} rsx_policy_mlp;
+/*   params_dev   [n_policies][P] f32 device memory, dense.  One policy is laid out like torch.nn.Linear.weight and .bias, in this
+ *                order: W1 [hidden][obs_dim] row-major (the weights of unit j contiguous), b1 [hidden]; with two hidden layers W2
+ *                [hidden][hidden], b2 [hidden]; Wo [act_dim][hidden], bo [act_dim].  P is the sum of these sizes
+ *                (rsx_policy_num_params; obs_dim and act_dim as rsx_task_view reports them).  Non-finite parameters are not checked,
+ *                as fed actions are not.
+ *   arithmetic   unit j of a layer: acc = bias[j]; for i = 0 .. n_in - 1 ascending: acc = fmaf(W[j][i], x[i], acc), in float32, then
+ *                the activation.  One lane computes a whole unit and nothing is reduced across lanes, so the bits do not depend on the
+ *                kernel layout or on per-env physics.  No stochastic head: parameter noise is the caller's.
+ *   what it sees at step 0 of a pair the env's row of the handle's obs buffer — what the caller's own policy would have seen after the
+ *                last rsx_task_step / reset / reset_to / transfer (NOT a recomputation from the state: SSLDribbling's observation
+ *                carries a task scalar that lags the state by design); at step t >= 1 the observation simulated step t - 1 produced,
+ *                the floats rsx_task_step would have written to obs.
+ *   returns_dev, steps_dev, flags_dev, last_obs_dev   exactly rsx_task_lookahead's ([num_envs][n_policies] ...), the same float32
+ *                return recurrence; a pair stops at its env's first episode end.
+ *   actions_out_dev  [num_envs][n_policies][horizon][act_dim] f32, or NULL: the action the policy produced at each simulated step.
+ *   obs_out_dev      [num_envs][n_policies][horizon][obs_dim] f32, or NULL: the observation that action was computed from.
+ *                Entries of steps a pair did not simulate are not written.
+ * Exactness: feeding actions_out_dev to rsx_task_lookahead from the same handle state gives the same returns, steps, flags and
+ * last_obs bit for bit — hence also `horizon` rsx_task_step calls with those actions — on every lane width (8, 16, 32), with and without
+ * per-env physics, on host-keyed and device-keyed handles.
+ * No side effects: the call reads the state, the scalar arena, the obs buffer, the step counter and params_dev and writes only its
+ * outputs; the handle is left exactly as it was.  Stream-ordered, never synchronises, capturable under rsx_task_lookahead's conditions
+ * (a launch at the counter limit of a device-keyed handle simulates nothing).
+ * Refusals (nothing is enqueued): all of rsx_task_lookahead's, and RSX_ERR_ARG for a null p or params_dev, n_hidden_layers, hidden or
+ * an activation outside the listed values, a policy whose weights do not fit a workgroup's 64 KB of LDS (2 x 64 units fit every
+ * observation of at most 100 floats), and the scrimmage task: it commands every robot (act_dim = 4 N), which one agent's policy per env
+ * does not drive — a different feature. */
+int rsx_policy_num_params(const rsx_sim* h, const rsx_policy_mlp* p, int64_t* out);
+int rsx_task_lookahead_policy(rsx_sim* h, const rsx_policy_mlp* p, const float* params_dev, int n_policies, int horizon, float gamma,
+                              float* returns_dev, int32_t* steps_dev, uint8_t* flags_dev, float* last_obs_dev,
+                              float* actions_out_dev, float* obs_out_dev, void* stream);
+
 /* Debugging aid: number of non-finite floats in the state rows and, with a task attached, in the
  * observations, rewards and info rows.  Synchronises `stream`.  With RSX_DEBUG_FINITE=1 in the
  * environment every stepping call (rsx_step_dev, rsx_task_step, rsx_task_step_n, rsx_task_rollout)

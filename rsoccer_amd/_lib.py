@@ -51,7 +51,10 @@ SYMBOLS = (
     "rsx_render_view_reference", "rsx_render_size", "rsx_render_field", "rsx_render_open", "rsx_render", "rsx_render_errors",
     "rsx_task_transfer", "rsx_task_transfer_errors",
     "rsx_task_lookahead_sampled", "rsx_plan_candidates", "rsx_plan_update",
+    "rsx_policy_num_params", "rsx_task_lookahead_policy",
 )
+# activations of rsx_policy_mlp (include/rsx.h: RSX_ACT_*)
+ACT_RELU, ACT_TANH, ACT_CLIP = 0, 1, 2
 
 
 class RsxError(RuntimeError):
@@ -61,6 +64,11 @@ class RsxError(RuntimeError):
 class PlanSampler(C.Structure):
     """rsx_plan_sampler (include/rsx.h): the noise of sampled planning candidates"""
     _fields_ = [("sample_seed", C.c_uint64), ("sigma", C.c_float), ("hold", C.c_int32)]
+
+
+class PolicyMLP(C.Structure):
+    """rsx_policy_mlp (include/rsx.h): the shape of the policies of rsx_task_lookahead_policy"""
+    _fields_ = [("n_hidden_layers", C.c_int32), ("hidden", C.c_int32), ("hidden_act", C.c_int32), ("out_act", C.c_int32)]
 
 
 class DevView(C.Structure):
@@ -158,6 +166,8 @@ def load():
     lib.rsx_task_lookahead_sampled.argtypes = [vp, vp, C.POINTER(PlanSampler), ip, ip, C.c_float, vp, vp, vp, vp, vp]
     lib.rsx_plan_candidates.argtypes = [vp, vp, C.POINTER(PlanSampler), ip, ip, vp, vp]
     lib.rsx_plan_update.argtypes = [vp, vp, C.POINTER(PlanSampler), ip, ip, vp, C.c_float, vp, vp, vp]
+    lib.rsx_policy_num_params.argtypes = [vp, C.POINTER(PolicyMLP), C.POINTER(C.c_int64)]
+    lib.rsx_task_lookahead_policy.argtypes = [vp, C.POINTER(PolicyMLP), vp, ip, ip, C.c_float, vp, vp, vp, vp, vp, vp, vp]
     lib.rsx_physics_defaults.argtypes = [ip, vp]
     lib.rsx_physics_derive.argtypes = [ip, ip, vp, vp]
     lib.rsx_physics_enable.argtypes = [vp, vp]
@@ -479,6 +489,23 @@ class Sim:
         ([B][H][act_dim] f32 device address or None = zeros) by ``sampler`` (a PlanSampler, or None to pass NULL)."""
         rc = self._lib.rsx_task_lookahead_sampled(self._h, mean_ptr, None if sampler is None else C.byref(sampler), int(n_candidates),
                                                   int(horizon), float(gamma), returns_ptr, steps_ptr, flags_ptr, last_obs_ptr, stream)
+        if rc:
+            _chk(rc)
+
+    def policy_num_params(self, spec):
+        """rsx_policy_num_params: floats of one policy of shape ``spec`` (a PolicyMLP) on this handle's task"""
+        n = C.c_int64(0)
+        _chk(self._lib.rsx_policy_num_params(self._h, None if spec is None else C.byref(spec), C.byref(n)))
+        return int(n.value)
+
+    def task_lookahead_policy(self, spec, params_ptr, n_policies, horizon, gamma, returns_ptr, steps_ptr, flags_ptr, last_obs_ptr=None,
+                              actions_out_ptr=None, obs_out_ptr=None, stream=None):
+        """rsx_task_lookahead_policy: rsx_task_lookahead with each step's action computed by MLP policy k (``spec``: a PolicyMLP, or
+        None to pass NULL; params [K][P] f32) from the observation the pair just produced.  Optional records: actions_out
+        [B][K][H][act_dim], obs_out [B][K][H][obs_dim] (entries of steps a pair did not simulate are not written)."""
+        rc = self._lib.rsx_task_lookahead_policy(self._h, None if spec is None else C.byref(spec), params_ptr, int(n_policies), int(horizon),
+                                                 float(gamma), returns_ptr, steps_ptr, flags_ptr, last_obs_ptr, actions_out_ptr, obs_out_ptr,
+                                                 stream)
         if rc:
             _chk(rc)
 

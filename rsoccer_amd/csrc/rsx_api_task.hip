@@ -302,6 +302,56 @@ int rsx_task_lookahead(rsx_sim* h, const float* actions_dev, int n_candidates, i
     return RSX_OK;
 }
 
+// ---- the lookahead with an MLP policy as its action source (rsx.h: rsx_policy_mlp) ----
+// what both calls check of a policy; on success S is the spec as the kernels take it and *n_params the floats of one policy
+static int policy_prologue(const rsx_sim* h, const rsx_policy_mlp* p, PolicySpec* S, int64_t* n_params) {
+    if (h->P.task == RSX_TASK_NONE) return fail(RSX_ERR_STATE, "no task attached (rsx_task_attach)");
+    if (!p) return fail(RSX_ERR_ARG, "the policy (rsx_policy_mlp) must not be null");
+    if (h->P.task == RSX_TASK_SSL_SCRIMMAGE || h->P.task == RSX_TASK_SSL_SCRIMMAGE_CROWDED)
+        return fail(RSX_ERR_ARG, "the scrimmage task commands every robot (act_dim = 4 N): one policy per env does not drive it");
+    if (p->n_hidden_layers != 1 && p->n_hidden_layers != 2) return fail(RSX_ERR_ARG, "n_hidden_layers must be 1 or 2");
+    if (p->hidden != 32 && p->hidden != 64) return fail(RSX_ERR_ARG, "hidden must be 32 or 64");
+    if (p->hidden_act != RSX_ACT_RELU && p->hidden_act != RSX_ACT_TANH) return fail(RSX_ERR_ARG, "hidden_act must be RSX_ACT_RELU or RSX_ACT_TANH");
+    if (p->out_act != RSX_ACT_CLIP && p->out_act != RSX_ACT_TANH) return fail(RSX_ERR_ARG, "out_act must be RSX_ACT_CLIP or RSX_ACT_TANH");
+    *S = PolicySpec{p->n_hidden_layers, p->hidden, p->hidden_act, p->out_act};
+    const int64_t H = p->hidden;
+    *n_params = H * h->P.obs_dim + H + (p->n_hidden_layers == 2 ? H * H + H : 0) + (int64_t)h->M.act_dim * H + h->M.act_dim;
+    return RSX_OK;
+}
+
+int rsx_policy_num_params(const rsx_sim* h, const rsx_policy_mlp* p, int64_t* out) {
+    if (!h) return fail(RSX_ERR_ARG, "null handle");
+    if (!out) return fail(RSX_ERR_ARG, "out must not be null");
+    PolicySpec S;
+    return policy_prologue(h, p, &S, out);
+}
+
+int rsx_task_lookahead_policy(rsx_sim* h, const rsx_policy_mlp* p, const float* params_dev, int n_policies, int horizon, float gamma,
+                              float* returns_dev, int32_t* steps_dev, uint8_t* flags_dev, float* last_obs_dev, float* actions_out_dev,
+                              float* obs_out_dev, void* stream) {
+    RSX_ENTER(h);   // (as rsx_task_lookahead: nothing the handle owns changes)
+    PolicySpec S; int64_t n_params = 0;
+    if (int rc = policy_prologue(h, p, &S, &n_params)) return rc;
+    RSX_NEED_RESET(h);
+    if (n_policies < 1 || horizon < 1) return fail(RSX_ERR_ARG, "n_policies and horizon must be >= 1");
+    if (!params_dev || !returns_dev || !steps_dev || !flags_dev) return fail(RSX_ERR_ARG, "params_dev, returns_dev, steps_dev and flags_dev must not be null");
+    if (!std::isfinite(gamma)) return fail(RSX_ERR_ARG, "gamma must be finite");
+    if (h->L > 32) return fail(RSX_ERR_ARG, "rsx_task_lookahead_policy has no 64-lanes-per-env kernels (unset RSX_LANES_PER_ENV)");
+    if (lookahead_grid(h->L, h->P.num_envs, n_policies) > 0x7FFFFFFFll)
+        return fail(RSX_ERR_ARG, "num_envs x n_policies exceeds the launch limit (2^31 - 1 workgroups): split the policies over several calls");
+    if (policy_lds_bytes(h->L, h->P.obs_dim, h->M.act_dim, S) > 65536ll)
+        return fail(RSX_ERR_ARG, "the policy's weights do not fit a workgroup's 64 KB of LDS at this observation width: use fewer or smaller hidden layers");
+    int fl = 0;
+    if (int rc = step_prologue(h, (hipStream_t)stream, (uint64_t)horizon, &fl)) return rc;   // capture of a host-keyed handle, counter limit
+    Params P = h->P;
+    P.tick_base = h->tick;   // the tick the next step would take; not advanced
+    launch_task_lookahead_policy(P, h->L, h->NR, h->d_state, h->d_aux, h->d_obs, h->tick_dev ? tick_slot0(h) : nullptr, h->d_phys, S, params_dev,
+                                 (int)n_params, h->M.act_dim, n_policies, horizon, gamma, returns_dev, steps_dev, flags_dev, last_obs_dev,
+                                 actions_out_dev, obs_out_dev, (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
 // ---- planning with candidates drawn on the device (rsx.h: rsx_plan_sampler) ----
 // what the three calls check alike; on success S is the sampler as the kernels take it and P the handle's parameters with the step
 // counter the next step would take (not advanced).  n_steps: what the counter limit is checked against (0: the call simulates nothing)

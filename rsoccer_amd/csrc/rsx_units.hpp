@@ -66,6 +66,15 @@ void launch_plan_candidates(const Params& P, const uint32_t* ticks, const float*
                             int act_dim, float* out, hipStream_t s);
 void launch_plan_update(const Params& P, const uint32_t* ticks, const float* mean, const PlanSampler& S, int n_candidates, int horizon,
                         int act_dim, const float* returns, float temperature, float* new_mean, int32_t* best, hipStream_t s);
+// rsx_policy.hip: the lookahead with each step's action computed by an MLP policy from the observation the pair just produced
+// (rsx_task_lookahead_policy).  PolicySpec: rsx_policy_mlp, checked; params: [n_policies][n_params]; obs: the handle's obs buffer, read
+// only; actions_out / obs_out: optional.  policy_lds_bytes: LDS of one workgroup of that launch (the host refuses more than 64 KB)
+struct PolicySpec { int layers, hidden, hidden_act, out_act; };
+long long policy_lds_bytes(int L, int obs_dim, int act_dim, const PolicySpec& p);
+void launch_task_lookahead_policy(const Params& P, int L, int NR, const float* state, const float* aux, const float* obs, const uint32_t* ticks,
+                                  const float* phys, const PolicySpec& p, const float* params, int n_params, int act_dim, int n_policies,
+                                  int horizon, float gamma, float* returns, int32_t* steps, uint8_t* flags, float* last_obs,
+                                  float* actions_out, float* obs_out, hipStream_t s);
 // rsx_render.hip: batched rgb frames (rsx_render_*).  render_check_view: nullptr when the view is valid (and the frame size), else the
 // message; render_field_host: the static field image [H][W][3]; RenderGeom: what the kernel needs of a view, in float32
 struct RenderGeom { int W, H; float s, cx, cy, r, rb; int square; };

@@ -202,6 +202,61 @@ class VecFusedEnv(RenderMixin):
             out["last_obs"] = obs
         return out
 
+    def lookahead_policy(self, policy, params, horizon, gamma=1.0, return_obs=False, return_actions=False, return_policy_obs=False):
+        """``lookahead()`` closed-loop: ``K`` MLP policies instead of ``K`` action sequences (``rsx_task_lookahead_policy``).
+
+        ``policy``: an ``rsoccer_amd.vec.policy.MLPPolicy`` for this env's ``obs_dim`` / ``act_dim``; ``params``: ``[K, P]`` float32,
+        one flat parameter vector per policy (``MLPPolicy.pack`` / ``from_module``), shared by all envs.  Pair (env, k) starts from where
+        the env stands now; the action of each simulated step is policy ``k``'s answer to the observation the pair just produced — at
+        step 0 the env's current ``obs`` row — evaluated inside the launch.  Everything else is ``lookahead()``'s: the env's real
+        future draws, a pair stops at its env's first episode end, the env is left exactly as it was.  ``horizon=max_episode_steps``
+        straight after ``reset()`` scores whole episodes.
+
+        Returns the dict of ``lookahead()`` (``return``, ``steps``, ``terminated``, ``truncated``, ``last_obs`` with
+        ``return_obs=True``) plus, on request, ``actions`` ``[num_envs, K, H, act_dim]`` — the action taken at every simulated step —
+        and ``policy_obs`` ``[num_envs, K, H, obs_dim]`` — the observation it was computed from; entries behind a pair's end stay zero.
+        ``lookahead(out["actions"])`` from the same state returns the same bits.  Capturable after ``enable_graph_capture()``."""
+        torch = self._torch
+        from rsoccer_amd.vec.policy import MLPPolicy
+        if not isinstance(policy, MLPPolicy):
+            raise ValueError("policy must be an rsoccer_amd.vec.policy.MLPPolicy")
+        H, gamma = int(horizon), float(gamma)
+        if H < 1:
+            raise ValueError(f"horizon must be >= 1, got {horizon}")
+        if not np.isfinite(gamma):
+            raise ValueError("gamma must be finite")
+        if self.sim.act_dim != policy.act_dim or self.sim.obs_dim != policy.obs_dim:
+            raise ValueError(f"the policy maps {policy.obs_dim} -> {policy.act_dim}, the env {self.sim.obs_dim} -> {self.sim.act_dim}")
+        shape = tuple(np.shape(params))   # checked on the INPUT, as lookahead() checks its actions
+        if len(shape) != 2 or shape[0] < 1 or shape[1] != policy.num_params:
+            raise ValueError(f"params must be [K >= 1, {policy.num_params}], got {shape}")
+        K = int(shape[0])
+        if isinstance(params, torch.Tensor):
+            p = params
+            if p.device != self.device or p.dtype != torch.float32 or not p.is_contiguous():
+                p = p.to(device=self.device, dtype=torch.float32).contiguous()
+        else:
+            p = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float32)).to(self.device)
+        B, dev = self.num_envs, self.device
+        ret = torch.empty((B, K), dtype=torch.float32, device=dev)
+        steps = torch.empty((B, K), dtype=torch.int32, device=dev)
+        flags = torch.empty((B, K), dtype=torch.uint8, device=dev)
+        obs = torch.empty((B, K, self.sim.obs_dim), dtype=torch.float32, device=dev) if return_obs else None
+        acts = torch.zeros((B, K, H, self.sim.act_dim), dtype=torch.float32, device=dev) if return_actions else None
+        pobs = torch.zeros((B, K, H, self.sim.obs_dim), dtype=torch.float32, device=dev) if return_policy_obs else None
+        self.sim.task_lookahead_policy(policy.spec(), p.data_ptr(), K, H, gamma, ret.data_ptr(), steps.data_ptr(), flags.data_ptr(),
+                                       obs.data_ptr() if return_obs else None, acts.data_ptr() if return_actions else None,
+                                       pobs.data_ptr() if return_policy_obs else None, self._stream())
+        self._keep_plan = p   # alive until the launch has consumed it
+        out = {"return": ret, "steps": steps, "terminated": (flags & 1).bool(), "truncated": (flags & 2).bool()}
+        if return_obs:
+            out["last_obs"] = obs
+        if return_actions:
+            out["actions"] = acts
+        if return_policy_obs:
+            out["policy_obs"] = pobs
+        return out
+
     # ---- planning with candidates drawn on the device (include/rsx.h: rsx_plan_sampler) ----
     def _plan_sampler(self, sigma, hold, seed, iteration):
         """the rsx_plan_sampler of a call: ``sample_seed`` is a 64-bit mix (splitmix64) of ``seed`` (default: the env's) and

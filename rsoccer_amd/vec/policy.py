@@ -1,0 +1,105 @@
+"""The MLP policies ``VecFusedEnv.lookahead_policy`` evaluates inside the lookahead launch (include/rsx.h: rsx_policy_mlp).
+
+:class:`MLPPolicy` describes the SHAPE of a policy; its parameters are a flat float32 vector laid out like
+``torch.nn.utils.parameters_to_vector`` of ``Sequential(Linear(obs_dim, hidden), act, [Linear(hidden, hidden), act,]
+Linear(hidden, act_dim))``: ``W1 [hidden, obs_dim]`` row-major, ``b1``, (``W2``, ``b2``,) ``Wo [act_dim, hidden]``, ``bo``.  Many
+parameter vectors of one shape — a population — form the ``[K, P]`` tensor the env call takes."""
+from rsoccer_amd import _lib
+
+_HIDDEN_ACTS = {"relu": _lib.ACT_RELU, "tanh": _lib.ACT_TANH}
+_OUT_ACTS = {"clip": _lib.ACT_CLIP, "tanh": _lib.ACT_TANH}
+
+
+class MLPPolicy:
+    """``obs_dim -> hidden [-> hidden] -> act_dim`` with ``layers`` in (1, 2) hidden layers of ``hidden`` in (32, 64) units,
+    ``hidden_act`` in ("relu", "tanh") and ``out_act`` in ("clip", "tanh") — "clip" clamps to [-1, 1].  Anything else: ValueError."""
+
+    def __init__(self, obs_dim, act_dim, hidden=64, layers=2, hidden_act="tanh", out_act="tanh"):
+        self.obs_dim, self.act_dim, self.hidden, self.layers = int(obs_dim), int(act_dim), int(hidden), int(layers)
+        if self.obs_dim < 1 or self.act_dim < 1:
+            raise ValueError(f"obs_dim and act_dim must be >= 1, got {obs_dim}, {act_dim}")
+        if self.hidden not in (32, 64):
+            raise ValueError(f"hidden must be 32 or 64, got {hidden}")
+        if self.layers not in (1, 2):
+            raise ValueError(f"layers must be 1 or 2, got {layers}")
+        if hidden_act not in _HIDDEN_ACTS:
+            raise ValueError(f"hidden_act must be one of {sorted(_HIDDEN_ACTS)}, got {hidden_act!r}")
+        if out_act not in _OUT_ACTS:
+            raise ValueError(f"out_act must be one of {sorted(_OUT_ACTS)}, got {out_act!r}")
+        self.hidden_act, self.out_act = hidden_act, out_act
+
+    # ---- layout ----
+    @property
+    def shapes(self):
+        """the tensors of one policy in layout order: [(out, in), (out,), ...]"""
+        h = self.hidden
+        dims = [(h, self.obs_dim)] + [(h, h)] * (self.layers - 1) + [(self.act_dim, h)]
+        out = []
+        for o, i in dims:
+            out += [(o, i), (o,)]
+        return out
+
+    @property
+    def num_params(self):
+        n = 0
+        for s in self.shapes:
+            n += s[0] * (s[1] if len(s) == 2 else 1)
+        return n
+
+    def spec(self):
+        """the rsx_policy_mlp of this shape"""
+        return _lib.PolicyMLP(self.layers, self.hidden, _HIDDEN_ACTS[self.hidden_act], _OUT_ACTS[self.out_act])
+
+    def pack(self, weights_and_biases):
+        """``[W1, b1, (W2, b2,) Wo, bo]`` (tensors or arrays of the shapes above) -> the flat float32 vector ``[P]``"""
+        import torch
+        ts = [torch.as_tensor(t) for t in weights_and_biases]
+        if [tuple(t.shape) for t in ts] != self.shapes:
+            raise ValueError(f"expected tensors of shapes {self.shapes}, got {[tuple(t.shape) for t in ts]}")
+        return torch.cat([t.detach().to(torch.float32).reshape(-1) for t in ts])
+
+    def unpack(self, flat):
+        """``[..., P]`` -> ``[W1, b1, (W2, b2,) Wo, bo]`` as views, leading dimensions kept (``[K, P]`` gives ``[K, out, in]`` ...)"""
+        import torch
+        flat = torch.as_tensor(flat)
+        if flat.shape[-1] != self.num_params:
+            raise ValueError(f"expected {self.num_params} parameters per policy, got {flat.shape[-1]}")
+        out, at = [], 0
+        for s in self.shapes:
+            n = s[0] * (s[1] if len(s) == 2 else 1)
+            out.append(flat[..., at:at + n].reshape(tuple(flat.shape[:-1]) + s))
+            at += n
+        return out
+
+    def _torch_acts(self):
+        import torch
+        hid = torch.relu if self.hidden_act == "relu" else torch.tanh
+        out = torch.tanh if self.out_act == "tanh" else (lambda v: v.clamp(-1.0, 1.0))
+        return hid, out
+
+    def from_module(self, module):
+        """the flat parameters of a ``torch.nn.Sequential(Linear, act, Linear, ...)`` of this shape (its Linear layers in order)"""
+        import torch
+        lin = [m for m in module if isinstance(m, torch.nn.Linear)]
+        ps = []
+        for m in lin:
+            if m.bias is None:
+                raise ValueError("every Linear layer needs a bias")
+            ps += [m.weight, m.bias]
+        return self.pack(ps)
+
+    def forward(self, obs, params, dtype=None):
+        """The reference forward pass in torch: ``obs [..., obs_dim]``, ``params [P]`` (or ``[..., P]`` with leading dimensions that
+        broadcast against obs's) -> actions ``[..., act_dim]`` in ``dtype`` (default float64).  For tests and for callers who run
+        the same policy through ``step()``; the engine's own arithmetic is float32 in a fixed order (include/rsx.h)."""
+        import torch
+        dtype = torch.float64 if dtype is None else dtype
+        x = torch.as_tensor(obs).to(dtype)
+        ts = [t.to(dtype) for t in self.unpack(torch.as_tensor(params).to(x.device))]
+        hid, out = self._torch_acts()
+        n = len(ts) // 2
+        for li in range(n):
+            w, b = ts[2 * li], ts[2 * li + 1]
+            x = (w @ x.unsqueeze(-1)).squeeze(-1) + b
+            x = hid(x) if li + 1 < n else out(x)
+        return x
