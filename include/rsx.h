@@ -257,8 +257,17 @@ int rsx_task_reseed(rsx_sim* h, uint64_t seed, void* stream);
 /* Which tile layout steps this handle's envs (chosen at attach from task and batch size; results are identical in all):
  * "8-lanes-per-env" / "16-..." / "32-..." / "64-...", "32-lanes-per-env-large-batch", "one-lane-per-env",
  * "four-lanes-per-env".  NUL-terminated into out[n] — for profiles and benchmark lines, so that nothing outside the
- * library restates its thresholds. */
+ * library restates its thresholds.
+ * VSS-v0 3v3 handles of at most 4096 envs run the single steps of "8-lanes-per-env" in its PAIRED form: workgroups of two
+ * waves, the lane-group wave (loads, commands, physics, observation, episode end and placement, state stores) and a service
+ * wave with the same lane map that takes the rest off it: the step's random draws and the touch of the kernel's code at the
+ * start; the reward, the info terms, the reward / flag / info stores, the task scalar and the episode counters at the end
+ * (RSX_SERVICE_WAVE=0|1 before rsx_task_attach overrides the batch rule).  It is still that layout — same lane map, same grid,
+ * same results bit for bit — and this call names it so; rollouts, resets and every other handle run the one-wave kernels. */
 int rsx_task_layout(rsx_sim* h, char* out, size_t n);
+/* Whether the handle's single steps run in that paired form: *out = 1 or 0 (the plan made by rsx_task_attach /
+ * rsx_physics_enable from task, batch and RSX_SERVICE_WAVE).  For tests and profiles: the layout name does not tell. */
+int rsx_task_service_wave(rsx_sim* h, int* out);
 /* Introspection of the placement cache (handles of STATIC_DEFENDERS 1v6 with at most 16 384 envs: every
  * single-step launch carries helper workgroups that compute each env's NEXT episode's random placement ahead of time —
  * a pure function of seed, global env id and episode — so that the wave that resets an env only copies it; results are

@@ -41,7 +41,7 @@ SYMBOLS = (
     "rsx_get_field_params", "rsx_reset", "rsx_step", "rsx_get_state", "rsx_step_state", "rsx_wire_buffers", "rsx_step_wire", "rsx_set_state",
     "rsx_get_state_full", "rsx_dev_view_get", "rsx_step_dev", "rsx_step_dev_random", "rsx_step_dev_flip", "rsx_state_buffers",
     "rsx_reset_dev", "rsx_task_attach",
-    "rsx_task_view_get", "rsx_task_reseed", "rsx_task_layout", "rsx_task_placement_cache_stats", "rsx_task_reset", "rsx_task_reset_to", "rsx_task_step",
+    "rsx_task_view_get", "rsx_task_reseed", "rsx_task_layout", "rsx_task_service_wave", "rsx_task_placement_cache_stats", "rsx_task_reset", "rsx_task_reset_to", "rsx_task_step",
     "rsx_task_step_n", "rsx_task_rollout", "rsx_read_metrics", "rsx_metrics_fold", "rsx_check_finite",
     "rsx_task_checkpoint_size", "rsx_task_checkpoint_save", "rsx_task_checkpoint_load",
     "rsx_task_enable_capture", "rsx_task_tick", "rsx_drop_pending_hip_error", "rsx_task_lookahead",
@@ -134,6 +134,7 @@ def load():
     lib.rsx_get_state.argtypes = [vp, vp, vp]
     lib.rsx_step_state.argtypes = [vp, vp, vp, vp]
     lib.rsx_task_layout.argtypes = [vp, C.c_char_p, C.c_size_t]
+    lib.rsx_task_service_wave.argtypes = [vp, C.POINTER(C.c_int)]
     lib.rsx_task_placement_cache_stats.argtypes = [vp, C.POINTER(C.c_int64), vp]
     lib.rsx_set_state.argtypes = [vp, vp, vp]
     lib.rsx_wire_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
@@ -423,6 +424,12 @@ class Sim:
         buf = C.create_string_buffer(64)
         _chk(self._lib.rsx_task_layout(self._h, buf, 64))
         return buf.value.decode()
+
+    def task_service_wave(self):
+        """whether single steps run in the paired form, a service wave next to each physics wave (rsx_task_service_wave)"""
+        out = C.c_int(0)
+        _chk(self._lib.rsx_task_service_wave(self._h, C.byref(out)))
+        return bool(out.value)
 
     def placement_cache_stats(self, stream=None):
         """(resets served from the placement cache, resets placed inline), or (-1, -1) — rsx_task_placement_cache_stats"""

@@ -44,6 +44,7 @@ void launch_task_of(const rsx_sim* h, const float* actions, int n_steps, int mod
         case Layout::LanesBig: launch_scrimmage_big(rollout, h->P, b, n_steps, s); break;
         case Layout::Lanes:
             if (h->d_phys) launch_task_phys(h->P, b, h->L, h->NR, h->d_phys, n_steps, mode, s);
+            else if (mode == MODE_STEP && h->plan.service_wave) launch_task_pair(h->P, b, n_steps, s);   // (same grid, two waves per workgroup)
             else launch_task(h->P, b, h->L, h->NR, helpers_for(h, mode), n_steps, mode, s);
             break;
     }
@@ -55,7 +56,7 @@ bool rollout_as_steps(const rsx_sim* h) { return h->plan.rollout_as_steps || (h-
 void rsx::plan_stepping(rsx_sim* h) {
     const Params& P = h->P;
     h->plan = plan_layout(LayoutQuery{P.task, P.kind, h->L, h->NR, P.n_blue, P.num_envs, P.row_stride, P.state_dim, P.obs_dim, P.n_sub,
-                                      h->d_phys != nullptr, std::getenv("RSX_LAYOUT")});
+                                      h->d_phys != nullptr, std::getenv("RSX_LAYOUT"), std::getenv("RSX_SERVICE_WAVE")});
     h->tick_slots = step_grid(h, MODE_STEP);
 }
 
@@ -182,6 +183,13 @@ int rsx_task_layout(rsx_sim* h, char* out, size_t n) {
     const char* name = lay == Layout::Epl ? "one-lane-per-env" : lay == Layout::Quad ? "four-lanes-per-env" : lay == Layout::LanesBig ? "32-lanes-per-env-large-batch"
                      : h->L == 8 ? "8-lanes-per-env" : h->L == 16 ? "16-lanes-per-env" : h->L == 32 ? "32-lanes-per-env" : "64-lanes-per-env";
     std::snprintf(out, n, "%s", name);
+    return RSX_OK;
+}
+
+int rsx_task_service_wave(rsx_sim* h, int* out) {
+    if (!h || !out) return fail(RSX_ERR_ARG, "null argument");
+    if (h->P.task == RSX_TASK_NONE) return fail(RSX_ERR_STATE, "no task attached (rsx_task_attach)");
+    *out = h->plan.step == Layout::Lanes && h->plan.service_wave && !h->d_phys ? 1 : 0;   // (what launch_task_of dispatches on)
     return RSX_OK;
 }
 

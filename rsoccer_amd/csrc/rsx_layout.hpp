@@ -44,6 +44,14 @@ constexpr int RSX_EPL_MIN_ENVS_DRIBBLING = 49152, RSX_EPL_MIN_ENVS_DUEL = 32768;
 #ifndef RSX_QUAD_ROLLOUT_MIN_ENVS_CROWDED
 #define RSX_QUAD_ROLLOUT_MIN_ENVS_CROWDED 196608
 #endif
+// largest batch of VSS-v0 3v3 whose single steps run in the paired form (rsx_pair.hpp: a service wave next to each physics wave;
+// RSX_SERVICE_WAVE=0|1 overrides).  Measured, one build, RSX_SERVICE_WAVE=0 vs 1, us per step (profiles/LABBOOK.md, "A service wave
+// for the VSS-v0 3v3 single step"): 2048 envs 8.77 vs 8.31 (-5.3 %), 4096 envs 9.45 vs 9.17 (-3.0 %), 6144 envs 9.73 vs 9.55 (-1.9 %),
+// 8192 envs 9.91 vs 9.81 (-1.0 %).  The form still wins above 4096 envs, where the service waves no longer find SIMDs of their own
+// (2 x tiles > 1024 on this part), but by less than the 2 % that keeps a change: the threshold is the last measured batch that clears it.
+#ifndef RSX_SERVICE_WAVE_MAX_ENVS
+#define RSX_SERVICE_WAVE_MAX_ENVS 4096
+#endif
 
 namespace rsx {
 
@@ -55,12 +63,14 @@ struct StepPlan {
     Layout step = Layout::Lanes;      // single-step launches (MODE_STEP)
     Layout rollout = Layout::Lanes;   // one-launch rollouts (MODE_ROLLOUT); resets always run on the lane-group kernels
     bool rollout_as_steps = false;    // rsx_task_rollout issues n single-step launches instead of one launch
+    bool service_wave = false;        // single-step launches of Layout::Lanes run the paired form (VSS-v0 3v3 only; rollouts and resets never)
 };
 
 struct LayoutQuery {
     int task, kind, L, NR, n_blue, num_envs, row_stride, state_dim, obs_dim, n_sub;
     bool physics;             // per-env physics is on (rsx_physics_enable)
     const char* env_layout;   // the value of RSX_LAYOUT, or null (the caller reads the environment)
+    const char* env_service;  // the value of RSX_SERVICE_WAVE ("0" / "1"), or null
 };
 
 inline StepPlan plan_layout(const LayoutQuery& q) {
@@ -91,6 +101,9 @@ inline StepPlan plan_layout(const LayoutQuery& q) {
         const bool epl = asked("epl") || (!asked("lanes") && q.num_envs >= epl_min);
         if (epl && rows_below_2g && (size_t)q.num_envs * q.obs_dim * sizeof(float) < ((size_t)1 << 31)) p.step = p.rollout = Layout::Epl;
     }
+    // the paired single step: the one variant that is built (8 lanes per env, kernels specialised for 3v3), where the lane-group kernels step
+    if (task == RSX_TASK_VSS_V0 && q.NR == 6 && q.L == 8 && p.step == Layout::Lanes)
+        p.service_wave = q.env_service ? std::strcmp(q.env_service, "1") == 0 : q.num_envs <= RSX_SERVICE_WAVE_MAX_ENVS;
     return p;
 }
 

@@ -3,6 +3,10 @@
 // before the per-env variant existed (an inlined body function moved registers and instructions around: -2 % on the VSS-v0
 // headline).  Expects PHYS (constexpr bool) and `phys` (the physics block, or nullptr) in scope.  What a step shares with the lookahead
 // (rsx_plan_body.inc) is text of its own, for the same reason: rsx_step_commands.inc, rsx_step_wire.inc, rsx_step_xr.inc.
+// The paired form (rsx_pair.hpp: task_pair_step_kernel, RSX_STEP_PAIRED defined around the inclusion) runs this body with two waves
+// per workgroup: the blocks under RSX_STEP_PAIRED split the work, and what the reward lane does is text of its own that the service
+// wave includes instead (rsx_step_ball_load.inc, rsx_step_reward.inc, rsx_step_vss_metrics.inc, from rsx_step_service.inc).  Without
+// the macro the preprocessed text is what it was before that form existed.
     // A multi-step launch is short of SGPRs, not of start-up latency: there the preloaded copies
     // are left dead and everything is fetched from the kernarg segment when it is needed.
     constexpr bool HOT = MODE != MODE_ROLLOUT;
@@ -35,12 +39,37 @@
         }
     }
     StepTick tk{0u, true};
+#ifdef RSX_STEP_PAIRED
+    __shared__ PairBox pb;
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // 0: the physics wave, 1: the service wave
+    // the first 8 KB of code behind this point are touched by the service wave (CODE_PF below; taken here, where both waves pass, so
+    // that the window starts at the head of the kernel whatever the layout of the two waves' code)
+    unsigned long long code_pc;
+    asm volatile("s_getpc_b64 %0" : "=s"(code_pc));
+    if (tick_dev) {
+        // a device-keyed handle: the physics wave reads, checks and advances the workgroup's slot, the service wave is handed the
+        // result.  tick_dev is a launch argument: both waves are here or neither is
+        if (wv == 0) {
+            tk = step_tick(true, P, bufs, 1u);
+            if (threadIdx.x == 0) { pb.tick = tk.t; pb.ok = tk.ok ? 1u : 0u; }
+        }
+        pair_barrier();
+        if (wv != 0) tk = StepTick{(uint32_t)__builtin_amdgcn_readfirstlane((int)pb.tick), __builtin_amdgcn_readfirstlane((int)pb.ok) != 0};
+    } else {
+        tk = step_tick(false, P, bufs, 1u);
+    }
+    // the one early exit: the same value on both waves, taken by both, in front of barrier 1
+    if (__builtin_expect(!tk.ok, 0)) return;
+    const uint32_t tick0 = tk.t;
+    const int lane = threadIdx.x & 63;
+#else
     if (MODE == MODE_STEP || MODE == MODE_ROLLOUT) {
         tk = step_tick(tick_dev, P, bufs, (uint32_t)n_steps);
         if (__builtin_expect(!tk.ok, 0)) return;
     }
     const uint32_t tick0 = tk.t;
     const int lane = threadIdx.x;
+#endif
     const int b = LaneMap<L>::body(lane), g = LaneMap<L>::env(lane);
     const int tile = tile_of_block(HOT ? hp_per_xcd : (int)(gridDim.x >> 3));
     const int e = tile * G + g;
@@ -53,6 +82,14 @@
     constexpr int OD_C = obs_dim_c<TASK, NR>();
     const int OD = OD_C ? OD_C : P.obs_dim;
 #define auxe(ROW) at_byte(bufs.aux, (ix_t)(ROW) * ((ix_t)4 * (ix_t)P.row_stride) + (ix_t)4 * (ix_t)e)   // row ROW of this env in the scalar arena
+#ifdef RSX_STEP_PAIRED
+    // (a workgroup of the idle tail behind the last tile has no live lane and still runs to the end on both waves: both barriers are met)
+    // The included text is ONE braced block, the whole life of the service wave from here on, and its last statement is `return`:
+    // nothing below this line runs on wave 1.  Keep it so — a service wave that fell through would run the physics wave's
+    // barriers a second time and park its partner.
+    if (wv != 0)
+#include "rsx_step_service.inc"
+#endif
 
 #ifdef RSX_TIMING
     if (lane == 0) { sh.dbg = bufs.dbg; bufs.dbg[(size_t)13 * gridDim.x + blockIdx.x] = __builtin_amdgcn_s_memrealtime(); }  // 100 MHz, chip-wide
@@ -66,7 +103,11 @@
     // ONE data load — a lane per 128-byte line; it lands with the state loads, long before the wave gets there — so that those
     // instruction fetches find their lines in the L2: VSS-v0 at 4096 envs 9.02 -> 8.88 us per step (three interleaved rounds).
     // Measured per kernel: later windows (+4, +8, +12 KB) or 16 / 24 KB gain nothing; the SSL kernels lose (11v11 +4 %, 1v6 +0.5 %).
+#ifdef RSX_STEP_PAIRED
+    constexpr bool CODE_PF = false;   // (the service wave's load)
+#else
     constexpr bool CODE_PF = !PHYS && KIND == RSX_KIND_VSS && MODE == MODE_STEP;   // (measured for the literal kernels only)
+#endif
     uint32_t code_touch = 0;
     if (CODE_PF) {
         unsigned long long pc;
@@ -86,15 +127,9 @@
     }
     float info[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     float prev_pot = 0.0f, ep_ret = 0.0f;
-    if (is_ball) {
-        // VSS-v0: rows 0, 4, 5 (goal counters) are zero except on a terminal step, and the step after it
-        // clears them: they are neither read nor — in the common case — written
-#pragma unroll
-        for (int i = 0; i < ID; ++i)
-            if (!(TASK == RSX_TASK_VSS_V0 && (i == 0 || i >= 4))) info[i] = auxe(ROW_INFO + i);
-        prev_pot = auxe(ROW_PREV_POT);
-        if (TASK != RSX_TASK_VSS_V0) ep_ret = auxe(ROW_EP_RET);   // VSS-v0: derived from the info terms
-    }
+#ifndef RSX_STEP_PAIRED   // (the paired form: the service wave loads them)
+#include "rsx_step_ball_load.inc"
+#endif
     // metrics[0] (env-steps) is counted on the device by ONE lane of the grid: launches of a handle
     // are stream-ordered, so a plain read-modify-write is race free and costs no atomic
     const bool counts_steps = (MODE == MODE_STEP || MODE == MODE_ROLLOUT) && blockIdx.x == 0 && lane == 0;
@@ -135,7 +170,9 @@
 
     // single-step launches: this step's random numbers, computed in the shadow of the loads
     StepDraw pre;
+#ifndef RSX_STEP_PAIRED   // (the paired form: the service wave's, picked up behind the load wait)
     if (MODE == MODE_STEP) pre = draw_for_step<KIND, TASK>(P, env_id, tick0, b, is_robot, fed);
+#endif
 
     // All loads land here, once.  Without this the compiler parks a vmcnt(0) at the top of the
     // step loop (loop-carried values come from loads on the first trip), and on gfx9-class
@@ -144,6 +181,18 @@
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
     if (CODE_PF) asm volatile("" :: "v"(code_touch));   // (the value itself is of no interest)
     interpret_body<KIND>(raw, is_robot, is_ball, o, od, wd, wheels);
+#ifdef RSX_STEP_PAIRED
+    RSX_STAMP(22);
+    // barrier 1 (both waves, unconditionally: no branch between the early exit above and this line): the service wave has published
+    // this step's draws, and its loads of the step counter and the info rows have landed
+    pair_barrier();
+    {
+        const float2 d2 = pb.dr[lane];
+#pragma unroll
+        for (int i = 0; i < 5; ++i) pre.v[i] = 0.0f;
+        pre.v[0] = d2.x; pre.v[1] = d2.y;
+    }
+#endif
     RSX_STAMP(1);
 
     for (int it = 0; it < n_steps; ++it) {
@@ -215,31 +264,15 @@
             }
 
             // ---- wire-format values, observation, reward ----
+#ifdef RSX_STEP_PAIRED
+#include "rsx_step_pair_tail.inc"   // (hand-over to the service wave right behind physics(), then the wire format and the observation)
+#else
 #include "rsx_step_wire.inc"
             write_obs<KIND, TASK>(P, bufs.obs + (size_t)e * OD, b, is_robot, is_ball, o.x, o.y, o.vx, o.vy, o.s, o.c, wd, o.ir, obs_ts);
 #include "rsx_step_xr.inc"   // what the reward lane (the ball's) needs from the robots' lanes -> sh.x0[g]
             wave_sync();
-            if (is_ball) {
-                const float* xr = sh.x0[g];
-                task_reward<KIND, TASK>(P, xr, o.x, o.y, lastx, lasty, first_step, prev_pot, info, reward, term, success, against);
-                ep_ret = ep_ret + reward;
-            }
-            steps += 1;
-            trunc = steps >= P.max_steps;
-            // episode-end flag of the env: held by its ball lane (lane N*G + g), spread with one
-            // ballot instead of an LDS round trip
-            const unsigned long long endm = __ballot(is_ball && (term | trunc));
-            ended = live && ((endm >> (LaneMap<L>::slot(N, g))) & 1ull) != 0;
-            if (is_ball) {
-                // info is reported as it stands after this step (cleared lazily at the next
-                // episode's first step), like the dict the reference returns with `done`
-#pragma unroll
-                for (int i = 0; i < ID; ++i)
-                    if (!(TASK == RSX_TASK_VSS_V0 && (i == 0 || i >= 4)) || term || first_step) auxe(ROW_INFO + i) = info[i];
-                auxe(ROW_REWARD) = reward;
-                if (MODE == MODE_STEP) { bufs.flags[(ix_t)e] = (uint8_t)term; bufs.flags[(ix_t)P.num_envs + (ix_t)e] = (uint8_t)trunc; }
-                else { bufs.flags[e] = (uint8_t)term; bufs.flags[B + e] = (uint8_t)trunc; }
-            }
+#include "rsx_step_reward.inc"
+#endif
         }
 
         RSX_STAMP(4);
@@ -250,15 +283,9 @@
             }
             if (ended && mode == 0) episode += 1;   // every lane of the env: the new episode's id
             if (KIND == RSX_KIND_VSS) {
-                if (ended && is_ball && mode == 0) {
-                    unsigned long long* const ms = metric_slot(bufs);
-                    atomicAdd(&ms[1], 1ull);
-                    if (info[4] > 0.0f) atomicAdd(&ms[2], 1ull);
-                    if (info[5] > 0.0f) atomicAdd(&ms[3], 1ull);
-                    atomicAdd(&ms[4], (unsigned long long)__float2ll_rn(vss_episode_return(info) * 1048576.0f));
-                    atomicAdd(&ms[5], (unsigned long long)steps);
-                    if (trunc && !term) atomicAdd(&ms[6], 1ull);
-                }
+#ifndef RSX_STEP_PAIRED   // (the paired form: the service wave holds the info terms and adds the counters)
+#include "rsx_step_vss_metrics.inc"
+#endif
             } else if (mode == 0) {
                 // SSL tasks (short episodes: several resetting waves in every launch): the ball lane
                 // holds the increments, lanes 0..5 of the env add one each, so the wave issues ONE
@@ -347,11 +374,13 @@
     if (TASK == RSX_TASK_VSS_V0 && is_robot && b >= 1) {
         auxe(ROW_OU + 2 * b) = ou0; auxe(ROW_OU + 2 * b + 1) = ou1;
     }
+#ifndef RSX_STEP_PAIRED   // (the paired form: the service wave's store)
     if (is_ball) {
         auxe(ROW_PREV_POT) = prev_pot;
         if (TASK != RSX_TASK_VSS_V0) auxe(ROW_EP_RET) = ep_ret;
-#undef auxe
     }
+#endif
+#undef auxe
     if (counts_steps) bufs.metrics[0] = steps_before + (unsigned long long)P.num_envs * (unsigned long long)n_steps;
     RSX_STAMP(6);
 #ifdef RSX_TIMING

@@ -38,6 +38,9 @@ int epl_grid(int num_envs);
 int ssl_quad_grid(int num_envs);
 // rsx_big.hip: the 32-lanes-per-env kernel of the scrimmage task built for large batches
 void launch_scrimmage_big(bool rollout, const Params& P, const Buffers& b, int n_steps, hipStream_t s);
+// rsx_pair.hip: the paired form of the VSS-v0 3v3 single step (8 lanes per env, literal coefficients; n_steps = 1 | flags): launch_task's
+// grid with workgroups of two waves, a physics wave and a service wave (rsx_pair.hpp; chosen by rsx_layout.hpp: StepPlan::service_wave)
+void launch_task_pair(const Params& P, const Buffers& b, int n_steps, hipStream_t s);
 // rsx_phys.hip: the kernels of physics-enabled handles (rsx_physics_enable)
 void launch_task_phys(const Params& P, const Buffers& b, int L, int NR, float* phys, int n_steps, int mode, hipStream_t s);
 void launch_sim_phys(const Params& P, const Buffers& b, int L, int NR, float* phys, float* state_out, int rand_tick, hipStream_t s);

@@ -12,7 +12,7 @@
 // guards keep a branch that can never be taken for this KIND / TASK from instantiating a kernel of its own.
 //
 // Not here: the choice of LAYOUT for a handle (one lane per env, four lanes per env, the large-batch build, placement helpers,
-// the per-env physics route) — rsx_layout.hpp decides that (plan_layout), and rsx_api_task.hip dispatches on it in front of these tables.
+// the per-env physics route, the paired single step of VSS-v0 3v3 — one variant, named by rsx_pair.hip itself) — rsx_layout.hpp decides that (plan_layout), and rsx_api_task.hip dispatches on it in front of these tables.
 #pragma once
 #include <type_traits>
 #include <utility>
@@ -95,11 +95,13 @@ inline int mode_steps(const int mode, const int n_steps) { return mode == MODE_S
 // ---- launches ----------------------------------------------------------------------------------------------------------
 // Workgroups of a launch of a kernel with the RSX_HOT_ARGS parameter list: `tiles` of them map to tiles, `helpers` more sit
 // behind them (the tile map still sees the tile grid); `lds`: dynamic LDS; `per_xcd`: the tile-map argument where it is not
-// tiles / 8 (the zig-zag order of the one-lane-per-env single steps), 0 = tiles / 8
+// tiles / 8 (the zig-zag order of the one-lane-per-env single steps), 0 = tiles / 8; `threads`: per workgroup — one wave, or the two of
+// the paired single step (rsx_pair.hpp)
 struct HotGrid {
     int tiles, helpers = 0;
     size_t lds = 0;
     int per_xcd = 0;
+    int threads = 64;
 };
 
 // hot arguments first (preloaded into SGPRs, see RSX_HOT_ARGS), then the by-value structs, then the unit's own trailing
@@ -107,7 +109,7 @@ struct HotGrid {
 template <typename... KArgs, typename... Tail>
 void launch_hot(void (*kernel)(KArgs...), const HotGrid& g, hipStream_t s, float* out, const float* in, const int n, const Params& P,
                 const Buffers& b, Tail&&... tail) {
-    rsx_launch(kernel, dim3((unsigned)(g.tiles + g.helpers)), dim3(64), g.lds, s, b.state, out, in, b.flags, P.num_envs,
+    rsx_launch(kernel, dim3((unsigned)(g.tiles + g.helpers)), dim3((unsigned)g.threads), g.lds, s, b.state, out, in, b.flags, P.num_envs,
                RSX_HOT_DIM(P.state_dim, P.row_stride, P.num_envs), g.per_xcd ? g.per_xcd : g.tiles >> 3, n, P, b, std::forward<Tail>(tail)...);
 }
 // task step: aux rows and fed actions, n_steps

@@ -6,7 +6,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from rsoccer_amd import _lib as L
 B = int(os.environ.get("B", 4096))
-NS = 20
+NS = 26   # stamp rows: 0-7 the step, 8-12 sub-steps, 13 / 14 real time, 15-18 reset, 19-21 service wave, 22 / 23 physics wave at the two barriers (paired form)
 G = 64 // int(os.environ.get("LANES", 8))   # envs per wave (LANES=32 for the 11v11 task)
 nb = ((B + G - 1) // G + 7) // 8 * 8
 # SSLStaticDefenders single-step launches with the placement cache on carry ceil(B / 64) helper workgroups behind the tiles: the
@@ -60,6 +60,16 @@ for label, fn in (("single-step launch", lambda: sim.task_step(None, s)),
             for n_, a_, b_ in (("reset: terminal obs + metrics", 4, 15), ("reset: predraw", 15, 16), ("reset: placement", 16, 17), ("reset: new obs", 17, 18), ("obs copy-out after reset", 18, 5)):
                 x = (d[:, b_] - d[:, a_])[rs]
                 print(f"    {n_:34s} mean {x.mean():8.0f} over {rs.sum() / d.shape[0]:.1f} waves per launch")
+        if (d[:, 20] > 0).any():   # the paired form (rsx_pair.hpp): both waves of a workgroup stamp the same clock
+            print("  paired form, shader cycles (median / p95 over workgroups and launches; 'entry' is the physics wave's):")
+            for n_, a_, b_ in (("service: entry -> at barrier 1", 0, 19), ("physics: entry -> at barrier 1", 0, 22), ("physics: at barrier 1 -> draws read", 22, 1),
+                               ("physics: physics done -> at barrier 2", 3, 23), ("physics: at barrier 2 -> end test, wire format, obs done", 23, 4),
+                               ("service: physics at barrier 2 -> passed", 23, 20), ("service: reward, info, flags, counters", 20, 21),
+                               ("service done - physics stores issued", 6, 21)):
+                if n_.startswith("physics: entry -> at barrier 1") and not (d[:, 22] > 0).any():
+                    continue
+                x = d[:, b_] - d[:, a_]
+                print(f"    {n_:42s} median {np.median(x):8.0f}  p95 {np.percentile(x, 95):8.0f}")
         print("  wave duration ns: mean %.0f, of the last-finishing wave %.0f" % (((d[:, 14] - d[:, 13]) * 10).mean(), ((d[it, 14, last] - d[it, 13, last]) * 10).mean()))
         print("  last wave to finish (avg over launches), shader cycles per region:")
         for n, a, b in seq:
