@@ -1,0 +1,91 @@
+"""PPO on VSS-v0 with every rollout collected in one launch.
+
+    python examples/ppo_vss.py [--envs 1024] [--steps 128] [--updates 10] [--epochs 4] [--minibatches 4] [--lr 3e-4]
+
+One update: env.collect(...) advances the envs `steps` steps under the current actor — the MLP evaluated inside the engine's launch, a
+Gaussian head on top, episode ends handled in the launch — and returns the [T, B] batch; the critic (a torch module the engine never
+sees) is evaluated on the recorded observations, advantages are GAE, and a few epochs of clipped PPO follow in torch.  The actor's
+weights reach the engine as one flat vector (MLPPolicy.from_module: torch's own layout).  The density PPO compares is the
+pre-activation one: log N(sample; mean, exp(log_std)), where the action fed to the env is clip(sample) — the trainer evaluates the
+same expression on the recorded `sample`, so the ratio is exact.  A demonstration of the call pattern, not a tuned trainer."""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from rsoccer_amd.vec import VecVSSEnv
+from rsoccer_amd.vec.policy import MLPPolicy
+
+
+def log_prob(mean, log_std, sample):
+    z = (sample - mean) / log_std.exp()
+    return (-0.5 * z * z - log_std - 0.9189385332046727).sum(-1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=1024)
+    ap.add_argument("--steps", type=int, default=128, help="T: steps per env and update")
+    ap.add_argument("--updates", type=int, default=10)
+    ap.add_argument("--epochs", type=int, default=4)
+    ap.add_argument("--minibatches", type=int, default=4)
+    ap.add_argument("--lr", type=float, default=3e-4)
+    ap.add_argument("--gamma", type=float, default=0.99)
+    ap.add_argument("--lam", type=float, default=0.95)
+    ap.add_argument("--clip", type=float, default=0.2)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+
+    torch.manual_seed(args.seed)
+    env = VecVSSEnv(args.envs, device=0, seed=args.seed)
+    dev, OD, AD = env.device, env.sim.obs_dim, env.sim.act_dim
+    pol = MLPPolicy(OD, AD, hidden=64, layers=2, hidden_act="tanh", out_act="clip")
+    # the actor WITHOUT its output activation: the engine applies the clip to the noisy sample, the trainer needs the mean
+    actor = torch.nn.Sequential(torch.nn.Linear(OD, 64), torch.nn.Tanh(), torch.nn.Linear(64, 64), torch.nn.Tanh(), torch.nn.Linear(64, AD)).to(dev)
+    critic = torch.nn.Sequential(torch.nn.Linear(OD, 64), torch.nn.Tanh(), torch.nn.Linear(64, 64), torch.nn.Tanh(), torch.nn.Linear(64, 1)).to(dev)
+    log_std = torch.nn.Parameter(torch.full((AD,), -0.5, device=dev))
+    opt = torch.optim.Adam(list(actor.parameters()) + list(critic.parameters()) + [log_std], lr=args.lr)
+    T, B = args.steps, args.envs
+    env.reset()
+    for update in range(args.updates):
+        t0 = time.perf_counter()
+        batch = env.collect(pol, pol.from_module(actor), T, log_std=log_std, iteration=update)
+        with torch.no_grad():
+            done = batch["terminated"] | batch["truncated"]
+            values = critic(batch["obs"]).squeeze(-1)                      # [T, B]
+            nxt = torch.cat([values[1:], critic(batch["next_obs"]).squeeze(-1)[None]])
+            # an ended row bootstraps nothing (a truncated one could bootstrap from return_final_obs=True's rows; kept simple here)
+            delta = batch["reward"] + args.gamma * nxt * (~done) - values
+            adv = torch.zeros_like(delta)
+            run = torch.zeros(B, device=dev)
+            for t in reversed(range(T)):
+                run = delta[t] + args.gamma * args.lam * (~done[t]) * run
+                adv[t] = run
+            ret = adv + values
+            adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+        torch.cuda.synchronize()
+        t_collect = time.perf_counter() - t0
+        flat = {k: batch[k].reshape(T * B, -1) for k in ("obs", "sample")}
+        old_lp, adv_f, ret_f = batch["log_prob"].reshape(-1), adv.reshape(-1), ret.reshape(-1)
+        for _ in range(args.epochs):
+            for idx in torch.randperm(T * B, device=dev).chunk(args.minibatches):
+                lp = log_prob(actor(flat["obs"][idx]), log_std, flat["sample"][idx])
+                ratio = (lp - old_lp[idx]).exp()
+                loss_pi = -torch.min(ratio * adv_f[idx], ratio.clamp(1 - args.clip, 1 + args.clip) * adv_f[idx]).mean()
+                loss_v = 0.5 * (critic(flat["obs"][idx]).squeeze(-1) - ret_f[idx]).pow(2).mean()
+                opt.zero_grad(set_to_none=True)
+                (loss_pi + 0.5 * loss_v).backward()
+                opt.step()
+        torch.cuda.synchronize()
+        m = env.metrics()
+        print(f"update {update}: mean reward / step {float(batch['reward'].mean()):+.5f}, episodes {m['episodes']}, goals for / against "
+              f"{m['goals_for']} / {m['goals_against']}, sigma {log_std.exp().mean().item():.3f}; collect + advantages "
+              f"{t_collect * 1e3:.1f} ms, update {((time.perf_counter() - t0) - t_collect) * 1e3:.1f} ms")
+    env.close()
+
+
+if __name__ == "__main__":
+    main()

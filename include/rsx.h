@@ -448,7 +448,8 @@ typedef struct rsx_policy_mlp {
  *                as fed actions are not.
  *   arithmetic   unit j of a layer: acc = bias[j]; for i = 0 .. n_in - 1 ascending: acc = fmaf(W[j][i], x[i], acc), in float32, then
  *                the activation.  One lane computes a whole unit and nothing is reduced across lanes, so the bits do not depend on the
- *                kernel layout or on per-env physics.  No stochastic head: parameter noise is the caller's.
+ *                kernel layout or on per-env physics.  No stochastic head in this call (parameter noise is the caller's);
+ *                rsx_task_collect_policy below has one.
  *   what it sees at step 0 of a pair the env's row of the handle's obs buffer — what the caller's own policy would have seen after the
  *                last rsx_task_step / reset / reset_to / transfer (NOT a recomputation from the state: SSLDribbling's observation
  *                carries a task scalar that lags the state by design); at step t >= 1 the observation simulated step t - 1 produced,
@@ -473,9 +474,56 @@ int rsx_task_lookahead_policy(rsx_sim* h, const rsx_policy_mlp* p, const float* 
                               float* returns_dev, int32_t* steps_dev, uint8_t* flags_dev, float* last_obs_dev,
                               float* actions_out_dev, float* obs_out_dev, void* stream);
 
+/* ---- on-policy collection: the envs advanced under an MLP policy inside one launch (additive extension of ABI 6) ------------------
+ * What an on-policy trainer (PPO, A2C) calls between two updates: advance the REAL envs n_steps steps under the current policy, keep
+ * going through episode ends, and hand back the [T][B] batch (T = n_steps, B = num_envs) of observations, actions, rewards and done
+ * flags.  One launch: rsx_task_rollout's multi-step trip with auto-reset, rsx_task_lookahead_policy's policy between the steps.
+ *   p, params_dev    the policy of rsx_task_lookahead_policy (rsx_policy_mlp, the same parameter layout and arithmetic), ONE parameter
+ *                    vector [P].
+ *   step 0           sees the env's row of the handle's obs buffer, as rsx_task_lookahead_policy does; step t >= 1 the observation
+ *                    step t - 1 wrote — for an env whose episode ended at t - 1, the first observation of its next episode.
+ *   the head         mean_i = the output layer's accumulator (bias and ascending fmaf, before out_act);
+ *                    sample_i = mean_i + sigma_i * eps_i in float32, a multiplication and an addition (two roundings); with
+ *                    sigma_dev == NULL, sample_i = mean_i (deterministic); action_i = out_act(sample_i).
+ *   sigma_dev        [act_dim] f32 device memory, >= 0 and finite, or NULL.  Device memory is NOT checked (as params_dev and fed
+ *                    actions are not): a negative or non-finite sigma is the caller's to refuse before it is uploaded.
+ *   eps              a standard normal from the sampler's recipe above (rsx_plan_sampler: Philox 4x32-7, the same Box-Muller), with
+ *                    domain word 7:  block (i >> 2) is philox4x32-7(counter = (g, 0, tick of that step, 7 | (i >> 2) << 8), key =
+ *                    (noise_seed lo, noise_seed hi)), g the global env id; component i takes normal i & 3.  Keyed by global env id
+ *                    and step counter like every other draw: independent of the batch split, and a captured call draws fresh noise
+ *                    on every replay.  Pass another noise_seed per training run; the handle's seed is not involved. */
+typedef struct rsx_collect_out {
+    float*   obs;        /* [T][B][obs_dim]  the observation each action answered            required */
+    float*   actions;    /* [T][B][act_dim]  the action fed to the step                      required */
+    float*   rewards;    /* [T][B]                                                           required */
+    uint8_t* flags;      /* [T][B] bit 0 terminated, bit 1 truncated (as rsx_task_lookahead) required */
+    float*   final_obs;  /* [T][B][obs_dim] or NULL: written ONLY in rows whose flags != 0 (the terminal observation) */
+    float*   mean;       /* [T][B][act_dim] or NULL: the output layer before noise and before out_act */
+    float*   sample;     /* [T][B][act_dim] or NULL: mean + sigma * eps, before out_act */
+} rsx_collect_out;
+/* Commit: the call advances the handle exactly as n_steps calls of rsx_task_step(h, out->actions[t]) would.  Bit-identical to that
+ * sequence of calls are the state, every per-env task scalar (steps, episode, OU noise, info terms, task scalar, episode return),
+ * obs / reward / terminated / truncated / final_obs (the last step's values, final_obs per env that of its latest episode end), the
+ * metrics, the step counter (advanced by n_steps) and, with per-env physics, the physics block (redrawn at every episode start inside
+ * the launch): a checkpoint taken afterwards is byte for byte the checkpoint of the stepped twin.  Episode ends are handled inside the
+ * launch as in rsx_task_rollout (the placement cache of small SSLStaticDefenders handles is left as that call leaves it: entries are
+ * tagged and stay valid).  The results do not depend on the lane width (8, 16, 32) or on the physics form, and the call serves every
+ * handle rsx_task_lookahead_policy serves, those whose single steps run one lane per env included (the arrays are the same).
+ * Step counter: host-keyed handles check the 2^32 - 1 limit here and refuse to be captured (RSX_ERR_STATE, like the stepping calls);
+ * device-keyed handles (rsx_task_enable_capture) read, check and advance it on the device — a launch that would wrap it changes
+ * nothing, writes none of the outputs and sets the mark rsx_task_tick / rsx_read_metrics report — and the call may be captured and
+ * replayed.  Stream-ordered, never synchronises (RSX_DEBUG_FINITE=1 scans afterwards as for the other stepping calls).
+ * Refusals (nothing is enqueued): RSX_ERR_STATE before the first reset, at the counter limit and for a capture of a host-keyed handle;
+ * RSX_ERR_ARG for everything rsx_task_lookahead_policy refuses of a policy and a handle (null p or params_dev, a spec outside the
+ * listed values, an LDS image over 64 KB, the scrimmage task, 64 lanes per env), n_steps < 1 or > 2^30 - 1, a null `out` or a null
+ * required array. */
+int rsx_task_collect_policy(rsx_sim* h, const rsx_policy_mlp* p, const float* params_dev /* [P], one policy */,
+                            const float* sigma_dev /* [act_dim] >= 0, or NULL = deterministic */, uint64_t noise_seed,
+                            int n_steps, const rsx_collect_out* out, void* stream);
+
 /* Debugging aid: number of non-finite floats in the state rows and, with a task attached, in the
  * observations, rewards and info rows.  Synchronises `stream`.  With RSX_DEBUG_FINITE=1 in the
- * environment every stepping call (rsx_step_dev, rsx_task_step, rsx_task_step_n, rsx_task_rollout)
+ * environment every stepping call (rsx_step_dev, rsx_task_step, rsx_task_step_n, rsx_task_rollout, rsx_task_collect_policy)
  * runs this scan afterwards and returns RSX_ERR_STATE when it finds one (the reference has no such
  * guard: e.g. rsoccer_gym/vss/env_vss/vss_gym.py:298 divides by a distance that can be zero). */
 int rsx_check_finite(rsx_sim* h, int64_t* n_bad, void* stream);

@@ -52,6 +52,7 @@ SYMBOLS = (
     "rsx_task_transfer", "rsx_task_transfer_errors",
     "rsx_task_lookahead_sampled", "rsx_plan_candidates", "rsx_plan_update",
     "rsx_policy_num_params", "rsx_task_lookahead_policy",
+    "rsx_task_collect_policy",
 )
 # activations of rsx_policy_mlp (include/rsx.h: RSX_ACT_*)
 ACT_RELU, ACT_TANH, ACT_CLIP = 0, 1, 2
@@ -69,6 +70,12 @@ class PlanSampler(C.Structure):
 class PolicyMLP(C.Structure):
     """rsx_policy_mlp (include/rsx.h): the shape of the policies of rsx_task_lookahead_policy"""
     _fields_ = [("n_hidden_layers", C.c_int32), ("hidden", C.c_int32), ("hidden_act", C.c_int32), ("out_act", C.c_int32)]
+
+
+class CollectOut(C.Structure):
+    """rsx_collect_out (include/rsx.h): the [T][B] record of rsx_task_collect_policy; device addresses, the last three may be None"""
+    _fields_ = [("obs", C.c_void_p), ("actions", C.c_void_p), ("rewards", C.c_void_p), ("flags", C.c_void_p),
+                ("final_obs", C.c_void_p), ("mean", C.c_void_p), ("sample", C.c_void_p)]
 
 
 class DevView(C.Structure):
@@ -169,6 +176,7 @@ def load():
     lib.rsx_plan_update.argtypes = [vp, vp, C.POINTER(PlanSampler), ip, ip, vp, C.c_float, vp, vp, vp]
     lib.rsx_policy_num_params.argtypes = [vp, C.POINTER(PolicyMLP), C.POINTER(C.c_int64)]
     lib.rsx_task_lookahead_policy.argtypes = [vp, C.POINTER(PolicyMLP), vp, ip, ip, C.c_float, vp, vp, vp, vp, vp, vp, vp]
+    lib.rsx_task_collect_policy.argtypes = [vp, C.POINTER(PolicyMLP), vp, vp, C.c_uint64, ip, C.POINTER(CollectOut), vp]
     lib.rsx_physics_defaults.argtypes = [ip, vp]
     lib.rsx_physics_derive.argtypes = [ip, ip, vp, vp]
     lib.rsx_physics_enable.argtypes = [vp, vp]
@@ -513,6 +521,15 @@ class Sim:
         rc = self._lib.rsx_task_lookahead_policy(self._h, None if spec is None else C.byref(spec), params_ptr, int(n_policies), int(horizon),
                                                  float(gamma), returns_ptr, steps_ptr, flags_ptr, last_obs_ptr, actions_out_ptr, obs_out_ptr,
                                                  stream)
+        if rc:
+            _chk(rc)
+
+    def task_collect_policy(self, spec, params_ptr, sigma_ptr, noise_seed, n_steps, out, stream=None):
+        """rsx_task_collect_policy: ``n_steps`` steps of the handle's envs under MLP policy ``spec`` (a PolicyMLP, or None to pass
+        NULL; params [P] f32) in one launch, with auto-reset; ``out``: a CollectOut of device addresses ([T][B] records), or None to
+        pass NULL.  ``sigma_ptr``: [act_dim] f32 device address of the Gaussian head's standard deviations, or None = deterministic."""
+        rc = self._lib.rsx_task_collect_policy(self._h, None if spec is None else C.byref(spec), params_ptr, sigma_ptr,
+                                               int(noise_seed) & 0xFFFFFFFFFFFFFFFF, int(n_steps), None if out is None else C.byref(out), stream)
         if rc:
             _chk(rc)
 

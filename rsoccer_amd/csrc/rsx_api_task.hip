@@ -360,6 +360,38 @@ int rsx_task_lookahead_policy(rsx_sim* h, const rsx_policy_mlp* p, const float* 
     return RSX_OK;
 }
 
+// ---- on-policy collection: n steps under the policy in one launch, the [T][B] batch written out (rsx.h: rsx_task_collect_policy) ----
+int rsx_task_collect_policy(rsx_sim* h, const rsx_policy_mlp* p, const float* params_dev, const float* sigma_dev, uint64_t noise_seed,
+                            int n_steps, const rsx_collect_out* out, void* stream) {
+    RSX_ENTER(h);
+    PolicySpec S; int64_t n_params = 0;
+    if (int rc = policy_prologue(h, p, &S, &n_params)) return rc;
+    RSX_NEED_RESET(h);
+    if (n_steps < 1 || n_steps > RSX_N_STEPS_MASK) return fail(RSX_ERR_ARG, "n_steps must be in 1 .. 2^30 - 1");
+    if (!params_dev) return fail(RSX_ERR_ARG, "params_dev must not be null");
+    if (!out || !out->obs || !out->actions || !out->rewards || !out->flags)
+        return fail(RSX_ERR_ARG, "out and its obs, actions, rewards and flags arrays must not be null");
+    if (h->L > 32) return fail(RSX_ERR_ARG, "rsx_task_collect_policy has no 64-lanes-per-env kernels (unset RSX_LANES_PER_ENV)");
+    if (policy_lds_bytes(h->L, h->P.obs_dim, h->M.act_dim, S) > 65536ll)
+        return fail(RSX_ERR_ARG, "the policy's weights do not fit a workgroup's 64 KB of LDS at this observation width: use fewer or smaller hidden layers");
+    hipStream_t s = (hipStream_t)stream;
+    int fl = 0;
+    if (int rc = step_prologue(h, s, (uint64_t)n_steps, &fl)) return rc;   // capture of a host-keyed handle, counter limit
+    h->host_state_valid = false;   // (from here on the call changes the state, as every stepping call does)
+    // device-keyed handles: the launch reads, checks and advances the slots of its lane_grid workgroups.  Where the handle's steps run
+    // on a smaller grid (one lane per env), the slots behind that grid are not kept in sync by them: they follow slot 0 first
+    const int grid = grid_for(h);
+    if (h->tick_dev) launch_tick_fill(tick_slot0(h), h->tick_slots, grid, 0u, 1, s);
+    h->P.tick_base = h->tick; h->tick += (uint32_t)n_steps;
+    launch_task_collect_policy(h->P, buffers_of(h, nullptr), h->L, h->NR, h->d_phys, S, params_dev, (int)n_params, h->M.act_dim, sigma_dev,
+                               noise_seed, n_steps | fl, out->obs, out->actions, out->rewards, out->flags, out->final_obs, out->mean,
+                               out->sample, s);
+    // ... and the slots the launch did not cover (placement helpers behind the tiles) follow slot 0 afterwards, as after a rollout
+    if (h->tick_dev) launch_tick_fill(tick_slot0(h), grid, h->tick_slots, 0u, 1, s);
+    HIP_TRY(launch_status());
+    return debug_finite(h, s, "rsx_task_collect_policy");
+}
+
 // ---- planning with candidates drawn on the device (rsx.h: rsx_plan_sampler) ----
 // what the three calls check alike; on success S is the sampler as the kernels take it and P the handle's parameters with the step
 // counter the next step would take (not advanced).  n_steps: what the counter limit is checked against (0: the call simulates nothing)

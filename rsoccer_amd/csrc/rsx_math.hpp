@@ -153,6 +153,9 @@ constexpr uint32_t DOM_PHYS = 5u;
 // PLAN: the perturbations of sampled planning candidates (rsx_plan_common.hpp), counter (env, candidate, tick, PLAN | block << 8), keyed
 // by the call's sample_seed, not the handle's seed
 constexpr uint32_t DOM_PLAN = 6u;
+// POLICY: the noise of the collector's Gaussian policy head (rsx_collect.hip), counter (env, 0, tick, POLICY | block << 8), keyed by the
+// call's noise_seed, not the handle's seed
+constexpr uint32_t DOM_POLICY = 7u;
 
 // 24-bit uniform in [0, 1)
 __device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * 5.9604644775390625e-08f; }

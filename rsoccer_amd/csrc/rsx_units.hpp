@@ -78,6 +78,13 @@ void launch_task_lookahead_policy(const Params& P, int L, int NR, const float* s
                                   const float* phys, const PolicySpec& p, const float* params, int n_params, int act_dim, int n_policies,
                                   int horizon, float gamma, float* returns, int32_t* steps, uint8_t* flags, float* last_obs,
                                   float* actions_out, float* obs_out, hipStream_t s);
+// rsx_collect.hip: on-policy collection (rsx_task_collect_policy): n_steps fused steps with auto-reset in one launch on the handle's own
+// buffers `b` (as a rollout: state, scalars, obs, flags, metrics and the tick slots of the lane_grid workgroups are advanced), each step's
+// action computed by the policy (one parameter vector [n_params]) and, with sigma [act_dim] non-null, perturbed by Gaussian noise keyed by
+// noise_seed.  obs / actions / rewards / flags: the [n_steps][num_envs] record; final_obs / mean / sample: optional.  LDS: policy_lds_bytes
+void launch_task_collect_policy(const Params& P, const Buffers& b, int L, int NR, float* phys, const PolicySpec& p, const float* params,
+                                int n_params, int act_dim, const float* sigma, uint64_t noise_seed, int n_steps, float* obs, float* actions,
+                                float* rewards, uint8_t* flags, float* final_obs, float* mean, float* sample, hipStream_t s);
 // rsx_render.hip: batched rgb frames (rsx_render_*).  render_check_view: nullptr when the view is valid (and the frame size), else the
 // message; render_field_host: the static field image [H][W][3]; RenderGeom: what the kernel needs of a view, in float32
 struct RenderGeom { int W, H; float s, cx, cy, r, rb; int square; };

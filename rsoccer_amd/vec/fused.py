@@ -257,6 +257,92 @@ class VecFusedEnv(RenderMixin):
             out["policy_obs"] = pobs
         return out
 
+    def collect(self, policy, params, steps, log_std=None, noise_seed=None, iteration=0, return_final_obs=False):
+        """Advance the envs ``steps`` steps under an MLP policy in ONE launch and return the on-policy batch
+        (``rsx_task_collect_policy``): what a PPO / A2C loop calls between two updates.
+
+        ``policy``: an ``rsoccer_amd.vec.policy.MLPPolicy`` for this env's ``obs_dim`` / ``act_dim``; ``params``: ``[P]`` float32, its
+        flat parameters (``MLPPolicy.pack`` / ``from_module``).  Step 0 answers the env's current ``obs``; episode ends are handled
+        inside the launch (same-step auto-reset), and row ``t + 1`` of ``obs`` for an env that ended at ``t`` is the first
+        observation of its next episode.  The env ends up exactly where ``steps`` calls of ``step(out["actions"][t])`` leave it —
+        state, counters, metrics and checkpoint, bit for bit.
+
+        ``log_std``: ``[act_dim]`` (or a scalar) — the log standard deviations of a Gaussian head: ``sample = mean + exp(log_std) * eps``
+        and ``action = out_act(sample)``, where ``mean`` is the output layer BEFORE ``out_act``.  ``None``: deterministic
+        (``sample = mean``).  ``eps`` is keyed by ``noise_seed``, the global env id and the step counter; ``noise_seed`` defaults to a
+        64-bit mix (splitmix64) of the env's seed and ``iteration``, the way ``plan()`` derives its sample seed — pass the update's
+        index as ``iteration``.  A ``log_std`` given as host data (float, list, numpy) must be finite; a device tensor is not
+        checked (that would synchronise).
+
+        Returns a dict of fresh caller-owned device tensors (``T = steps``, ``B = num_envs``): ``obs`` ``[T, B, obs_dim]`` — the
+        observation each action answered, ``actions`` ``[T, B, act_dim]``, ``reward`` ``[T, B]``, ``terminated`` / ``truncated``
+        ``[T, B]`` bool, and ``next_obs`` — the env's ``obs`` VIEW after the call, for the bootstrap value.  With
+        ``return_final_obs=True`` also ``final_obs`` ``[T, B, obs_dim]``: zeros, except at ended rows the terminal observation.  With
+        ``log_std`` also ``mean``, ``sample`` ``[T, B, act_dim]`` and ``log_prob`` ``[T, B]``: the density of ``sample`` under
+        ``N(mean, exp(log_std))`` summed over the components, computed in torch — the PRE-``out_act`` density (no tanh / clip
+        correction; it cancels in PPO's ratio as long as the trainer evaluates the same pre-activation density).
+        Capturable into a ``torch.cuda.CUDAGraph`` after ``enable_graph_capture()``: every replay draws fresh noise."""
+        torch = self._torch
+        from rsoccer_amd.vec.policy import MLPPolicy
+        if not isinstance(policy, MLPPolicy):
+            raise ValueError("policy must be an rsoccer_amd.vec.policy.MLPPolicy")
+        T = int(steps)
+        if T < 1:
+            raise ValueError(f"steps must be >= 1, got {steps}")
+        if self.sim.act_dim != policy.act_dim or self.sim.obs_dim != policy.obs_dim:
+            raise ValueError(f"the policy maps {policy.obs_dim} -> {policy.act_dim}, the env {self.sim.obs_dim} -> {self.sim.act_dim}")
+        shape = tuple(np.shape(params))   # checked on the INPUT, as lookahead_policy() checks its parameters
+        if shape != (policy.num_params,):
+            raise ValueError(f"params must be [{policy.num_params}] (one policy), got {shape}")
+        dev, B, OD, AD = self.device, self.num_envs, self.sim.obs_dim, self.sim.act_dim
+        if isinstance(params, torch.Tensor):
+            p = params.detach()
+            if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
+                p = p.to(device=dev, dtype=torch.float32).contiguous()
+        else:
+            p = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float32)).to(dev)
+        ls = sigma = None
+        if log_std is not None:
+            if isinstance(log_std, torch.Tensor):
+                ls = log_std.detach().to(device=dev, dtype=torch.float32)
+            else:
+                host = np.asarray(log_std, dtype=np.float32)
+                if not np.all(np.isfinite(host)):
+                    raise ValueError("log_std must be finite")
+                ls = torch.from_numpy(np.array(host, dtype=np.float32, copy=True)).to(dev)   # (keeps a scalar 0-dimensional)
+            if ls.dim() == 0:
+                ls = ls.expand(AD)
+            if tuple(ls.shape) != (AD,):
+                raise ValueError(f"log_std must be a scalar or [{AD}], got {tuple(ls.shape)}")
+            sigma = ls.exp().contiguous()
+        if noise_seed is None:
+            m = (1 << 64) - 1   # splitmix64 of (seed, iteration), as _plan_sampler
+            z = (self._seed + 0x9E3779B97F4A7C15 * (int(iteration) + 1)) & m
+            z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+            z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+            noise_seed = z ^ (z >> 31)
+        f32 = dict(dtype=torch.float32, device=dev)
+        obs = torch.empty((T, B, OD), **f32)
+        acts = torch.empty((T, B, AD), **f32)
+        rew = torch.empty((T, B), **f32)
+        flags = torch.empty((T, B), dtype=torch.uint8, device=dev)
+        fobs = torch.zeros((T, B, OD), **f32) if return_final_obs else None
+        mean = torch.empty((T, B, AD), **f32) if sigma is not None else None
+        smp = torch.empty((T, B, AD), **f32) if sigma is not None else None
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        rec = _lib.CollectOut(ptr(obs), ptr(acts), ptr(rew), ptr(flags), ptr(fobs), ptr(mean), ptr(smp))
+        self.sim.task_collect_policy(policy.spec(), p.data_ptr(), ptr(sigma), noise_seed, T, rec, self._stream())
+        self._keep_plan = (p, sigma)   # alive until the launch has consumed them
+        out = {"obs": obs, "actions": acts, "reward": rew, "terminated": (flags & 1).bool(), "truncated": (flags & 2).bool(),
+               "next_obs": self._t["obs"]}
+        if return_final_obs:
+            out["final_obs"] = fobs
+        if sigma is not None:
+            out["mean"], out["sample"] = mean, smp
+            z = (smp - mean) / sigma
+            out["log_prob"] = (-0.5 * z * z - ls - 0.9189385332046727).sum(-1)   # 0.5 * log(2 pi)
+        return out
+
     # ---- planning with candidates drawn on the device (include/rsx.h: rsx_plan_sampler) ----
     def _plan_sampler(self, sigma, hold, seed, iteration):
         """the rsx_plan_sampler of a call: ``sample_seed`` is a 64-bit mix (splitmix64) of ``seed`` (default: the env's) and
