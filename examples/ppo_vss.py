@@ -3,11 +3,12 @@
     python examples/ppo_vss.py [--envs 1024] [--steps 128] [--updates 10] [--epochs 4] [--minibatches 4] [--lr 3e-4]
 
 One update: env.collect(...) advances the envs `steps` steps under the current actor — the MLP evaluated inside the engine's launch, a
-Gaussian head on top, episode ends handled in the launch — and returns the [T, B] batch; the critic (a torch module the engine never
-sees) is evaluated on the recorded observations, advantages are GAE, and a few epochs of clipped PPO follow in torch.  The actor's
-weights reach the engine as one flat vector (MLPPolicy.from_module: torch's own layout).  The density PPO compares is the
-pre-activation one: log N(sample; mean, exp(log_std)), where the action fed to the env is clip(sample) — the trainer evaluates the
-same expression on the recorded `sample`, so the ratio is exact.  A demonstration of the call pattern, not a tuned trainer."""
+Gaussian head on top, episode ends handled in the launch — and, given the critic, evaluates it on the recorded observations and runs
+the GAE recurrence in two more launches (env.advantages: a terminated row bootstraps from 0, a truncated one from the value of its
+terminal observation), returning the [T, B] batch with `value`, `advantage` and `return`; a few epochs of clipped PPO follow in torch.
+The actor's and the critic's weights reach the engine as flat vectors (MLPPolicy / MLPCritic.from_module: torch's own layout).  The
+density PPO compares is the pre-activation one: log N(sample; mean, exp(log_std)), where the action fed to the env is clip(sample) —
+the trainer evaluates the same expression on the recorded `sample`, so the ratio is exact.  A demonstration of the call pattern, not a tuned trainer."""
 import argparse
 import os
 import sys
@@ -17,7 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from rsoccer_amd.vec import VecVSSEnv
-from rsoccer_amd.vec.policy import MLPPolicy
+from rsoccer_amd.vec.policy import MLPCritic, MLPPolicy
 
 
 def log_prob(mean, log_std, sample):
@@ -43,6 +44,7 @@ def main():
     env = VecVSSEnv(args.envs, device=0, seed=args.seed)
     dev, OD, AD = env.device, env.sim.obs_dim, env.sim.act_dim
     pol = MLPPolicy(OD, AD, hidden=64, layers=2, hidden_act="tanh", out_act="clip")
+    val = MLPCritic(OD, hidden=64, layers=2, hidden_act="tanh")
     # the actor WITHOUT its output activation: the engine applies the clip to the noisy sample, the trainer needs the mean
     actor = torch.nn.Sequential(torch.nn.Linear(OD, 64), torch.nn.Tanh(), torch.nn.Linear(64, 64), torch.nn.Tanh(), torch.nn.Linear(64, AD)).to(dev)
     critic = torch.nn.Sequential(torch.nn.Linear(OD, 64), torch.nn.Tanh(), torch.nn.Linear(64, 64), torch.nn.Tanh(), torch.nn.Linear(64, 1)).to(dev)
@@ -52,20 +54,10 @@ def main():
     env.reset()
     for update in range(args.updates):
         t0 = time.perf_counter()
-        batch = env.collect(pol, pol.from_module(actor), T, log_std=log_std, iteration=update)
-        with torch.no_grad():
-            done = batch["terminated"] | batch["truncated"]
-            values = critic(batch["obs"]).squeeze(-1)                      # [T, B]
-            nxt = torch.cat([values[1:], critic(batch["next_obs"]).squeeze(-1)[None]])
-            # an ended row bootstraps nothing (a truncated one could bootstrap from return_final_obs=True's rows; kept simple here)
-            delta = batch["reward"] + args.gamma * nxt * (~done) - values
-            adv = torch.zeros_like(delta)
-            run = torch.zeros(B, device=dev)
-            for t in reversed(range(T)):
-                run = delta[t] + args.gamma * args.lam * (~done[t]) * run
-                adv[t] = run
-            ret = adv + values
-            adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+        batch = env.collect(pol, pol.from_module(actor), T, log_std=log_std, iteration=update,
+                            critic=val, critic_params=val.from_module(critic), gamma=args.gamma, lam=args.lam)
+        ret, adv = batch["return"], batch["advantage"]
+        adv = (adv - adv.mean()) / (adv.std() + 1e-8)
         torch.cuda.synchronize()
         t_collect = time.perf_counter() - t0
         flat = {k: batch[k].reshape(T * B, -1) for k in ("obs", "sample")}

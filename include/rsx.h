@@ -521,6 +521,62 @@ int rsx_task_collect_policy(rsx_sim* h, const rsx_policy_mlp* p, const float* pa
                             const float* sigma_dev /* [act_dim] >= 0, or NULL = deterministic */, uint64_t noise_seed,
                             int n_steps, const rsx_collect_out* out, void* stream);
 
+/* ---- values and GAE advantages of a collected batch (additive extension of ABI 6) ------------------------------------------------
+ * What an on-policy trainer does between rsx_task_collect_policy and its gradient step: evaluate a critic on the [T][B] batch and run
+ * the reverse recurrence of generalised advantage estimation — two launches instead of a torch critic plus a Python loop over T.
+ *   the handle       supplies only the device, obs_dim and the error string: the call reads and writes NOTHING of the envs, works on any
+ *                    handle with a task attached, before or after rsx_task_reset, and needs no step counter — host-keyed and
+ *                    device-keyed handles both capture.
+ *   critic           an rsx_policy_mlp with act_dim = 1 and out_act = RSX_ACT_NONE (a linear output); critic_params_dev [P] in
+ *                    rsx_policy_mlp's layout with act_dim = 1: W1 [hidden][obs_dim], b1, (W2, b2,) Wo [1][hidden], bo [1];
+ *                    P = rsx_critic_num_params (rsx_policy_num_params counts a policy of the TASK's act_dim and keeps refusing
+ *                    RSX_ACT_NONE, so the critic has a call of its own).
+ *   terminated, truncated   separate byte arrays, non-zero = true: the bool tensors of a collected batch and the flag tensors of a
+ *                    stepping loop both go in as they are.  n_envs is the batch's B, any >= 1 (not the handle's num_envs).
+ * The arithmetic is fixed, all float32, the unit is built with -ffp-contract=off:
+ *   V(x)             the critic's output accumulator in exactly rsx_policy_mlp's order: per unit acc = bias; for i ascending:
+ *                    acc = fmaf(W[j][i], x[i], acc); hidden activations as there; no activation on the output.  Hence, for a critic
+ *                    that shares its hidden layers with an actor and whose output row is the actor's output row 0, values[t][e]
+ *                    equals rsx_collect_out.mean[t][e][0] bit for bit.
+ *   end              terminated || truncated
+ *   nv               terminated: 0;  truncated only: V(final_obs[t][e]), or 0 when final_obs == NULL;  otherwise values[t + 1][e]
+ *                    for t < T - 1 and V(last_obs[e]) for the last row.  (With same-step auto-reset obs[t + 1] of an env that ended
+ *                    at t belongs to the next episode: the bootstrap of a time limit comes from the terminal observation.)
+ *   delta            (r + gamma * nv) - v: one multiplication, one addition, one subtraction, each rounded
+ *   adv              end ? delta : delta + gl * adv_next, with adv_next = 0 behind the last row and gl = (float)gamma * (float)lam,
+ *                    computed once on the host
+ *   ret              adv + v
+ * Selection is by select, never by a multiplication with 0: final_obs rows that were never written and the carried advantage of an
+ * ended row (NaN included) reach no output.
+ * The call owns no memory: V(last_obs) passes through row T - 1 of `advantages` and V(final_obs) through the truncated-only rows of
+ * `returns` before those rows receive their results, so the three required outputs must not overlap each other or an input.
+ * RSX_GAE_FORM=groups in the environment evaluates the critic eight lanes per row as the collector does (the same bits; the default is
+ * one row per lane, profiles/LABBOOK.md has the comparison).
+ * Stream-ordered, never synchronises, never allocates, capturable.  Refusals (nothing is enqueued, rsx_last_error says why), all
+ * RSX_ERR_ARG: a null critic, critic_params_dev, in, out or required array; n_steps < 1 or n_envs < 1; gamma or lam non-finite or
+ * outside [0, 1]; n_hidden_layers, hidden or hidden_act outside rsx_policy_mlp's listed values; out_act != RSX_ACT_NONE; a handle
+ * without a task; a critic whose weights and hidden rows do not fit a workgroup's 64 KB of LDS (2 x 64 units fit every observation a
+ * task can have). */
+#define RSX_ACT_NONE 3   /* identity: accepted as out_act by rsx_task_advantages ONLY; every other call keeps refusing it */
+typedef struct rsx_adv_in {
+    const float*   obs;         /* [T][B][obs_dim]   required */
+    const float*   rewards;     /* [T][B]            required */
+    const uint8_t* terminated;  /* [T][B] non-zero = true   required */
+    const uint8_t* truncated;   /* [T][B] non-zero = true   required */
+    const float*   final_obs;   /* [T][B][obs_dim] or NULL; read ONLY in rows truncated && !terminated */
+    const float*   last_obs;    /* [B][obs_dim]: the observation after step T - 1   required */
+} rsx_adv_in;
+typedef struct rsx_adv_out {
+    float* values;       /* [T][B] V(obs[t])                       required */
+    float* advantages;   /* [T][B]                                 required */
+    float* returns;      /* [T][B] advantages + values             required */
+    float* next_values;  /* [T][B] or NULL: the value row t bootstrapped from */
+} rsx_adv_out;
+int rsx_critic_num_params(const rsx_sim* h, const rsx_policy_mlp* critic, int64_t* out);
+int rsx_task_advantages(rsx_sim* h, const rsx_policy_mlp* critic, const float* critic_params_dev /* [P] with act_dim = 1 */,
+                        float gamma, float lam, int n_steps /* T */, int n_envs /* B, any >= 1 */,
+                        const rsx_adv_in* in, const rsx_adv_out* out, void* stream);
+
 /* Debugging aid: number of non-finite floats in the state rows and, with a task attached, in the
  * observations, rewards and info rows.  Synchronises `stream`.  With RSX_DEBUG_FINITE=1 in the
  * environment every stepping call (rsx_step_dev, rsx_task_step, rsx_task_step_n, rsx_task_rollout, rsx_task_collect_policy)

@@ -53,9 +53,11 @@ SYMBOLS = (
     "rsx_task_lookahead_sampled", "rsx_plan_candidates", "rsx_plan_update",
     "rsx_policy_num_params", "rsx_task_lookahead_policy",
     "rsx_task_collect_policy",
+    "rsx_critic_num_params", "rsx_task_advantages",
 )
 # activations of rsx_policy_mlp (include/rsx.h: RSX_ACT_*)
 ACT_RELU, ACT_TANH, ACT_CLIP = 0, 1, 2
+ACT_NONE = 3   # identity: the output of a critic (rsx_task_advantages only)
 
 
 class RsxError(RuntimeError):
@@ -76,6 +78,17 @@ class CollectOut(C.Structure):
     """rsx_collect_out (include/rsx.h): the [T][B] record of rsx_task_collect_policy; device addresses, the last three may be None"""
     _fields_ = [("obs", C.c_void_p), ("actions", C.c_void_p), ("rewards", C.c_void_p), ("flags", C.c_void_p),
                 ("final_obs", C.c_void_p), ("mean", C.c_void_p), ("sample", C.c_void_p)]
+
+
+class AdvIn(C.Structure):
+    """rsx_adv_in (include/rsx.h): the [T][B] batch rsx_task_advantages reads; device addresses, final_obs may be None"""
+    _fields_ = [("obs", C.c_void_p), ("rewards", C.c_void_p), ("terminated", C.c_void_p), ("truncated", C.c_void_p),
+                ("final_obs", C.c_void_p), ("last_obs", C.c_void_p)]
+
+
+class AdvOut(C.Structure):
+    """rsx_adv_out (include/rsx.h): the [T][B] results of rsx_task_advantages; device addresses, next_values may be None"""
+    _fields_ = [("values", C.c_void_p), ("advantages", C.c_void_p), ("returns", C.c_void_p), ("next_values", C.c_void_p)]
 
 
 class DevView(C.Structure):
@@ -177,6 +190,8 @@ def load():
     lib.rsx_policy_num_params.argtypes = [vp, C.POINTER(PolicyMLP), C.POINTER(C.c_int64)]
     lib.rsx_task_lookahead_policy.argtypes = [vp, C.POINTER(PolicyMLP), vp, ip, ip, C.c_float, vp, vp, vp, vp, vp, vp, vp]
     lib.rsx_task_collect_policy.argtypes = [vp, C.POINTER(PolicyMLP), vp, vp, C.c_uint64, ip, C.POINTER(CollectOut), vp]
+    lib.rsx_critic_num_params.argtypes = [vp, C.POINTER(PolicyMLP), C.POINTER(C.c_int64)]
+    lib.rsx_task_advantages.argtypes = [vp, C.POINTER(PolicyMLP), vp, C.c_float, C.c_float, ip, ip, C.POINTER(AdvIn), C.POINTER(AdvOut), vp]
     lib.rsx_physics_defaults.argtypes = [ip, vp]
     lib.rsx_physics_derive.argtypes = [ip, ip, vp, vp]
     lib.rsx_physics_enable.argtypes = [vp, vp]
@@ -530,6 +545,22 @@ class Sim:
         pass NULL.  ``sigma_ptr``: [act_dim] f32 device address of the Gaussian head's standard deviations, or None = deterministic."""
         rc = self._lib.rsx_task_collect_policy(self._h, None if spec is None else C.byref(spec), params_ptr, sigma_ptr,
                                                int(noise_seed) & 0xFFFFFFFFFFFFFFFF, int(n_steps), None if out is None else C.byref(out), stream)
+        if rc:
+            _chk(rc)
+
+    def critic_num_params(self, spec):
+        """rsx_critic_num_params: floats of one critic of shape ``spec`` (a PolicyMLP with out_act = ACT_NONE) on this handle's task"""
+        n = C.c_int64(0)
+        _chk(self._lib.rsx_critic_num_params(self._h, None if spec is None else C.byref(spec), C.byref(n)))
+        return int(n.value)
+
+    def task_advantages(self, spec, params_ptr, gamma, lam, n_steps, n_envs, inp, out, stream=None):
+        """rsx_task_advantages: values of critic ``spec`` (a PolicyMLP with out_act = ACT_NONE, or None to pass NULL; params [P] f32
+        with act_dim = 1) on a [T][B] batch and its GAE advantages and returns, in two launches.  ``inp``: an AdvIn, ``out``: an AdvOut
+        of device addresses (None passes NULL).  Reads and writes nothing of the envs."""
+        rc = self._lib.rsx_task_advantages(self._h, None if spec is None else C.byref(spec), params_ptr, float(gamma), float(lam),
+                                           int(n_steps), int(n_envs), None if inp is None else C.byref(inp),
+                                           None if out is None else C.byref(out), stream)
         if rc:
             _chk(rc)
 

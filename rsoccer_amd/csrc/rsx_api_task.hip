@@ -392,6 +392,51 @@ int rsx_task_collect_policy(rsx_sim* h, const rsx_policy_mlp* p, const float* pa
     return debug_finite(h, s, "rsx_task_collect_policy");
 }
 
+// ---- values and GAE advantages of a [T][B] batch (rsx.h: rsx_task_advantages).  The handle gives the device and obs_dim; nothing of it is touched ----
+// what both calls check of a critic; on success S is the spec as the kernels take it and *n_params the floats of one critic
+static int critic_prologue(const rsx_sim* h, const rsx_policy_mlp* c, PolicySpec* S, int64_t* n_params) {
+    if (h->P.task == RSX_TASK_NONE) return fail(RSX_ERR_ARG, "no task attached (rsx_task_attach): the critic's obs_dim is the task's");
+    if (!c) return fail(RSX_ERR_ARG, "the critic (rsx_policy_mlp) must not be null");
+    if (c->n_hidden_layers != 1 && c->n_hidden_layers != 2) return fail(RSX_ERR_ARG, "n_hidden_layers must be 1 or 2");
+    if (c->hidden != 32 && c->hidden != 64) return fail(RSX_ERR_ARG, "hidden must be 32 or 64");
+    if (c->hidden_act != RSX_ACT_RELU && c->hidden_act != RSX_ACT_TANH) return fail(RSX_ERR_ARG, "hidden_act must be RSX_ACT_RELU or RSX_ACT_TANH");
+    if (c->out_act != RSX_ACT_NONE) return fail(RSX_ERR_ARG, "a critic's out_act must be RSX_ACT_NONE (a linear output)");
+    *S = PolicySpec{c->n_hidden_layers, c->hidden, c->hidden_act, c->out_act};
+    const int64_t H = c->hidden;
+    *n_params = H * h->P.obs_dim + H + (c->n_hidden_layers == 2 ? H * H + H : 0) + H + 1;
+    return RSX_OK;
+}
+
+int rsx_critic_num_params(const rsx_sim* h, const rsx_policy_mlp* critic, int64_t* out) {
+    if (!h) return fail(RSX_ERR_ARG, "null handle");
+    if (!out) return fail(RSX_ERR_ARG, "out must not be null");
+    PolicySpec S;
+    return critic_prologue(h, critic, &S, out);
+}
+
+int rsx_task_advantages(rsx_sim* h, const rsx_policy_mlp* critic, const float* critic_params_dev, float gamma, float lam, int n_steps,
+                        int n_envs, const rsx_adv_in* in, const rsx_adv_out* out, void* stream) {
+    RSX_ENTER(h);   // (nothing the handle owns is read or written by the launches)
+    PolicySpec S; int64_t n_params = 0;
+    if (int rc = critic_prologue(h, critic, &S, &n_params)) return rc;
+    if (n_steps < 1 || n_envs < 1) return fail(RSX_ERR_ARG, "n_steps and n_envs must be >= 1");
+    if (!(std::isfinite(gamma) && gamma >= 0.0f && gamma <= 1.0f)) return fail(RSX_ERR_ARG, "gamma must be in [0, 1]");
+    if (!(std::isfinite(lam) && lam >= 0.0f && lam <= 1.0f)) return fail(RSX_ERR_ARG, "lam must be in [0, 1]");
+    if (!critic_params_dev) return fail(RSX_ERR_ARG, "critic_params_dev must not be null");
+    if (!in || !in->obs || !in->rewards || !in->terminated || !in->truncated || !in->last_obs)
+        return fail(RSX_ERR_ARG, "in and its obs, rewards, terminated, truncated and last_obs arrays must not be null");
+    if (!out || !out->values || !out->advantages || !out->returns)
+        return fail(RSX_ERR_ARG, "out and its values, advantages and returns arrays must not be null");
+    const char* form_env = std::getenv("RSX_GAE_FORM");
+    const int form = form_env && std::strcmp(form_env, "groups") == 0 ? GAE_FORM_GROUPS : GAE_FORM_ROWS;
+    if (gae_lds_bytes(form, h->P.obs_dim, S) > 65536ll)
+        return fail(RSX_ERR_ARG, "the critic's weights do not fit a workgroup's 64 KB of LDS at this observation width: use fewer or smaller hidden layers");
+    const float gl = gamma * lam;   // (one rounding; the unit is built with -ffp-contract=off like every other)
+    launch_advantages(form, S, critic_params_dev, h->P.obs_dim, gamma, gl, n_steps, n_envs, *in, *out, (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
 // ---- planning with candidates drawn on the device (rsx.h: rsx_plan_sampler) ----
 // what the three calls check alike; on success S is the sampler as the kernels take it and P the handle's parameters with the step
 // counter the next step would take (not advanced).  n_steps: what the counter limit is checked against (0: the call simulates nothing)

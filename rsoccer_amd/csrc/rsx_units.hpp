@@ -6,6 +6,8 @@
 #include <cstdint>
 
 struct rsx_render_view;   // include/rsx.h
+struct rsx_adv_in;
+struct rsx_adv_out;
 
 namespace rsx {
 
@@ -85,6 +87,15 @@ void launch_task_lookahead_policy(const Params& P, int L, int NR, const float* s
 void launch_task_collect_policy(const Params& P, const Buffers& b, int L, int NR, float* phys, const PolicySpec& p, const float* params,
                                 int n_params, int act_dim, const float* sigma, uint64_t noise_seed, int n_steps, float* obs, float* actions,
                                 float* rewards, uint8_t* flags, float* final_obs, float* mean, float* sample, hipStream_t s);
+// rsx_gae.hip: values and GAE advantages of a [T][B] batch (rsx_task_advantages).  critic: rsx_policy_mlp with act_dim = 1 and a linear
+// output, checked; params: [P]; gl: (float)gamma * (float)lam; in / out: the call's arrays, checked.  Two launches: the critic over
+// T * B + B rows (and the rows truncated only of final_obs), then the reverse scan.  form: which values kernel (GAE_FORM_ROWS: one row per
+// lane, the default; GAE_FORM_GROUPS: eight lanes per row, the collector's policy_forward — the same bits).  gae_lds_bytes: LDS of one
+// workgroup of the values launch (the host refuses more than 64 KB)
+enum : int { GAE_FORM_ROWS = 0, GAE_FORM_GROUPS = 1 };
+long long gae_lds_bytes(int form, int obs_dim, const PolicySpec& critic);
+void launch_advantages(int form, const PolicySpec& critic, const float* params, int obs_dim, float gamma, float gl, int T, int B,
+                       const rsx_adv_in& in, const rsx_adv_out& out, hipStream_t s);
 // rsx_render.hip: batched rgb frames (rsx_render_*).  render_check_view: nullptr when the view is valid (and the frame size), else the
 // message; render_field_host: the static field image [H][W][3]; RenderGeom: what the kernel needs of a view, in float32
 struct RenderGeom { int W, H; float s, cx, cy, r, rb; int square; };

@@ -257,7 +257,8 @@ class VecFusedEnv(RenderMixin):
             out["policy_obs"] = pobs
         return out
 
-    def collect(self, policy, params, steps, log_std=None, noise_seed=None, iteration=0, return_final_obs=False):
+    def collect(self, policy, params, steps, log_std=None, noise_seed=None, iteration=0, return_final_obs=False,
+                critic=None, critic_params=None, gamma=0.99, lam=0.95):
         """Advance the envs ``steps`` steps under an MLP policy in ONE launch and return the on-policy batch
         (``rsx_task_collect_policy``): what a PPO / A2C loop calls between two updates.
 
@@ -281,6 +282,9 @@ class VecFusedEnv(RenderMixin):
         ``log_std`` also ``mean``, ``sample`` ``[T, B, act_dim]`` and ``log_prob`` ``[T, B]``: the density of ``sample`` under
         ``N(mean, exp(log_std))`` summed over the components, computed in torch — the PRE-``out_act`` density (no tanh / clip
         correction; it cancels in PPO's ratio as long as the trainer evaluates the same pre-activation density).
+        With ``critic`` (an ``MLPCritic``) and ``critic_params`` the batch also carries ``value``, ``advantage`` and ``return``
+        ``[T, B]``: ``advantages(batch, critic, critic_params, gamma, lam)`` on the batch just collected (``final_obs`` is then always
+        recorded and returned).  Without a critic the returned dict and the launches are what they were.
         Capturable into a ``torch.cuda.CUDAGraph`` after ``enable_graph_capture()``: every replay draws fresh noise."""
         torch = self._torch
         from rsoccer_amd.vec.policy import MLPPolicy
@@ -291,6 +295,11 @@ class VecFusedEnv(RenderMixin):
             raise ValueError(f"steps must be >= 1, got {steps}")
         if self.sim.act_dim != policy.act_dim or self.sim.obs_dim != policy.obs_dim:
             raise ValueError(f"the policy maps {policy.obs_dim} -> {policy.act_dim}, the env {self.sim.obs_dim} -> {self.sim.act_dim}")
+        if critic is not None:
+            cp = self._critic_args(critic, critic_params, gamma, lam)   # (refused before anything is enqueued)
+            return_final_obs = True
+        elif critic_params is not None:
+            raise ValueError("critic_params given without a critic")
         shape = tuple(np.shape(params))   # checked on the INPUT, as lookahead_policy() checks its parameters
         if shape != (policy.num_params,):
             raise ValueError(f"params must be [{policy.num_params}] (one policy), got {shape}")
@@ -341,6 +350,94 @@ class VecFusedEnv(RenderMixin):
             out["mean"], out["sample"] = mean, smp
             z = (smp - mean) / sigma
             out["log_prob"] = (-0.5 * z * z - ls - 0.9189385332046727).sum(-1)   # 0.5 * log(2 pi)
+        if critic is not None:
+            out.update(self._advantages(out, critic, cp, float(gamma), float(lam), False))
+        return out
+
+    def _critic_args(self, critic, params, gamma, lam):
+        """what advantages() checks of its critic and scalars; returns the parameters as a device tensor"""
+        torch = self._torch
+        from rsoccer_amd.vec.policy import MLPCritic
+        if not isinstance(critic, MLPCritic):
+            raise ValueError("critic must be an rsoccer_amd.vec.policy.MLPCritic")
+        if critic.obs_dim != self.sim.obs_dim:
+            raise ValueError(f"the critic reads {critic.obs_dim} floats, the env's observation has {self.sim.obs_dim}")
+        for name, v in (("gamma", gamma), ("lam", lam)):
+            if not (np.isfinite(float(v)) and 0.0 <= float(v) <= 1.0):
+                raise ValueError(f"{name} must be in [0, 1], got {v}")
+        if params is None:
+            raise ValueError("critic_params must not be None")
+        shape = tuple(np.shape(params))
+        if shape != (critic.num_params,):
+            raise ValueError(f"critic params must be [{critic.num_params}], got {shape}")
+        if isinstance(params, torch.Tensor):
+            p = params.detach()
+            if p.device != self.device or p.dtype != torch.float32 or not p.is_contiguous():
+                p = p.to(device=self.device, dtype=torch.float32).contiguous()
+        else:
+            p = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float32)).to(self.device)
+        return p
+
+    def advantages(self, batch, critic, params, gamma=0.99, lam=0.95, return_next_values=False):
+        """Values of an MLP critic on a collected batch and its GAE advantages and returns, in two launches
+        (``rsx_task_advantages``): what a PPO / A2C loop does between ``collect()`` and its gradient step.
+
+        ``batch``: a mapping with ``obs`` ``[T, B, obs_dim]`` float32, ``reward`` ``[T, B]`` float32, ``terminated`` / ``truncated``
+        ``[T, B]`` bool or uint8, ``next_obs`` ``[B, obs_dim]`` float32 — the observation after the last step — and optionally
+        ``final_obs`` ``[T, B, obs_dim]``: what ``collect(..., return_final_obs=True)`` returns; the tensors of a ``step()`` loop,
+        stacked, serve as well.  All CUDA tensors on the env's device, contiguous; anything else is a ``ValueError`` naming the
+        offender.  ``T`` and ``B`` come from ``obs`` (``B`` need not be ``num_envs``).  ``critic``: an
+        ``rsoccer_amd.vec.policy.MLPCritic`` for this env's ``obs_dim``; ``params``: its flat ``[P]`` float32 parameters.
+
+        A terminated row bootstraps from 0, a row that was only truncated from ``V(final_obs[t])`` (0 without ``final_obs``), any
+        other from the next row's value, the last one from ``V(next_obs)``; the float32 recurrence is written out in
+        ``include/rsx.h``.  ``value[t, e]`` is bit for bit ``collect()``'s ``mean[t, e, 0]`` of an actor that shares the critic's
+        hidden layers and whose output row 0 is the critic's.
+
+        Returns fresh device tensors ``value``, ``advantage``, ``return`` ``[T, B]`` (and ``next_value`` with
+        ``return_next_values=True``).  Touches nothing of the env, never synchronises, capturable into a ``torch.cuda.CUDAGraph``."""
+        p = self._critic_args(critic, params, gamma, lam)
+        return self._advantages(batch, critic, p, float(gamma), float(lam), bool(return_next_values))
+
+    def _advantages(self, batch, critic, p, gamma, lam, return_next_values):
+        torch = self._torch
+        for key in ("obs", "reward", "terminated", "truncated", "next_obs"):
+            if key not in batch:
+                raise ValueError(f"batch lacks {key!r}")
+        obs = batch["obs"]
+        OD = self.sim.obs_dim
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or obs.shape[0] < 1 or obs.shape[1] < 1 or obs.shape[2] != OD:
+            raise ValueError(f"batch['obs'] must be a [T >= 1, B >= 1, {OD}] tensor, got {tuple(np.shape(obs))}")
+        T, B = int(obs.shape[0]), int(obs.shape[1])
+        fobs = batch.get("final_obs")
+        want = {"obs": ((T, B, OD), (torch.float32,)), "reward": ((T, B), (torch.float32,)),
+                "terminated": ((T, B), (torch.bool, torch.uint8)), "truncated": ((T, B), (torch.bool, torch.uint8)),
+                "next_obs": ((B, OD), (torch.float32,))}
+        if fobs is not None:
+            want["final_obs"] = ((T, B, OD), (torch.float32,))
+        for key, (shape, dtypes) in want.items():
+            t = batch[key]
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"batch[{key!r}] must be a torch tensor, got {type(t).__name__}")
+            if tuple(t.shape) != shape:
+                raise ValueError(f"batch[{key!r}] must be {list(shape)}, got {list(t.shape)}")
+            if t.dtype not in dtypes:
+                raise ValueError(f"batch[{key!r}] must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+            if t.device != self.device:
+                raise ValueError(f"batch[{key!r}] is on {t.device}, the env on {self.device}")
+            if not t.is_contiguous():
+                raise ValueError(f"batch[{key!r}] must be contiguous")
+        f32 = dict(dtype=torch.float32, device=self.device)
+        val, adv, ret = (torch.empty((T, B), **f32) for _ in range(3))
+        nxt = torch.empty((T, B), **f32) if return_next_values else None
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731  (a bool tensor is one byte per element, 0 or 1)
+        inp = _lib.AdvIn(ptr(obs), ptr(batch["reward"]), ptr(batch["terminated"]), ptr(batch["truncated"]), ptr(fobs), ptr(batch["next_obs"]))
+        self.sim.task_advantages(critic.spec(), p.data_ptr(), gamma, lam, T, B, inp, _lib.AdvOut(ptr(val), ptr(adv), ptr(ret), ptr(nxt)),
+                                 self._stream())
+        self._keep_adv = p   # alive until the launches have consumed it
+        out = {"value": val, "advantage": adv, "return": ret}
+        if return_next_values:
+            out["next_value"] = nxt
         return out
 
     # ---- planning with candidates drawn on the device (include/rsx.h: rsx_plan_sampler) ----

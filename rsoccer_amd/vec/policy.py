@@ -1,4 +1,5 @@
-"""The MLP policies ``VecFusedEnv.lookahead_policy`` evaluates inside the lookahead launch (include/rsx.h: rsx_policy_mlp).
+"""The MLP policies ``VecFusedEnv.lookahead_policy`` and ``collect`` evaluate inside their launches, and the critic of the same family
+``VecFusedEnv.advantages`` evaluates on a collected batch (include/rsx.h: rsx_policy_mlp).
 
 :class:`MLPPolicy` describes the SHAPE of a policy; its parameters are a flat float32 vector laid out like
 ``torch.nn.utils.parameters_to_vector`` of ``Sequential(Linear(obs_dim, hidden), act, [Linear(hidden, hidden), act,]
@@ -103,3 +104,22 @@ class MLPPolicy:
             x = (w @ x.unsqueeze(-1)).squeeze(-1) + b
             x = hid(x) if li + 1 < n else out(x)
         return x
+
+
+class MLPCritic(MLPPolicy):
+    """``obs_dim -> hidden [-> hidden] -> 1`` with a linear output: the critic ``VecFusedEnv.advantages`` evaluates
+    (``rsx_task_advantages``).  ``MLPPolicy``'s layout with ``act_dim = 1``: the flat parameters equal
+    ``parameters_to_vector`` of ``Sequential(Linear(obs_dim, hidden), act, [Linear(hidden, hidden), act,] Linear(hidden, 1))``.
+    ``forward`` returns ``[..., 1]``, like the module."""
+
+    def __init__(self, obs_dim, hidden=64, layers=2, hidden_act="tanh"):
+        super().__init__(obs_dim, 1, hidden=hidden, layers=layers, hidden_act=hidden_act, out_act="tanh")   # (checks the shape)
+        self.out_act = "none"
+
+    def spec(self):
+        """the rsx_policy_mlp of this shape, with out_act = RSX_ACT_NONE"""
+        return _lib.PolicyMLP(self.layers, self.hidden, _HIDDEN_ACTS[self.hidden_act], _lib.ACT_NONE)
+
+    def _torch_acts(self):
+        hid, _ = super()._torch_acts()
+        return hid, (lambda v: v)
