@@ -317,6 +317,7 @@ __device__ __forceinline__ void vss_epl_body(RSX_HOT_ARGS, const Params& P_, con
         if (__any(ended)) {
             if (ended) {
                 epl_store_row<EPL_OD>(bufs.final_obs, eo, ob);   // terminal observation
+                epl_row_stored<EPL_OD>(ob);   // the counters' constants and the placement take over the row's registers next
                 episode += 1; new_episode = true;
                 unsigned long long* const ms = metric_slot(bufs);
                 atomicAdd(&ms[1], 1ull);

@@ -61,6 +61,19 @@ __device__ __forceinline__ void epl_store_row(float* rows, const uint32_t eo, co
     if ((OD - T) & 1) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ob[OD - 1]), O, off, 4 * (OD - 1), 0);
 }
 
+// Behind epl_store_row on a path where the row's registers die with the store: wait until the stores have left, and keep every
+// register of the row defined until then.  A 16-byte buffer store whose data registers the very next VALU instruction redefines
+// read the new values in some lanes on gfx950 when the memory pipeline was backed up (VSS-v0 at 98 304 envs, every env ending in
+// one step: the 1ull of the first counter atomic landed in floats 36 and 37 of final_obs, lanes 12-15 of each sixteen of a wave;
+// profiles/LABBOOK.md).  The compiler adds no wait state there when the store's offset is in a scalar register.  The empty
+// statements emit nothing: their inputs are what keeps the registers from being reused above the wait.
+template <int OD>
+__device__ __forceinline__ void epl_row_stored(const float* ob) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int i = 0; i < OD; ++i) asm volatile("" ::"v"(ob[i]));
+}
+
 // contact sums of a sub-step (only when some lane touches something), column = lane; NB bodies (the ball last)
 template <int NB>
 struct EplSums { float acc[4][NB][64]; float accw[64]; };

@@ -407,16 +407,18 @@ def test_captured_call_on_a_host_keyed_handle_is_refused():
 # ---- 9. a handle whose single steps run one lane per env ----
 def test_handle_that_steps_one_lane_per_env():
     """The collect kernel is the lane-group kernel; what this case adds is that it reads and leaves the arrays as the one-lane-per-env
-    step keeps them (VSS-v0's task scalar row is not kept up to date there).  The registry's TimeLimit: no episode ends within these
-    steps, so the reference side takes no auto-reset in the one-lane-per-env kernel (episode ends inside collect are cases 1, 2, 7)."""
+    step keeps them (VSS-v0's task scalar row is not kept up to date there).  TimeLimit 5, two warm steps and T = 3: the last recorded row
+    ends every episode, so the stepped twin takes all 98 304 auto-resets in the one-lane-per-env kernel and must reproduce collect's
+    terminal observations and the checkpoint behind them."""
     import torch
     from rsoccer_amd import vec
-    env = vec.VecVSSEnv(98304, device=0, seed=5)
+    env = vec.VecVSSEnv(98304, device=0, seed=5, max_episode_steps=5)
     assert env.sim.task_layout() == "one-lane-per-env"
     _start(torch, env, 2)
     pol = _policy(env)
     out = _twin_check(torch, env, pol, _dense(torch, pol, 1)[0], 3, tag="98304 envs", log_std=-1.0, noise_seed=3)
     assert out["obs"].shape == (3, 98304, env.sim.obs_dim)
+    assert (out["terminated"][2] | out["truncated"][2]).mean() >= 0.9, "uninformative: the last recorded row does not end (nearly) every env"
     env.close()
 
 

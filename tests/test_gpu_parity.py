@@ -637,7 +637,7 @@ def test_env_per_lane_layout_is_bit_identical(oracle_mod, monkeypatch, task, kin
                 if layout == "epl":
                     for r in refs:
                         r.task_step(None)
-            if layout == "epl" and t % 7 == 0:
+            if layout == "epl" and (t % 7 == 0 or (t + 1) % max_steps == 0):   # and the steps at which the TimeLimit ends every env
                 _cmp_task(sim, refs, tens, t)
         sim.task_rollout(60)
         if layout == "epl":
@@ -690,7 +690,7 @@ def test_quad_layout_is_bit_identical(oracle_mod, monkeypatch, task):
                 if layout == "quad":
                     for r in refs:
                         r.task_step(None)
-            if layout == "quad" and t % 9 == 0:
+            if layout == "quad" and (t % 9 == 0 or (t + 1) % max_steps == 0):   # and the steps at which the TimeLimit ends every env
                 _cmp_task(sim, refs, tens, t)
         if layout == "quad":
             _cmp_task(sim, refs, tens, "end")
@@ -907,11 +907,15 @@ def test_large_batch_switches_layout_and_agrees(monkeypatch, task, kind, ft, nb,
         sim.task_step_n(25)
         sim.task_rollout(15)
         torch.cuda.synchronize()
-        outs.append((tens["obs"].clone(), tens["reward"].clone(), sim.state_tensor().clone(), sim.read_metrics()))
+        outs.append((tens["obs"].clone(), tens["reward"].clone(), sim.state_tensor().clone(), sim.read_metrics(),
+                     {k: tens[k].clone() for k in ("final_obs", "terminated", "truncated", "info", "steps")}))
         sim.close()
     for a, b in zip(outs[0][:3], outs[1][:3]):
         assert torch.equal(a, b)
     assert np.array_equal(outs[0][3], outs[1][3]) and outs[0][3][1] > 0
+    for k, a in outs[0][4].items():   # bit patterns: final_obs rows nobody wrote yet are zero in both
+        b = outs[1][4][k]
+        assert torch.equal(a.view(torch.int32) if a.dtype == torch.float32 else a, b.view(torch.int32) if b.dtype == torch.float32 else b), k
 
 
 def test_api_errors_are_reported_not_crashed():
