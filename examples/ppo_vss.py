@@ -1,6 +1,6 @@
 """PPO on VSS-v0 with every rollout collected in one launch.
 
-    python examples/ppo_vss.py [--envs 1024] [--steps 128] [--updates 10] [--epochs 4] [--minibatches 4] [--lr 3e-4]
+    python examples/ppo_vss.py [--envs 1024] [--steps 128] [--updates 10] [--epochs 4] [--minibatches 4] [--lr 3e-4] [--fused-update]
 
 One update: env.collect(...) advances the envs `steps` steps under the current actor — the MLP evaluated inside the engine's launch, a
 Gaussian head on top, episode ends handled in the launch — and, given the critic, evaluates it on the recorded observations and runs
@@ -8,7 +8,9 @@ the GAE recurrence in two more launches (env.advantages: a terminated row bootst
 terminal observation), returning the [T, B] batch with `value`, `advantage` and `return`; a few epochs of clipped PPO follow in torch.
 The actor's and the critic's weights reach the engine as flat vectors (MLPPolicy / MLPCritic.from_module: torch's own layout).  The
 density PPO compares is the pre-activation one: log N(sample; mean, exp(log_std)), where the action fed to the env is clip(sample) —
-the trainer evaluates the same expression on the recorded `sample`, so the ratio is exact.  A demonstration of the call pattern, not a tuned trainer."""
+the trainer evaluates the same expression on the recorded `sample`, so the ratio is exact.  With --fused-update the loss and its
+gradients come from the engine as well (env.ppo_gradient: three launches per minibatch): the leaves are the flat parameter vectors, the
+call's outputs become their .grad, and Adam steps on three tensors.  A demonstration of the call pattern, not a tuned trainer."""
 import argparse
 import os
 import sys
@@ -38,6 +40,7 @@ def main():
     ap.add_argument("--lam", type=float, default=0.95)
     ap.add_argument("--clip", type=float, default=0.2)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--fused-update", action="store_true", help="loss and gradients of a minibatch from env.ppo_gradient instead of torch")
     args = ap.parse_args()
 
     torch.manual_seed(args.seed)
@@ -49,13 +52,19 @@ def main():
     actor = torch.nn.Sequential(torch.nn.Linear(OD, 64), torch.nn.Tanh(), torch.nn.Linear(64, 64), torch.nn.Tanh(), torch.nn.Linear(64, AD)).to(dev)
     critic = torch.nn.Sequential(torch.nn.Linear(OD, 64), torch.nn.Tanh(), torch.nn.Linear(64, 64), torch.nn.Tanh(), torch.nn.Linear(64, 1)).to(dev)
     log_std = torch.nn.Parameter(torch.full((AD,), -0.5, device=dev))
-    opt = torch.optim.Adam(list(actor.parameters()) + list(critic.parameters()) + [log_std], lr=args.lr)
+    if args.fused_update:   # the flat vectors are the leaves: the engine reads and differentiates them as they are
+        p_actor = torch.nn.Parameter(pol.from_module(actor).to(dev))
+        p_critic = torch.nn.Parameter(val.from_module(critic).to(dev))
+        opt = torch.optim.Adam([p_actor, p_critic, log_std], lr=args.lr)
+    else:
+        opt = torch.optim.Adam(list(actor.parameters()) + list(critic.parameters()) + [log_std], lr=args.lr)
     T, B = args.steps, args.envs
     env.reset()
     for update in range(args.updates):
         t0 = time.perf_counter()
-        batch = env.collect(pol, pol.from_module(actor), T, log_std=log_std, iteration=update,
-                            critic=val, critic_params=val.from_module(critic), gamma=args.gamma, lam=args.lam)
+        batch = env.collect(pol, p_actor if args.fused_update else pol.from_module(actor), T, log_std=log_std, iteration=update,
+                            critic=val, critic_params=p_critic if args.fused_update else val.from_module(critic),
+                            gamma=args.gamma, lam=args.lam)
         ret, adv = batch["return"], batch["advantage"]
         adv = (adv - adv.mean()) / (adv.std() + 1e-8)
         torch.cuda.synchronize()
@@ -64,6 +73,12 @@ def main():
         old_lp, adv_f, ret_f = batch["log_prob"].reshape(-1), adv.reshape(-1), ret.reshape(-1)
         for _ in range(args.epochs):
             for idx in torch.randperm(T * B, device=dev).chunk(args.minibatches):
+                if args.fused_update:
+                    out = env.ppo_gradient(batch, pol, p_actor, log_std, val, p_critic, rows=idx, advantage=adv, clip=args.clip, vf_coef=0.5)
+                    p_actor.grad, p_critic.grad, log_std.grad = out["grad_params"], out["grad_critic_params"], out["grad_log_std"]
+                    opt.step()
+                    loss_pi, loss_v = out["stats"]["loss_pi"], out["stats"]["loss_v"]
+                    continue
                 lp = log_prob(actor(flat["obs"][idx]), log_std, flat["sample"][idx])
                 ratio = (lp - old_lp[idx]).exp()
                 loss_pi = -torch.min(ratio * adv_f[idx], ratio.clamp(1 - args.clip, 1 + args.clip) * adv_f[idx]).mean()
@@ -74,7 +89,8 @@ def main():
         torch.cuda.synchronize()
         m = env.metrics()
         print(f"update {update}: mean reward / step {float(batch['reward'].mean()):+.5f}, episodes {m['episodes']}, goals for / against "
-              f"{m['goals_for']} / {m['goals_against']}, sigma {log_std.exp().mean().item():.3f}; collect + advantages "
+              f"{m['goals_for']} / {m['goals_against']}, sigma {log_std.exp().mean().item():.3f}, loss_pi {float(loss_pi):+.5f}, "
+              f"loss_v {float(loss_v):.5f}; collect + advantages "
               f"{t_collect * 1e3:.1f} ms, update {((time.perf_counter() - t0) - t_collect) * 1e3:.1f} ms")
     env.close()
 

@@ -577,6 +577,85 @@ int rsx_task_advantages(rsx_sim* h, const rsx_policy_mlp* critic, const float* c
                         float gamma, float lam, int n_steps /* T */, int n_envs /* B, any >= 1 */,
                         const rsx_adv_in* in, const rsx_adv_out* out, void* stream);
 
+/* ---- PPO loss gradients of an MLP actor and critic on a collected batch (additive extension of ABI 6) ------------------------------
+ * What an on-policy trainer does with a minibatch between rsx_task_advantages and its optimiser step: the forward pass of both
+ * networks on the minibatch's rows, the clipped-surrogate and value losses, and their gradients — three launches instead of torch's
+ * gather, two MLP forwards, a few dozen elementwise kernels and backward().
+ *   the handle       supplies only the device, obs_dim, act_dim and the error string, as for rsx_task_advantages: the call reads and
+ *                    writes NOTHING of the envs; host-keyed and device-keyed handles both capture.
+ *   actor            an rsx_policy_mlp as rsx_task_collect_policy takes it, actor_params_dev [P_actor] (rsx_policy_num_params); its
+ *                    out_act plays no part: the density is that of the pre-out_act sample, as collected.  log_std_dev [act_dim].
+ *   critic           as for rsx_task_advantages (out_act = RSX_ACT_NONE), critic_params_dev [P_critic] (rsx_critic_num_params).
+ *   rows             the minibatch as flat indices into the N = T * B rows of the batch, repeats allowed; NULL: rows 0 .. M - 1.  Device
+ *                    memory is NOT checked: an index outside [0, N) (a padding entry, say -1) contributes nothing to any output, is
+ *                    counted in stats[7], and nothing outside the arrays is read for it.
+ * The loss, with every mean a sum over the M entries divided by M (skipped entries do not change the divisor):
+ *   mean_a           the actor's output accumulator before out_act;  value = the critic's output
+ *   z_a              (sample_a - mean_a) / exp(log_std_a)
+ *   lp               sum over a of (-0.5 z_a^2 - log_std_a - 0.5 log 2 pi)
+ *   ratio            exp(lp - old_log_prob)
+ *   L_pi             -mean(min(ratio * A, clamp(ratio, 1 - clip, 1 + clip) * A))
+ *   L_v              0.5 * mean((value - ret)^2)
+ *   entropy          sum over a of (log_std_a + 0.5 + 0.5 log 2 pi)
+ *   L                L_pi + vf_coef * L_v - ent_coef * entropy
+ * The outputs are the gradients of L.  Through the min they follow torch's autograd (a tie splits in half and both halves reach
+ * ratio; clamp passes the gradient at its bounds):  dL_pi / dratio = -A / M  where  1 - clip <= ratio <= 1 + clip  or
+ * ratio * A < clamp(ratio) * A,  else 0 — so at ratio == 1 and at ratio == 1 +- clip the gradient flows for both signs of A.
+ * The bounds 1 - clip and 1 + clip are computed in float32.  Activation derivatives come from the stored activation: tanh 1 - h^2,
+ * relu h > 0.
+ * Arithmetic, all float32, the unit is built with -ffp-contract=off.  Forward: rsx_policy_mlp's, bit for bit (per unit acc = bias,
+ * ascending fmaf, the same tanh), so `mean` equals rsx_collect_out.mean and `value` equals rsx_adv_out.values on the same parameters
+ * and rows.  Backward: minibatch entries are taken in blocks of 64; workgroup w of G = min(ceil(M / 64), max_workgroups) takes blocks
+ * w, w + G, ...  Per entry dL/dmean_a = dlp * (z_a / sigma_a) and dL/dlog_std_a = dlp * (z_a^2 - 1) with dlp = (-(A / M)) * ratio where
+ * the gradient flows, dL/dvalue = ((value - ret) * vf_coef) / M (the division by M is a multiplication by the float32 1 / M);
+ * dz = (W^T d(next)) * act', the product with the second layer's weights summed as four interleaved fmaf chains over the units,
+ * combined (s0 + s1) + (s2 + s3).  A weight or bias gradient is ONE fmaf (bias: addition) chain per workgroup over all its entries in
+ * the order it met them, starting from 0 (v_mfma_f32_32x32x2_f32, which is a k-ordered fmaf chain, for the hidden layers' weights); the
+ * per-workgroup partials are then added in workgroup order, starting from 0.  The stats and the log_std gradient are summed per lane
+ * (entry mod 64), then over the lanes in ascending order, then over the workgroups.  Hence the result bits are a function of the inputs
+ * and of G alone — not of the device, its CU count or the timing.
+ *   stats            [8]: 0 L_pi, 1 L_v, 2 entropy, 3 approx_kl = mean((ratio - 1) - log ratio), 4 clip_fraction = the share of entries
+ *                    with ratio outside [1 - clip, 1 + clip], 5 mean ratio, 6 entries used, 7 entries skipped
+ *   mean, value      optional: the forward pass's outputs per minibatch entry (0 for a skipped entry)
+ *   workspace        at least rsx_ppo_gradient_workspace bytes (one partial per workgroup and network), 16-byte aligned, for the same
+ *                    n_rows and max_workgroups; its contents before the call do not matter
+ *   max_workgroups   0: the default, a constant of the build (512), not the device's CU count; > 0: caps G
+ * Stream-ordered, never synchronises, never allocates, capturable.  Refusals (nothing is enqueued, rsx_last_error says why), all
+ * RSX_ERR_ARG: a null actor, critic, parameter or log_std array, in, cfg, out or required array; n_rows < 1, n_batch_rows < 1 or
+ * either above 2^31 - 1; clip non-finite or outside (0, 1); vf_coef or ent_coef non-finite; max_workgroups < 0; a spec outside
+ * rsx_policy_mlp's listed values (the critic's out_act != RSX_ACT_NONE); a handle without a task; the scrimmage task; a network whose
+ * weights and row buffers do not fit a workgroup's 64 KB of LDS (2 x 64 units fit 64 observation floats). */
+typedef struct rsx_ppo_in {
+    const float*   obs;           /* [N][obs_dim]   required */
+    const float*   sample;        /* [N][act_dim]   the pre-out_act sample rsx_task_collect_policy records   required */
+    const float*   old_log_prob;  /* [N]            log-density under the collecting policy   required */
+    const float*   advantage;     /* [N]            required */
+    const float*   ret;           /* [N]            returns   required */
+    const int32_t* rows;          /* [M] flat row indices, repeats allowed, or NULL = rows 0 .. M - 1 */
+    int64_t        n_batch_rows;  /* N */
+    int64_t        n_rows;        /* M */
+} rsx_ppo_in;
+typedef struct rsx_ppo_cfg {
+    float   clip;            /* in (0, 1) */
+    float   vf_coef;         /* finite */
+    float   ent_coef;        /* finite */
+    int32_t max_workgroups;  /* 0 = the build's default; > 0 caps the grid */
+} rsx_ppo_cfg;
+typedef struct rsx_ppo_out {
+    float* grad_actor;    /* [P_actor]    required */
+    float* grad_log_std;  /* [act_dim]    required */
+    float* grad_critic;   /* [P_critic]   required */
+    float* stats;         /* [8]          required */
+    float* mean;          /* [M][act_dim] or NULL */
+    float* value;         /* [M] or NULL */
+    void*  workspace;     /* rsx_ppo_gradient_workspace bytes   required */
+} rsx_ppo_out;
+int rsx_ppo_gradient_workspace(const rsx_sim* h, const rsx_policy_mlp* actor, const rsx_policy_mlp* critic,
+                               int64_t n_rows, int max_workgroups, int64_t* bytes_out);
+int rsx_task_ppo_gradient(rsx_sim* h, const rsx_policy_mlp* actor, const float* actor_params_dev, const float* log_std_dev,
+                          const rsx_policy_mlp* critic, const float* critic_params_dev,
+                          const rsx_ppo_in* in, const rsx_ppo_cfg* cfg, const rsx_ppo_out* out, void* stream);
+
 /* Debugging aid: number of non-finite floats in the state rows and, with a task attached, in the
  * observations, rewards and info rows.  Synchronises `stream`.  With RSX_DEBUG_FINITE=1 in the
  * environment every stepping call (rsx_step_dev, rsx_task_step, rsx_task_step_n, rsx_task_rollout, rsx_task_collect_policy)

@@ -54,6 +54,7 @@ SYMBOLS = (
     "rsx_policy_num_params", "rsx_task_lookahead_policy",
     "rsx_task_collect_policy",
     "rsx_critic_num_params", "rsx_task_advantages",
+    "rsx_ppo_gradient_workspace", "rsx_task_ppo_gradient",
 )
 # activations of rsx_policy_mlp (include/rsx.h: RSX_ACT_*)
 ACT_RELU, ACT_TANH, ACT_CLIP = 0, 1, 2
@@ -89,6 +90,28 @@ class AdvIn(C.Structure):
 class AdvOut(C.Structure):
     """rsx_adv_out (include/rsx.h): the [T][B] results of rsx_task_advantages; device addresses, next_values may be None"""
     _fields_ = [("values", C.c_void_p), ("advantages", C.c_void_p), ("returns", C.c_void_p), ("next_values", C.c_void_p)]
+
+
+class PpoIn(C.Structure):
+    """rsx_ppo_in (include/rsx.h): the flattened [N] batch rsx_task_ppo_gradient reads and the minibatch's rows; device addresses,
+    rows may be None (rows 0 .. M - 1)"""
+    _fields_ = [("obs", C.c_void_p), ("sample", C.c_void_p), ("old_log_prob", C.c_void_p), ("advantage", C.c_void_p), ("ret", C.c_void_p),
+                ("rows", C.c_void_p), ("n_batch_rows", C.c_int64), ("n_rows", C.c_int64)]
+
+
+class PpoCfg(C.Structure):
+    """rsx_ppo_cfg (include/rsx.h): the scalars of the PPO loss and the cap of the grid (0 = the build's default)"""
+    _fields_ = [("clip", C.c_float), ("vf_coef", C.c_float), ("ent_coef", C.c_float), ("max_workgroups", C.c_int32)]
+
+
+class PpoOut(C.Structure):
+    """rsx_ppo_out (include/rsx.h): the gradients, the stats [8], the optional forward outputs and the workspace; device addresses"""
+    _fields_ = [("grad_actor", C.c_void_p), ("grad_log_std", C.c_void_p), ("grad_critic", C.c_void_p), ("stats", C.c_void_p),
+                ("mean", C.c_void_p), ("value", C.c_void_p), ("workspace", C.c_void_p)]
+
+
+# the slots of rsx_ppo_out.stats, in order
+PPO_STATS = ("loss_pi", "loss_v", "entropy", "approx_kl", "clip_fraction", "ratio", "rows_used", "rows_skipped")
 
 
 class DevView(C.Structure):
@@ -192,6 +215,9 @@ def load():
     lib.rsx_task_collect_policy.argtypes = [vp, C.POINTER(PolicyMLP), vp, vp, C.c_uint64, ip, C.POINTER(CollectOut), vp]
     lib.rsx_critic_num_params.argtypes = [vp, C.POINTER(PolicyMLP), C.POINTER(C.c_int64)]
     lib.rsx_task_advantages.argtypes = [vp, C.POINTER(PolicyMLP), vp, C.c_float, C.c_float, ip, ip, C.POINTER(AdvIn), C.POINTER(AdvOut), vp]
+    lib.rsx_ppo_gradient_workspace.argtypes = [vp, C.POINTER(PolicyMLP), C.POINTER(PolicyMLP), C.c_int64, ip, C.POINTER(C.c_int64)]
+    lib.rsx_task_ppo_gradient.argtypes = [vp, C.POINTER(PolicyMLP), vp, vp, C.POINTER(PolicyMLP), vp, C.POINTER(PpoIn), C.POINTER(PpoCfg),
+                                          C.POINTER(PpoOut), vp]
     lib.rsx_physics_defaults.argtypes = [ip, vp]
     lib.rsx_physics_derive.argtypes = [ip, ip, vp, vp]
     lib.rsx_physics_enable.argtypes = [vp, vp]
@@ -561,6 +587,24 @@ class Sim:
         rc = self._lib.rsx_task_advantages(self._h, None if spec is None else C.byref(spec), params_ptr, float(gamma), float(lam),
                                            int(n_steps), int(n_envs), None if inp is None else C.byref(inp),
                                            None if out is None else C.byref(out), stream)
+        if rc:
+            _chk(rc)
+
+    def ppo_gradient_workspace(self, actor, critic, n_rows, max_workgroups=0):
+        """rsx_ppo_gradient_workspace: bytes of scratch rsx_task_ppo_gradient needs for a minibatch of ``n_rows`` rows"""
+        n = C.c_int64(0)
+        _chk(self._lib.rsx_ppo_gradient_workspace(self._h, None if actor is None else C.byref(actor), None if critic is None else C.byref(critic),
+                                                  int(n_rows), int(max_workgroups), C.byref(n)))
+        return int(n.value)
+
+    def task_ppo_gradient(self, actor, actor_params_ptr, log_std_ptr, critic, critic_params_ptr, inp, cfg, out, stream=None):
+        """rsx_task_ppo_gradient: gradients of the PPO loss with respect to the actor's parameters, log_std and the critic's parameters on
+        a minibatch, in three launches.  ``actor`` / ``critic``: PolicyMLP specs, ``inp``: a PpoIn, ``cfg``: a PpoCfg, ``out``: a PpoOut
+        of device addresses (None passes NULL).  Reads and writes nothing of the envs."""
+        rc = self._lib.rsx_task_ppo_gradient(self._h, None if actor is None else C.byref(actor), actor_params_ptr, log_std_ptr,
+                                             None if critic is None else C.byref(critic), critic_params_ptr,
+                                             None if inp is None else C.byref(inp), None if cfg is None else C.byref(cfg),
+                                             None if out is None else C.byref(out), stream)
         if rc:
             _chk(rc)
 

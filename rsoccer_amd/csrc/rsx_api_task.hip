@@ -437,6 +437,54 @@ int rsx_task_advantages(rsx_sim* h, const rsx_policy_mlp* critic, const float* c
     return RSX_OK;
 }
 
+// ---- PPO loss gradients of an actor and a critic on a minibatch (rsx.h: rsx_task_ppo_gradient).  The handle as for rsx_task_advantages ----
+// what both calls check of the two networks; on success the specs as the kernels take them and the floats of each
+static int ppo_prologue(const rsx_sim* h, const rsx_policy_mlp* actor, const rsx_policy_mlp* critic, PolicySpec* SA, int64_t* n_actor,
+                        PolicySpec* SC, int64_t* n_critic) {
+    if (h->P.task == RSX_TASK_NONE) return fail(RSX_ERR_ARG, "no task attached (rsx_task_attach): obs_dim and act_dim are the task's");
+    if (int rc = policy_prologue(h, actor, SA, n_actor)) return rc;
+    if (int rc = critic_prologue(h, critic, SC, n_critic)) return rc;
+    if (ppo_lds_bytes(h->P.obs_dim, h->M.act_dim, *SA) > 65536ll || ppo_lds_bytes(h->P.obs_dim, 1, *SC) > 65536ll)
+        return fail(RSX_ERR_ARG, "a network's weights and row buffers do not fit a workgroup's 64 KB of LDS at this observation width: use fewer or smaller hidden layers");
+    return RSX_OK;
+}
+
+int rsx_ppo_gradient_workspace(const rsx_sim* h, const rsx_policy_mlp* actor, const rsx_policy_mlp* critic, int64_t n_rows,
+                               int max_workgroups, int64_t* bytes_out) {
+    if (!h) return fail(RSX_ERR_ARG, "null handle");
+    if (!bytes_out) return fail(RSX_ERR_ARG, "bytes_out must not be null");
+    PolicySpec SA, SC; int64_t na = 0, nc = 0;
+    if (int rc = ppo_prologue(h, actor, critic, &SA, &na, &SC, &nc)) return rc;
+    if (n_rows < 1 || n_rows > 0x7FFFFFFFll) return fail(RSX_ERR_ARG, "n_rows must be in 1 .. 2^31 - 1");
+    if (max_workgroups < 0) return fail(RSX_ERR_ARG, "max_workgroups must be >= 0");
+    *bytes_out = ppo_workspace_bytes(na, nc, h->M.act_dim, n_rows, max_workgroups);
+    return RSX_OK;
+}
+
+int rsx_task_ppo_gradient(rsx_sim* h, const rsx_policy_mlp* actor, const float* actor_params_dev, const float* log_std_dev,
+                          const rsx_policy_mlp* critic, const float* critic_params_dev, const rsx_ppo_in* in, const rsx_ppo_cfg* cfg,
+                          const rsx_ppo_out* out, void* stream) {
+    RSX_ENTER(h);   // (nothing the handle owns is read or written by the launches)
+    PolicySpec SA, SC; int64_t na = 0, nc = 0;
+    if (int rc = ppo_prologue(h, actor, critic, &SA, &na, &SC, &nc)) return rc;
+    if (!actor_params_dev || !log_std_dev || !critic_params_dev)
+        return fail(RSX_ERR_ARG, "actor_params_dev, log_std_dev and critic_params_dev must not be null");
+    if (!in || !in->obs || !in->sample || !in->old_log_prob || !in->advantage || !in->ret)
+        return fail(RSX_ERR_ARG, "in and its obs, sample, old_log_prob, advantage and ret arrays must not be null");
+    if (in->n_rows < 1 || in->n_batch_rows < 1 || in->n_rows > 0x7FFFFFFFll || in->n_batch_rows > 0x7FFFFFFFll)
+        return fail(RSX_ERR_ARG, "n_rows and n_batch_rows must be in 1 .. 2^31 - 1");
+    if (!cfg) return fail(RSX_ERR_ARG, "cfg must not be null");
+    if (!(std::isfinite(cfg->clip) && cfg->clip > 0.0f && cfg->clip < 1.0f)) return fail(RSX_ERR_ARG, "clip must be in (0, 1)");
+    if (!std::isfinite(cfg->vf_coef) || !std::isfinite(cfg->ent_coef)) return fail(RSX_ERR_ARG, "vf_coef and ent_coef must be finite");
+    if (cfg->max_workgroups < 0) return fail(RSX_ERR_ARG, "max_workgroups must be >= 0");
+    if (!out || !out->grad_actor || !out->grad_log_std || !out->grad_critic || !out->stats || !out->workspace)
+        return fail(RSX_ERR_ARG, "out and its grad_actor, grad_log_std, grad_critic, stats and workspace must not be null");
+    launch_ppo_gradient(SA, na, actor_params_dev, log_std_dev, SC, nc, critic_params_dev, h->P.obs_dim, h->M.act_dim, *in, *cfg, *out,
+                        (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
 // ---- planning with candidates drawn on the device (rsx.h: rsx_plan_sampler) ----
 // what the three calls check alike; on success S is the sampler as the kernels take it and P the handle's parameters with the step
 // counter the next step would take (not advanced).  n_steps: what the counter limit is checked against (0: the call simulates nothing)

@@ -8,6 +8,9 @@
 struct rsx_render_view;   // include/rsx.h
 struct rsx_adv_in;
 struct rsx_adv_out;
+struct rsx_ppo_in;
+struct rsx_ppo_cfg;
+struct rsx_ppo_out;
 
 namespace rsx {
 
@@ -96,6 +99,17 @@ enum : int { GAE_FORM_ROWS = 0, GAE_FORM_GROUPS = 1 };
 long long gae_lds_bytes(int form, int obs_dim, const PolicySpec& critic);
 void launch_advantages(int form, const PolicySpec& critic, const float* params, int obs_dim, float gamma, float gl, int T, int B,
                        const rsx_adv_in& in, const rsx_adv_out& out, hipStream_t s);
+// rsx_ppo.hip: gradients of the PPO loss with respect to an MLP actor, its log_std and an MLP critic (rsx_task_ppo_gradient).  actor /
+// critic: rsx_policy_mlp, checked (the actor's out_act plays no part); n_params_*: the floats of each; in / cfg / out: the call's
+// structs, checked.  Three launches: the row kernel for the actor, the same for the critic, the reduce.  ppo_grid: workgroups of a row
+// launch (min(ceil(n_rows / 64), max_workgroups or the build's default)); ppo_workspace_bytes: one partial per workgroup and network;
+// ppo_lds_bytes: LDS of one workgroup of a row launch (the host refuses more than 64 KB)
+int ppo_grid(long long n_rows, int max_workgroups);
+long long ppo_lds_bytes(int obs_dim, int act_dim, const PolicySpec& net);
+long long ppo_workspace_bytes(long long n_params_actor, long long n_params_critic, int act_dim, long long n_rows, int max_workgroups);
+void launch_ppo_gradient(const PolicySpec& actor, long long n_params_actor, const float* actor_params, const float* log_std,
+                         const PolicySpec& critic, long long n_params_critic, const float* critic_params, int obs_dim, int act_dim,
+                         const rsx_ppo_in& in, const rsx_ppo_cfg& cfg, const rsx_ppo_out& out, hipStream_t s);
 // rsx_render.hip: batched rgb frames (rsx_render_*).  render_check_view: nullptr when the view is valid (and the frame size), else the
 // message; render_field_host: the static field image [H][W][3]; RenderGeom: what the kernel needs of a view, in float32
 struct RenderGeom { int W, H; float s, cx, cy, r, rb; int square; };

@@ -440,6 +440,117 @@ class VecFusedEnv(RenderMixin):
             out["next_value"] = nxt
         return out
 
+    def ppo_gradient(self, batch, policy, params, log_std, critic, critic_params, rows=None, advantage=None, clip=0.2, vf_coef=0.5,
+                     ent_coef=0.0, max_workgroups=None, return_forward=False):
+        """Gradients of the PPO loss with respect to an MLP actor, its ``log_std`` and an MLP critic on a minibatch of a collected
+        batch, in three launches (``rsx_task_ppo_gradient``): what a PPO loop does per minibatch before ``opt.step()``.
+
+        ``batch``: ``collect(..., critic=...)``'s dict; ``obs`` ``[T, B, obs_dim]``, ``sample`` ``[T, B, act_dim]``, ``log_prob``,
+        ``advantage`` and ``return`` ``[T, B]`` are used, all float32 CUDA tensors on the env's device, contiguous (anything else is a
+        ``ValueError`` naming the offender).  ``advantage=`` overrides the batch's with a ``[T, B]`` tensor (a normalised one, say).
+        ``policy`` / ``params`` ``[P]`` / ``log_std`` ``[act_dim]`` and ``critic`` / ``critic_params`` ``[Pc]``: as for ``collect``, float32
+        device tensors.  ``rows``: the minibatch as a 1-D int32 / int64 tensor of flat indices into the ``T * B`` rows, repeats allowed
+        (int64 is converted by one torch op); ``None``: the whole batch.  Host-side ``rows`` (list, numpy, CPU tensor) are range-checked;
+        a device tensor is not — an index outside ``[0, T * B)`` contributes nothing and is counted in ``stats["rows_skipped"]``.
+
+        The loss is ``L_pi + vf_coef * L_v - ent_coef * entropy`` with the clipped surrogate of ``clip`` and means over the minibatch,
+        written out in ``include/rsx.h`` with its float32 arithmetic.  ``max_workgroups`` caps the grid of the row launches (``None``:
+        the build's default); the result bits depend on the inputs and that number only.
+
+        Returns fresh device tensors ``grad_params`` ``[P]``, ``grad_log_std`` ``[act_dim]``, ``grad_critic_params`` ``[Pc]`` and
+        ``stats``: a dict of 0-d views (``loss_pi``, ``loss_v``, ``entropy``, ``approx_kl``, ``clip_fraction``, ``ratio``, ``rows_used``,
+        ``rows_skipped``; no synchronisation); with ``return_forward=True`` also ``mean`` ``[M, act_dim]`` and ``value`` ``[M]``, bit for
+        bit ``batch["mean"]`` / ``batch["value"]`` at the rows.  Touches nothing of the env, never synchronises, capturable."""
+        torch = self._torch
+        from rsoccer_amd.vec.policy import MLPCritic, MLPPolicy
+        if not isinstance(policy, MLPPolicy) or isinstance(policy, MLPCritic):
+            raise ValueError("policy must be an rsoccer_amd.vec.policy.MLPPolicy")
+        if not isinstance(critic, MLPCritic):
+            raise ValueError("critic must be an rsoccer_amd.vec.policy.MLPCritic")
+        OD, AD, dev = self.sim.obs_dim, self.sim.act_dim, self.device
+        if policy.obs_dim != OD or policy.act_dim != AD:
+            raise ValueError(f"the policy maps {policy.obs_dim} -> {policy.act_dim}, the env {OD} -> {AD}")
+        if critic.obs_dim != OD:
+            raise ValueError(f"the critic reads {critic.obs_dim} floats, the env's observation has {OD}")
+        clip, vf_coef, ent_coef = float(clip), float(vf_coef), float(ent_coef)
+        if not (np.isfinite(clip) and 0.0 < clip < 1.0):
+            raise ValueError(f"clip must be in (0, 1), got {clip}")
+        for name, v in (("vf_coef", vf_coef), ("ent_coef", ent_coef)):
+            if not np.isfinite(v):
+                raise ValueError(f"{name} must be finite, got {v}")
+        mw = 0 if max_workgroups is None else int(max_workgroups)
+        if mw < 0 or (max_workgroups is not None and mw < 1):
+            raise ValueError(f"max_workgroups must be >= 1 or None, got {max_workgroups}")
+
+        def need(name, t, shape, dtypes=(torch.float32,)):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
+            if tuple(t.shape) != tuple(shape):
+                raise ValueError(f"{name} must be {list(shape)}, got {list(t.shape)}")
+            if t.dtype not in dtypes:
+                raise ValueError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+            if t.device != dev:
+                raise ValueError(f"{name} is on {t.device}, the env on {dev}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+            return t.detach()
+
+        keys = ("obs", "sample", "log_prob", "return") + (("advantage",) if advantage is None else ())
+        for key in keys:
+            if key not in batch:
+                raise ValueError(f"batch lacks {key!r}")
+        obs = batch["obs"]
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or obs.shape[0] < 1 or obs.shape[1] < 1 or obs.shape[2] != OD:
+            raise ValueError(f"batch['obs'] must be a [T >= 1, B >= 1, {OD}] tensor, got {tuple(np.shape(obs))}")
+        T, B = int(obs.shape[0]), int(obs.shape[1])
+        N = T * B
+        obs = need("batch['obs']", obs, (T, B, OD))
+        smp = need("batch['sample']", batch["sample"], (T, B, AD))
+        olp = need("batch['log_prob']", batch["log_prob"], (T, B))
+        ret = need("batch['return']", batch["return"], (T, B))
+        adv = need("batch['advantage']", batch["advantage"], (T, B)) if advantage is None else need("advantage", advantage, (T, B))
+        p = need("params", params, (policy.num_params,))
+        ls = need("log_std", log_std, (AD,))
+        cp = need("critic_params", critic_params, (critic.num_params,))
+        if rows is None:
+            r, M = None, N
+        else:
+            if not isinstance(rows, torch.Tensor) or not rows.is_cuda:   # host data: checked, then uploaded
+                host = np.asarray(rows.numpy() if isinstance(rows, torch.Tensor) else rows)
+                if host.ndim != 1 or host.size < 1 or host.dtype.kind not in "iu":
+                    raise ValueError(f"rows must be a 1-D integer array with at least one entry, got shape {host.shape} dtype {host.dtype}")
+                if int(host.min()) < 0 or int(host.max()) >= N:
+                    raise ValueError(f"rows must lie in [0, {N}), got {int(host.min())} .. {int(host.max())}")
+                rows = torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32)).to(dev)
+            if rows.dim() != 1 or rows.shape[0] < 1:
+                raise ValueError(f"rows must be 1-D with at least one entry, got {list(rows.shape)}")
+            if rows.dtype not in (torch.int32, torch.int64):
+                raise ValueError(f"rows must be torch.int32 or torch.int64, got {rows.dtype}")
+            if rows.device != dev:
+                raise ValueError(f"rows is on {rows.device}, the env on {dev}")
+            r = rows.to(torch.int32) if rows.dtype == torch.int64 else rows
+            if not r.is_contiguous():
+                raise ValueError("rows must be contiguous")
+            M = int(r.shape[0])
+        aspec, cspec = policy.spec(), critic.spec()
+        nbytes = self.sim.ppo_gradient_workspace(aspec, cspec, M, mw)
+        f32 = dict(dtype=torch.float32, device=dev)
+        ws = torch.empty(((nbytes + 3) // 4,), **f32)
+        ga, gl, gc = torch.empty((policy.num_params,), **f32), torch.empty((AD,), **f32), torch.empty((critic.num_params,), **f32)
+        stats = torch.empty((8,), **f32)
+        mean = torch.empty((M, AD), **f32) if return_forward else None
+        val = torch.empty((M,), **f32) if return_forward else None
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        inp = _lib.PpoIn(ptr(obs), ptr(smp), ptr(olp), ptr(adv), ptr(ret), ptr(r), N, M)
+        out = _lib.PpoOut(ptr(ga), ptr(gl), ptr(gc), ptr(stats), ptr(mean), ptr(val), ptr(ws))
+        self.sim.task_ppo_gradient(aspec, ptr(p), ptr(ls), cspec, ptr(cp), inp, _lib.PpoCfg(clip, vf_coef, ent_coef, mw), out, self._stream())
+        self._keep_ppo = (ws, r)   # the call's own tensors: alive until the launches have consumed them
+        res = {"grad_params": ga, "grad_log_std": gl, "grad_critic_params": gc,
+               "stats": {name: stats[k] for k, name in enumerate(_lib.PPO_STATS)}}
+        if return_forward:
+            res["mean"], res["value"] = mean, val
+        return res
+
     # ---- planning with candidates drawn on the device (include/rsx.h: rsx_plan_sampler) ----
     def _plan_sampler(self, sigma, hold, seed, iteration):
         """the rsx_plan_sampler of a call: ``sample_seed`` is a 64-bit mix (splitmix64) of ``seed`` (default: the env's) and
