@@ -325,13 +325,27 @@ __device__ __forceinline__ void respond(const float nx, const float ny, const fl
 // a wall, wall_shares above); the Coulomb limit keeps the nominal share w.  With wx == wy == w every operation is the one respond()
 // performs ((ope vn) w, (beta pen) w: same association), so the two agree bit for bit — which lets the kernels keep the short form
 // on the hot path and take this one only next to a wall.
+// VN_SELECT (SubstepCuts::vn_select, rsx_contact.hpp): the impulse block is computed for every lane and the sums keep their OLD values
+// by select where vn < 0 is false (NaN included) — the same operations on the same operands where it is true, untouched bits where it
+// is not, and no exec-mask branch inside the partner walk.  (Not a multiplication by a zeroed q: -0.0 sums would need an argument.)
+template <bool VN_SELECT = false>
 __device__ __forceinline__ void respond_axes(const float nx, const float ny, const float pen, const float dvx,
                                              const float dvy, const float wsum, const float ope, const float w,
                                              const float wx, const float wy,
                                              const float kt, const float mu, const float spin_c, const float beta,
                                              float& avx, float& avy, float& apx, float& apy, float& aw) {
     float vn = fma_(dvx, nx, dvy * ny);
-    if (vn < 0.0f) {
+    if constexpr (VN_SELECT) {
+        const float q = ope * vn;
+        float nvx = fma_(q * wx, nx, avx), nvy = fma_(q * wy, ny, avy);
+        const float vt = fma_(dvy, nx, -(dvx * ny)) - wsum;
+        const float lim = (q * w) * mu;
+        const float ft = clampf(vt * kt, lim, -lim);
+        nvx = fma_(-ft, ny, nvx); nvy = fma_(ft, nx, nvy);
+        const float nw = fma_(ft, spin_c, aw);
+        const bool closing = vn < 0.0f;
+        avx = closing ? nvx : avx; avy = closing ? nvy : avy; aw = closing ? nw : aw;
+    } else if (vn < 0.0f) {
         float q = ope * vn;
         avx = fma_(q * wx, nx, avx); avy = fma_(q * wy, ny, avy);
         float vt = fma_(dvy, nx, -(dvx * ny)) - wsum;
@@ -349,7 +363,7 @@ __device__ __forceinline__ void respond_axes(const float nx, const float ny, con
 // v2w: WAVE-UNIFORM, computed once per sweep by the caller — does any robot of the wave stand at_wall?  If not, no pair can have a
 // blocked axis and the partner loop runs v1's instructions, untouched; the wall-aware code hangs off a scalar branch (a divergent
 // test here would be structurised in place: its body, exec-mask copies and all, in the middle of the hot loop).
-template <int KIND>
+template <int KIND, bool VN_SELECT = false>
 __device__ __forceinline__ void contact_response(const Params& P, const Body& o, const float4 oj, const float d2,
                                                  const float rs, const float ope, const float w,
                                                  const float kt, const float mu, const float spin_c,
@@ -364,7 +378,7 @@ __device__ __forceinline__ void contact_response(const Params& P, const Body& o,
         // a pair with the ball keeps w on both axes (fma(d, 0, w) == w)
         const float2 hd = held_diff(fo, fj);
         const float hr = rr ? 0.5f : 0.0f;
-        respond_axes(nx, ny, rs - d, oj.z - o.vx, oj.w - o.vy, wsum, ope, w, fma_(hd.x, hr, w), fma_(hd.y, hr, w), kt, mu, spin_c, beta, avx, avy, apx, apy, aw);
+        respond_axes<VN_SELECT>(nx, ny, rs - d, oj.z - o.vx, oj.w - o.vy, wsum, ope, w, fma_(hd.x, hr, w), fma_(hd.y, hr, w), kt, mu, spin_c, beta, avx, avy, apx, apy, aw);
         deep |= rs - d > pen2;
         return;
     }

@@ -4,6 +4,11 @@
 // at the start, the ball lane's reward / info / flags / episode counters at the end.  At the headline batch a launch lasts as long
 // as the instruction stream of its slowest wave, and half of the SIMDs are empty: the service wave runs on one of them.
 //
+// The physics wave's sub-steps (rsx_contact.hpp: physics, rsx_substep_body.inc) take the three sub-step cuts (SubstepCuts: one
+// ball-in-flight ballot per step and a loop without the flight gate and the ball-height ballot when every ball of the wave is down,
+// the normal impulse by select, the partner prefetch in every iteration): the wave that finishes last walks partners in every sub-step,
+// and each exec-mask branch chain it no longer runs there is a stall no other wave covers.  task_step_kernel<0,8,1,6,0> takes the same.
+//
 // The waves meet at two hardware barriers per step and exchange through LDS (PairBox, and Shared::x0 as before); nothing crosses a
 // launch and no array is added.  Results are those of task_step_kernel bit for bit: the same functions on the same floats.
 // Which handles run it: rsx_layout.hpp (StepPlan::service_wave).

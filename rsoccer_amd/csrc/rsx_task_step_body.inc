@@ -245,7 +245,14 @@
 
             // ---- physics ----
             RSX_STAMP(2);
-            physics<KIND, L, NR>(P, o, b, g, live, sh, cf);
+            // the sub-step cuts (rsx_contact.hpp: SubstepCuts) of the VSS-v0 3v3 eight-lane single-step kernels with literal coefficients,
+            // per kernel as measured; every other instantiation: none
+#ifdef RSX_STEP_PAIRED
+            constexpr int CUTS = RSX_SUBSTEP_CUTS_PAIR;
+#else
+            constexpr int CUTS = !PHYS && KIND == RSX_KIND_VSS && TASK == RSX_TASK_VSS_V0 && L == 8 && NR == 6 && MODE == MODE_STEP ? RSX_SUBSTEP_CUTS_LANES : 0;
+#endif
+            physics<KIND, L, NR, SubstepCuts<(CUTS & 1) != 0, (CUTS & 2) != 0, (CUTS & 4) != 0>>(P, o, b, g, live, sh, cf);
             RSX_STAMP(3);
             if (MODE == MODE_STEP && KIND == RSX_KIND_SSL) {
                 // Single-step launches of the SSL tasks: what the rest of the step reads of the parameter block is fetched from the kernarg
