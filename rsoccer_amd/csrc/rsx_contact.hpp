@@ -310,18 +310,24 @@ __device__ __forceinline__ bool ssl_sweep(const Params& P, Body& o, const int N,
 //              of a step stays down.  An airborne ball is caller-set state, and its wave runs the general loop, laid out behind.
 //   VN_SELECT  respond_axes computes the normal impulse for every walking lane and keeps the old sums by select (rsx_body.hpp)
 //   PREFETCH   the walk fetches the next partner's slot in every iteration; with no partner left, the current one's again
+//   EXCHANGE_ALL  every lane publishes its snapshot (and its held axes) and computes the overlap keys in every sweep, without the
+//              `active` guards; `any` is masked with `active` instead (which starts as the lane's role, robot or ball, and only
+//              shrinks).  A lane writes its own LDS slots and reads its own env's, and slot L - 1 of an env, the idle lane's, is read
+//              by nobody: what an idle or inactive lane publishes and tests disturbs no other lane
+//   ACT_SELECT the actuation and the heading advance run on every lane; the lanes that are no robot keep their bits by select
 // (A fourth, leaving a sweep in which no lane of the wave has a touching pair ahead of the deep ballot, was measured and lost on both
 // kernels, alone and on top of these three: profiles/LABBOOK.md.)
-template <bool GROUNDED, bool VN_SELECT, bool PREFETCH>
+template <bool GROUNDED, bool VN_SELECT, bool PREFETCH, bool EXCHANGE_ALL = false, bool ACT_SELECT = false>
 struct SubstepCuts {
-    static constexpr bool grounded = GROUNDED, vn_select = VN_SELECT, prefetch = PREFETCH;
+    static constexpr bool grounded = GROUNDED, vn_select = VN_SELECT, prefetch = PREFETCH, exchange_all = EXCHANGE_ALL, act_select = ACT_SELECT;
 };
 using NoSubstepCuts = SubstepCuts<false, false, false>;
-// The cuts of the two kernels that take any, as bits (1 GROUNDED, 2 VN_SELECT, 4 PREFETCH): task_pair_step_kernel<0,8,1,6,0> and
-// task_step_kernel<0,8,1,6,0>; both measured best with all three.  A -D on the compiler's line builds another combination
-// (tools/build_variant.py) for an A/B.
+// The cuts of the two kernels that take any, as bits (1 GROUNDED, 2 VN_SELECT, 4 PREFETCH, 8 EXCHANGE_ALL, 16 ACT_SELECT):
+// task_pair_step_kernel<0,8,1,6,0> and task_step_kernel<0,8,1,6,0>, each with what it measured best with (profiles/LABBOOK.md): the
+// paired kernel all five; the one-wave kernel the first three (the last two gain 2.2-2.6 % there, under three times its run-to-run range).
+// A -D on the compiler's line builds another combination (tools/build_variant.py) for an A/B.
 #ifndef RSX_SUBSTEP_CUTS_PAIR
-#define RSX_SUBSTEP_CUTS_PAIR 7
+#define RSX_SUBSTEP_CUTS_PAIR 31
 #endif
 #ifndef RSX_SUBSTEP_CUTS_LANES
 #define RSX_SUBSTEP_CUTS_LANES 7

@@ -8,6 +8,7 @@
 // ball-in-flight ballot per step and a loop without the flight gate and the ball-height ballot when every ball of the wave is down,
 // the normal impulse by select, the partner prefetch in every iteration): the wave that finishes last walks partners in every sub-step,
 // and each exec-mask branch chain it no longer runs there is a stall no other wave covers.  task_step_kernel<0,8,1,6,0> takes the same.
+// This kernel alone takes two more: the exchange of every sweep on all lanes and the actuation by select (measured per kernel).
 //
 // The waves meet at two hardware barriers per step and exchange through LDS (PairBox, and Shared::x0 as before); nothing crosses a
 // launch and no array is added.  Results are those of task_step_kernel bit for bit: the same functions on the same floats.
@@ -33,6 +34,13 @@ __device__ __forceinline__ void pair_barrier() {
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
+
+// The physics wave's head (rsx_task_step_body.inc, the line under RSX_PAIR_HEAD): every global load of the wave in front of barrier 1
+// is issued in front of ONE wait, one memory round trip instead of two.  -DRSX_PAIR_HEAD=0 on the compiler's line builds the head
+// without it for an A/B (tools/build_variant.py).
+#ifndef RSX_PAIR_HEAD
+#define RSX_PAIR_HEAD 1
+#endif
 
 // VSS-v0, eight lanes per env, single steps, literal coefficients: the one variant that is built (rsx_pair.hip)
 template <int KIND, int L, int TASK, int NR, int MODE>

@@ -8,6 +8,14 @@
         ts0 = __builtin_readcyclecounter();
 #endif
         // ---- A: actuation + integration ----
+        if constexpr (SC::act_select) {   // every lane computes, the robots keep the result (the ball and the idle lanes: their own bits)
+            Body t = o;
+            actuate_robot<KIND>(P, t, cf);
+            t.th = advance_heading(P, t.om, t.th);
+            rotate_heading(t.om * P.h, t.c, t.s);
+            o.vx = is_robot ? t.vx : o.vx; o.vy = is_robot ? t.vy : o.vy; o.om = is_robot ? t.om : o.om;
+            o.th = is_robot ? t.th : o.th; o.c = is_robot ? t.c : o.c; o.s = is_robot ? t.s : o.s;
+        } else
         if (is_robot) {   // rsx_body.hpp: the per-body arithmetic is stated once for all kernel layouts
             actuate_robot<KIND>(P, o, cf);
             o.th = advance_heading(P, o.om, o.th);
@@ -39,7 +47,7 @@
         BallOverride bo{false, false, 0.0f, 0.0f, 0.0f};
         for (int sweep = 0;; ++sweep) {
             float2 fo = float2{0.0f, 0.0f};   // VSS: this body's held axes in the snapshot of this sweep (robots; the ball publishes zeros)
-            if (active) {
+            if (SC::exchange_all || active) {   // (exchange_all: every lane, its own slots)
                 sh.A[lane] = make_float4(o.x, o.y, o.vx, o.vy);
                 sh.W[lane] = o.om;   // yaw rate / spin: read on the contact path only
                 sh.X[g * L + b] = o.x; sh.Y[g * L + b] = o.y;
@@ -58,7 +66,7 @@
 
             if (KIND == RSX_KIND_VSS) {
                 // every pair is circle-circle; only the constants depend on the pair type
-                if (active) {
+                if (SC::exchange_all || active) {
                     if (NR) {
                         // Overlap test of the whole sweep, exact and with ONE compare per partner class:
                         // d2 is a sum of squares (>= +0), and non-negative floats order like their bit
@@ -76,7 +84,10 @@
                         for (int j = 1; j < NR; ++j) um = min(um, u[j]);
                         // robot lane: robot slots are robot-robot pairs, slot NR the ball; ball lane:
                         // every robot slot is a robot-ball pair, slot NR itself (u = 0xFFFFFFFF)
-                        const bool any = ((um < (is_ball ? T_RB : T_RR)) & (!is_ball | ball_low)) | ((u[NR] < T_RB) & ball_low);
+                        bool any = ((um < (is_ball ? T_RB : T_RR)) & (!is_ball | ball_low)) | ((u[NR] < T_RB) & ball_low);
+                        // exchange_all: an idle lane (zeros: a body at the origin) and a lane of an env that sits this sweep out have
+                        // tested as well; `active` holds the lane's role and its env's part in the sweep
+                        if constexpr (SC::exchange_all) any = any & active;
                         if (RSX_RARE_B(KIND, 2, any)) {
                             // Each lane walks ITS partners in body-index order; lanes with different
                             // partners share an iteration, so a wave pays for the deepest lane (one

@@ -180,6 +180,13 @@
     // trip per env step in the multi-step (rollout) launches.
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
     if (CODE_PF) asm volatile("" :: "v"(code_touch));   // (the value itself is of no interest)
+#if defined(RSX_STEP_PAIRED) && RSX_PAIR_HEAD
+    // The paired form's physics wave has no arithmetic in the shadow of its loads, so a second round trip is all exposed.  There was
+    // one: the compiler placed the tail's `steps + 1` in the guarded block that loads the step counter, with a vmcnt(1) in front of it
+    // that drains the state rows, and the OU rows, the env-step counter and the fed actions were issued behind it.  The loaded
+    // scalars pass through here: no use of one can be scheduled ahead of the wait above.
+    asm volatile("" : "+v"(steps), "+v"(episode), "+v"(ou0), "+v"(ou1));
+#endif
     interpret_body<KIND>(raw, is_robot, is_ball, o, od, wd, wheels);
 #ifdef RSX_STEP_PAIRED
     RSX_STAMP(22);
@@ -252,7 +259,7 @@
 #else
             constexpr int CUTS = !PHYS && KIND == RSX_KIND_VSS && TASK == RSX_TASK_VSS_V0 && L == 8 && NR == 6 && MODE == MODE_STEP ? RSX_SUBSTEP_CUTS_LANES : 0;
 #endif
-            physics<KIND, L, NR, SubstepCuts<(CUTS & 1) != 0, (CUTS & 2) != 0, (CUTS & 4) != 0>>(P, o, b, g, live, sh, cf);
+            physics<KIND, L, NR, SubstepCuts<(CUTS & 1) != 0, (CUTS & 2) != 0, (CUTS & 4) != 0, (CUTS & 8) != 0, (CUTS & 16) != 0>>(P, o, b, g, live, sh, cf);
             RSX_STAMP(3);
             if (MODE == MODE_STEP && KIND == RSX_KIND_SSL) {
                 // Single-step launches of the SSL tasks: what the rest of the step reads of the parameter block is fetched from the kernarg
