@@ -1,6 +1,7 @@
 """PPO on VSS-v0 with every rollout collected in one launch.
 
-    python examples/ppo_vss.py [--envs 1024] [--steps 128] [--updates 10] [--epochs 4] [--minibatches 4] [--lr 3e-4] [--fused-update]
+    python examples/ppo_vss.py [--envs 1024] [--steps 128] [--updates 10] [--epochs 4] [--minibatches 4] [--lr 3e-4]
+                               [--fused-update | --device-update [--graph]] [--target-kl 0.02]
 
 One update: env.collect(...) advances the envs `steps` steps under the current actor — the MLP evaluated inside the engine's launch, a
 Gaussian head on top, episode ends handled in the launch — and, given the critic, evaluates it on the recorded observations and runs
@@ -10,7 +11,10 @@ The actor's and the critic's weights reach the engine as flat vectors (MLPPolicy
 density PPO compares is the pre-activation one: log N(sample; mean, exp(log_std)), where the action fed to the env is clip(sample) —
 the trainer evaluates the same expression on the recorded `sample`, so the ratio is exact.  With --fused-update the loss and its
 gradients come from the engine as well (env.ppo_gradient: three launches per minibatch): the leaves are the flat parameter vectors, the
-call's outputs become their .grad, and Adam steps on three tensors.  A demonstration of the call pattern, not a tuned trainer."""
+call's outputs become their .grad, and Adam steps on three tensors.  With --device-update the whole inner loop is ONE call
+(env.ppo_update: advantage normalisation, a keyed permutation per epoch, the gradients, the global-norm clip and Adam per minibatch, all
+stream-ordered with the optimiser's state and counters on the device); --graph captures collect + ppo_update once on a device-keyed
+env and replays it: one replay is one PPO iteration.  A demonstration of the call pattern, not a tuned trainer."""
 import argparse
 import os
 import sys
@@ -28,6 +32,53 @@ def log_prob(mean, log_std, sample):
     return (-0.5 * z * z - log_std - 0.9189385332046727).sum(-1)
 
 
+def device_update(args):
+    """the loop with the update phase on the device; with --graph one replay per iteration"""
+    from rsoccer_amd.vec.optim import PPOOptimizer
+    torch.manual_seed(args.seed)
+    env = VecVSSEnv(args.envs, device=0, seed=args.seed)
+    dev, OD, AD = env.device, env.sim.obs_dim, env.sim.act_dim
+    pol = MLPPolicy(OD, AD, hidden=64, layers=2, hidden_act="tanh", out_act="clip")
+    val = MLPCritic(OD, hidden=64, layers=2, hidden_act="tanh")
+    actor = torch.nn.Sequential(torch.nn.Linear(OD, 64), torch.nn.Tanh(), torch.nn.Linear(64, 64), torch.nn.Tanh(), torch.nn.Linear(64, AD))
+    critic = torch.nn.Sequential(torch.nn.Linear(OD, 64), torch.nn.Tanh(), torch.nn.Linear(64, 64), torch.nn.Tanh(), torch.nn.Linear(64, 1))
+    # plain tensors, updated in place by the engine: no autograd anywhere in this loop
+    p_actor, p_critic = pol.from_module(actor).to(dev), val.from_module(critic).to(dev)
+    log_std = torch.full((AD,), -0.5, device=dev)
+    opt = PPOOptimizer(pol, val, device=dev, lr=args.lr, max_grad_norm=args.max_grad_norm)
+    env.reset()
+    if args.graph:
+        env.enable_graph_capture()   # the step counter moves to the device: collect() draws fresh noise on every replay
+
+    def iteration():
+        # (noise_seed fixed: the draws are keyed by the step counter, which advances; the permutations by opt's update count)
+        batch = env.collect(pol, p_actor, args.steps, log_std=log_std, noise_seed=args.seed + 1, critic=val, critic_params=p_critic,
+                            gamma=args.gamma, lam=args.lam)
+        out = env.ppo_update(batch, pol, p_actor, log_std, val, p_critic, opt, epochs=args.epochs, minibatches=args.minibatches,
+                             clip=args.clip, vf_coef=0.5, target_kl=args.target_kl, seed=args.seed)
+        return batch["reward"].mean(), out["stats"]
+
+    graph = None
+    for update in range(args.updates):
+        t0 = time.perf_counter()
+        if args.graph and update == 1:   # (iteration 0 ran eagerly: torch's warm-up before a capture)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                reward, stats = iteration()
+        if graph is not None:
+            graph.replay()
+        else:
+            reward, stats = iteration()
+        torch.cuda.synchronize()
+        m = env.metrics()
+        last = stats[-1, -1]
+        print(f"update {update}: mean reward / step {float(reward):+.5f}, episodes {m['episodes']}, goals for / against "
+              f"{m['goals_for']} / {m['goals_against']}, sigma {log_std.exp().mean().item():.3f}, loss_pi {float(last[0]):+.5f}, "
+              f"loss_v {float(last[1]):.5f}, steps applied {int(stats[:, :, 9].sum())} / {stats.shape[0] * stats.shape[1]}; "
+              f"collect + advantages + update {(time.perf_counter() - t0) * 1e3:.1f} ms{' (one graph replay)' if graph is not None else ''}")
+    env.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=1024)
@@ -41,7 +92,15 @@ def main():
     ap.add_argument("--clip", type=float, default=0.2)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--fused-update", action="store_true", help="loss and gradients of a minibatch from env.ppo_gradient instead of torch")
+    ap.add_argument("--device-update", action="store_true", help="the whole update phase in one call: env.ppo_update with a PPOOptimizer")
+    ap.add_argument("--graph", action="store_true", help="with --device-update: capture collect + ppo_update once, replay it per iteration")
+    ap.add_argument("--max-grad-norm", type=float, default=0.5, help="--device-update: the global-norm clip (<= 0: none)")
+    ap.add_argument("--target-kl", type=float, default=None, help="--device-update: stop an update's steps once approx_kl exceeds this")
     args = ap.parse_args()
+    if args.graph and not args.device_update:
+        ap.error("--graph needs --device-update")
+    if args.device_update:
+        return device_update(args)
 
     torch.manual_seed(args.seed)
     env = VecVSSEnv(args.envs, device=0, seed=args.seed)

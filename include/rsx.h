@@ -656,6 +656,133 @@ int rsx_task_ppo_gradient(rsx_sim* h, const rsx_policy_mlp* actor, const float* 
                           const rsx_policy_mlp* critic, const float* critic_params_dev,
                           const rsx_ppo_in* in, const rsx_ppo_cfg* cfg, const rsx_ppo_out* out, void* stream);
 
+/* ---- the PPO update phase on the device: normalise, shuffle, clip, Adam, KL stop (additive extension of ABI 6) ---------------------
+ * What an on-policy trainer does around rsx_task_ppo_gradient: normalise the advantages once per batch, draw a fresh permutation of
+ * the rows per epoch, and per minibatch clip the gradient's global norm and take an Adam step — here stream-ordered and keyed by
+ * counters that live on the device, so that rsx_task_collect_policy + rsx_task_ppo_update captured once is one whole PPO iteration
+ * per replay.  rsx_ppo_normalize, rsx_ppo_permutation, rsx_adam_step and rsx_adam_mark take no handle: they run on the thread's current
+ * device.  Every call is stream-ordered, never synchronises, never allocates and is capturable; invalid arguments are refused with
+ * RSX_ERR_ARG before anything is enqueued (rsx_last_error says why); no float atomics: the result bits are a function of the inputs
+ * (and, for rsx_task_ppo_update, of max_workgroups) alone.
+ *
+ * Reductions (the two moments of the advantages, the squared gradient norm) share one FIXED order, in float64: thread j of workgroup w
+ * (256 threads, G workgroups, G = min(ceil(n / 256), C) with C a constant of the build: 128 for the moments, 64 for the norm) adds
+ * its elements i = 256 w + j, + 256 G, ... ascending, from 0.0; a workgroup adds the 64 lanes of each of its four waves ascending
+ * from 0.0 and then the waves ((w0 + w1) + w2) + w3; the G partials are added in workgroup order from 0.0.
+ *
+ * rsx_ppo_normalize:  out[i] = (adv[i] - mean) / (std + eps)  over n entries, in two launches.
+ *   S = sum x, Q = sum x * x (the float32 entries widened; reduced as above);  mean64 = S / n;  var64 = (Q - S * mean64) / (n - 1)
+ *   (Bessel's correction, as torch's std()), a negative var64 is 0;  mean = (float)mean64, std = (float)sqrt(var64);  then per entry a
+ *   float32 subtraction, addition and division, each rounded.  mean_std_dev [2] or NULL receives mean and std.  out_dev must not
+ *   overlap adv_dev.  workspace_dev: RSX_PPO_NORMALIZE_WORKSPACE_BYTES, 8-byte aligned.  Refused: a null adv_dev, out_dev or
+ *   workspace_dev, n < 2 (no standard deviation) or n > 2^31 - 1, eps negative or non-finite. */
+#define RSX_PPO_NORMALIZE_WORKSPACE_BYTES 2048
+int rsx_ppo_normalize(const float* adv_dev, int64_t n, float eps, float* out_dev, float* mean_std_dev, void* workspace_dev, void* stream);
+/* rsx_ppo_permutation:  rows_dev [n] int32 := a permutation of 0 .. n - 1, every entry computed on its own from (seed, update, epoch,
+ * i) — no sort, no state.  All arithmetic is on 32-bit unsigned integers:
+ *   bits = max(8, ceil(log2 n)), the domain is [0, 2^bits);  wa = bits / 2 (integer), wb = bits - wa  (at least 8 bits: halves
+ *          narrower than four bits mix too slowly for eight rounds — measured on the host restatement, profiles/LABBOOK.md)
+ *   E(x):  a = x & (2^wa - 1), b = x >> wa;  for r = 0 .. 7:  f = word 0 of philox4x32-7(counter = (b, epoch, update, 8 | r << 8), key =
+ *          (seed lo, seed hi));  (a, b) := (b, (a ^ f) & (2^wa - 1));  swap wa and wb.   E(x) = a | b << wa
+ *          (an unbalanced Feistel network: each round is invertible whatever f is, so E is a bijection of the domain)
+ *   rows[i]:  x = E(i); while x >= n: x = E(x)      (cycle walking: the walk follows i's cycle of E, which holds at most 2^bits - n
+ *          values outside [0, n), so it ends within 2^bits - n + 1 applications — the bound of the kernel's loop; for n >= 128,
+ *          2^bits < 2 n makes the expected number less than 2)
+ *   update   the low 32 bits of `update`, or, with update_dev != NULL, of the int64 it points to, read on the device when the launch
+ *            runs: pass rsx_adam_state.counters + RSX_ADAM_UPDATES and a replayed graph draws a new permutation on every replay (the
+ *            tick design of the engine's other draws).
+ * Minibatch k of M covers rows[k c .. min((k + 1) c, n)) with c = ceil(n / M): torch.chunk's sizes.
+ * Refused: a null rows_dev, n < 1 or n > 2^31 - 1, epoch outside [0, 2^32). */
+int rsx_ppo_permutation(int32_t* rows_dev, int64_t n, uint64_t seed, uint64_t update, const int64_t* update_dev, int64_t epoch, void* stream);
+/* rsx_adam_step:  torch.nn.utils.clip_grad_norm_ followed by torch.optim.Adam (no amsgrad, no weight decay) on three flat tensors —
+ * the actor's parameters, log_std and the critic's parameters — in two launches.
+ *   counters   int64 [4] device memory, part of the optimiser state (zero at the start of training): */
+#define RSX_ADAM_T       0   /* Adam's step count t */
+#define RSX_ADAM_UPDATES 1   /* updates finished (rsx_adam_mark end / rsx_task_ppo_update): the permutation's key */
+#define RSX_ADAM_APPLIED 2   /* steps applied since the last update began */
+#define RSX_ADAM_STOPPED 3   /* non-zero: the KL stop was hit in the current update; every later step is withheld */
+/*   norm   = (float)sqrt(sum g^2) over the concatenation actor | log_std | critic, reduced as above (each g widened, g * g exact)
+ *   coef   = min(1, max_grad_norm / (norm + 1e-6f)) in float32;  max_grad_norm <= 0: coef = 1 (no clipping)
+ *   the gate   with target_kl > 0 and approx_kl != NULL, a step whose approx_kl[0] is not <= target_kl (a NaN included) sets STOPPED
+ *          before its own step.  A step with STOPPED set is WITHHELD: it changes no parameter, no moment and not t (selected, never
+ *          multiplied by 0; its launches still run — the price of not asking the host).  Otherwise t := t + 1, APPLIED += 1 and
+ *   bc1 = 1 - beta1^t, bc2 = 1 - beta2^t in float64 from the device's t;  beta^t by squaring (r = 1; while t: if t & 1: r *= b;
+ *          b *= b; t >>= 1), so that the bits can be restated on a host
+ *   g' = g * coef;   m = b1 * m + omb1 * g';   v = b2 * v + (omb2 * g') * g';   p = p - step * (m / (sqrtf(v) / s2 + eps))
+ *          in float32, every operation rounded, with b = (float)beta, omb = (float)(1.0 - beta), step = (float)((double)lr / bc1),
+ *          s2 = (float)sqrt(bc2).  A gradient entry that is 0 while its m is 0 leaves its parameter as it was.
+ *   lr     cfg->lr, or with cfg->lr_dev != NULL the float it points to, read on the device (a schedule under graph replay).
+ *   stats  [2] or NULL: the norm before the clip; 1.0f when the step was applied, 0.0f when it was withheld.
+ *   workspace   RSX_ADAM_WORKSPACE_BYTES, 8-byte aligned.
+ * Refused: a null cfg, st, io or required array; a size < 1 or a total above 2^31 - 1; lr or eps negative or non-finite; a beta outside
+ * [0, 1); max_grad_norm or target_kl non-finite, target_kl negative. */
+#define RSX_ADAM_WORKSPACE_BYTES 1024
+typedef struct rsx_adam_cfg {
+    double       beta1;          /* in [0, 1) */
+    double       beta2;          /* in [0, 1) */
+    const float* lr_dev;         /* [1] device memory, or NULL = lr */
+    float        lr;             /* >= 0, finite */
+    float        eps;            /* >= 0, finite */
+    float        max_grad_norm;  /* <= 0: no clipping */
+    float        target_kl;      /* 0: no KL stop; > 0: see the gate */
+} rsx_adam_cfg;
+typedef struct rsx_adam_state {
+    float*   m_actor;     /* [n_actor] */
+    float*   v_actor;
+    float*   m_log_std;   /* [n_log_std] */
+    float*   v_log_std;
+    float*   m_critic;    /* [n_critic] */
+    float*   v_critic;
+    int64_t* counters;    /* [4], RSX_ADAM_* */
+    int64_t  n_actor;
+    int64_t  n_log_std;
+    int64_t  n_critic;
+} rsx_adam_state;
+typedef struct rsx_adam_io {
+    float*       actor_params;   /* [n_actor]    updated in place   required */
+    float*       log_std;        /* [n_log_std]  updated in place   required */
+    float*       critic_params;  /* [n_critic]   updated in place   required */
+    const float* grad_actor;     /* required */
+    const float* grad_log_std;   /* required */
+    const float* grad_critic;    /* required */
+    const float* approx_kl;      /* [1] or NULL: what the gate compares with target_kl */
+    float*       stats;          /* [2] or NULL */
+    void*        workspace;      /* RSX_ADAM_WORKSPACE_BYTES   required */
+} rsx_adam_io;
+int rsx_adam_step(const rsx_adam_cfg* cfg, const rsx_adam_state* st, const rsx_adam_io* io, void* stream);
+/* end == 0: an update begins (APPLIED := 0, STOPPED := 0);  end != 0: it ends (UPDATES += 1).  One tiny launch. */
+int rsx_adam_mark(const rsx_adam_state* st, int end, void* stream);
+/* rsx_task_ppo_update:  the whole update phase in one call.  It enqueues, in this order: rsx_adam_mark(begin); with
+ * normalize_advantage, rsx_ppo_normalize of in->advantage into the workspace (once per batch); per epoch e = 0 .. epochs - 1
+ * rsx_ppo_permutation(n = n_batch_rows, seed, update = the DEVICE's counters[RSX_ADAM_UPDATES], epoch = e) into the workspace, and per
+ * minibatch k rsx_task_ppo_gradient on rows[k c .. min((k + 1) c, n)) (c = ceil(n / minibatches)) with the normalised advantages,
+ * followed by rsx_adam_step with approx_kl = that gradient call's stats[3];  rsx_adam_mark(end).  The results equal that sequence of
+ * calls bit for bit.
+ *   the handle, actor, critic, in, cfg    as for rsx_task_ppo_gradient; in->rows must be NULL and in->n_rows is ignored.
+ *   actor_params_dev, log_std_dev, critic_params_dev   updated in place.  Nothing `in` points to is written.
+ *   stats_dev   [epochs][minibatches][RSX_PPO_UPDATE_STATS]: rsx_task_ppo_gradient's eight, 8 the gradient norm before the clip, 9
+ *               whether the step was applied
+ *   workspace   rsx_ppo_update_workspace bytes, 16-byte aligned: rsx_task_ppo_gradient's for c rows, the rows, the normalised
+ *               advantages, the three gradients and the partials.  rows_offset_out (or NULL): where in it the int32 rows [n] of the
+ *               last epoch lie after the call.
+ * Refused: everything rsx_task_ppo_gradient and rsx_adam_step refuse; a null u, stats_dev or workspace; epochs < 1; minibatches < 1 or
+ * so many that the last chunk would be empty ((minibatches - 1) * c >= n); n_batch_rows < 2 with normalize_advantage; norm_eps negative
+ * or non-finite; a non-NULL in->rows; state sizes (st->n_*) that are not the two networks' and act_dim. */
+#define RSX_PPO_UPDATE_STATS 10
+typedef struct rsx_ppo_update_cfg {
+    uint64_t seed;                 /* the permutations' key */
+    int32_t  epochs;               /* >= 1 */
+    int32_t  minibatches;          /* >= 1 */
+    int32_t  normalize_advantage;  /* 0 | 1 */
+    float    norm_eps;             /* rsx_ppo_normalize's eps */
+} rsx_ppo_update_cfg;
+int rsx_ppo_update_workspace(const rsx_sim* h, const rsx_policy_mlp* actor, const rsx_policy_mlp* critic, int64_t n_batch_rows,
+                             int minibatches, int max_workgroups, int64_t* bytes_out, int64_t* rows_offset_out);
+int rsx_task_ppo_update(rsx_sim* h, const rsx_policy_mlp* actor, float* actor_params_dev, float* log_std_dev,
+                        const rsx_policy_mlp* critic, float* critic_params_dev, const rsx_ppo_in* in, const rsx_ppo_cfg* cfg,
+                        const rsx_ppo_update_cfg* u, const rsx_adam_cfg* adam, const rsx_adam_state* st, float* stats_dev,
+                        void* workspace, void* stream);
+
 /* Debugging aid: number of non-finite floats in the state rows and, with a task attached, in the
  * observations, rewards and info rows.  Synchronises `stream`.  With RSX_DEBUG_FINITE=1 in the
  * environment every stepping call (rsx_step_dev, rsx_task_step, rsx_task_step_n, rsx_task_rollout, rsx_task_collect_policy)

@@ -55,6 +55,7 @@ SYMBOLS = (
     "rsx_task_collect_policy",
     "rsx_critic_num_params", "rsx_task_advantages",
     "rsx_ppo_gradient_workspace", "rsx_task_ppo_gradient",
+    "rsx_ppo_normalize", "rsx_ppo_permutation", "rsx_adam_step", "rsx_adam_mark", "rsx_ppo_update_workspace", "rsx_task_ppo_update",
 )
 # activations of rsx_policy_mlp (include/rsx.h: RSX_ACT_*)
 ACT_RELU, ACT_TANH, ACT_CLIP = 0, 1, 2
@@ -112,6 +113,41 @@ class PpoOut(C.Structure):
 
 # the slots of rsx_ppo_out.stats, in order
 PPO_STATS = ("loss_pi", "loss_v", "entropy", "approx_kl", "clip_fraction", "ratio", "rows_used", "rows_skipped")
+
+
+# the update phase (include/rsx.h: rsx_ppo_normalize, rsx_adam_step, rsx_task_ppo_update)
+PPO_NORMALIZE_WORKSPACE_BYTES, ADAM_WORKSPACE_BYTES = 2048, 1024
+# the slots of rsx_adam_state.counters (RSX_ADAM_*), and of one row of rsx_task_ppo_update's stats: PPO_STATS and two more
+ADAM_COUNTERS = ("t", "updates", "applied", "stopped")
+PPO_UPDATE_STATS = PPO_STATS + ("grad_norm", "applied")
+
+
+class AdamCfg(C.Structure):
+    """rsx_adam_cfg (include/rsx.h): the betas as doubles, lr by value or as a device address (lr_dev, None = lr), eps, the clip's
+    max_grad_norm (<= 0: none) and the KL stop's target_kl (0: none)"""
+    _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("lr_dev", C.c_void_p), ("lr", C.c_float), ("eps", C.c_float),
+                ("max_grad_norm", C.c_float), ("target_kl", C.c_float)]
+
+
+class AdamState(C.Structure):
+    """rsx_adam_state (include/rsx.h): m and v of the three flat tensors, the int64 counters [4] and the three sizes; device addresses"""
+    _fields_ = [("m_actor", C.c_void_p), ("v_actor", C.c_void_p), ("m_log_std", C.c_void_p), ("v_log_std", C.c_void_p),
+                ("m_critic", C.c_void_p), ("v_critic", C.c_void_p), ("counters", C.c_void_p),
+                ("n_actor", C.c_int64), ("n_log_std", C.c_int64), ("n_critic", C.c_int64)]
+
+
+class AdamIo(C.Structure):
+    """rsx_adam_io (include/rsx.h): the three parameter tensors (updated in place), their gradients, the optional approx_kl [1] and
+    stats [2], and the workspace; device addresses"""
+    _fields_ = [("actor_params", C.c_void_p), ("log_std", C.c_void_p), ("critic_params", C.c_void_p), ("grad_actor", C.c_void_p),
+                ("grad_log_std", C.c_void_p), ("grad_critic", C.c_void_p), ("approx_kl", C.c_void_p), ("stats", C.c_void_p),
+                ("workspace", C.c_void_p)]
+
+
+class PpoUpdateCfg(C.Structure):
+    """rsx_ppo_update_cfg (include/rsx.h): the permutations' seed, epochs, minibatches, whether and with which eps advantages are normalised"""
+    _fields_ = [("seed", C.c_uint64), ("epochs", C.c_int32), ("minibatches", C.c_int32), ("normalize_advantage", C.c_int32),
+                ("norm_eps", C.c_float)]
 
 
 class DevView(C.Structure):
@@ -218,6 +254,14 @@ def load():
     lib.rsx_ppo_gradient_workspace.argtypes = [vp, C.POINTER(PolicyMLP), C.POINTER(PolicyMLP), C.c_int64, ip, C.POINTER(C.c_int64)]
     lib.rsx_task_ppo_gradient.argtypes = [vp, C.POINTER(PolicyMLP), vp, vp, C.POINTER(PolicyMLP), vp, C.POINTER(PpoIn), C.POINTER(PpoCfg),
                                           C.POINTER(PpoOut), vp]
+    lib.rsx_ppo_normalize.argtypes = [vp, C.c_int64, C.c_float, vp, vp, vp, vp]
+    lib.rsx_ppo_permutation.argtypes = [vp, C.c_int64, C.c_uint64, C.c_uint64, vp, C.c_int64, vp]
+    lib.rsx_adam_step.argtypes = [C.POINTER(AdamCfg), C.POINTER(AdamState), C.POINTER(AdamIo), vp]
+    lib.rsx_adam_mark.argtypes = [C.POINTER(AdamState), ip, vp]
+    lib.rsx_ppo_update_workspace.argtypes = [vp, C.POINTER(PolicyMLP), C.POINTER(PolicyMLP), C.c_int64, ip, ip, C.POINTER(C.c_int64),
+                                             C.POINTER(C.c_int64)]
+    lib.rsx_task_ppo_update.argtypes = [vp, C.POINTER(PolicyMLP), vp, vp, C.POINTER(PolicyMLP), vp, C.POINTER(PpoIn), C.POINTER(PpoCfg),
+                                        C.POINTER(PpoUpdateCfg), C.POINTER(AdamCfg), C.POINTER(AdamState), vp, vp, vp]
     lib.rsx_physics_defaults.argtypes = [ip, vp]
     lib.rsx_physics_derive.argtypes = [ip, ip, vp, vp]
     lib.rsx_physics_enable.argtypes = [vp, vp]
@@ -253,6 +297,36 @@ def _chk(rc):
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+# ---- the handle-free calls of the update phase: they run on the thread's current device (the callers make theirs current) ----
+def ppo_normalize(adv_ptr, n, eps, out_ptr, mean_std_ptr, workspace_ptr, stream=None):
+    """rsx_ppo_normalize: out = (adv - mean) / (std + eps) over n float32 entries, in two launches"""
+    rc = load().rsx_ppo_normalize(adv_ptr, int(n), float(eps), out_ptr, mean_std_ptr, workspace_ptr, stream)
+    if rc:
+        _chk(rc)
+
+
+def ppo_permutation(rows_ptr, n, seed, update, update_ptr, epoch, stream=None):
+    """rsx_ppo_permutation: rows [n] int32 := the permutation of 0 .. n - 1 keyed by (seed, update or the int64 at update_ptr, epoch)"""
+    rc = load().rsx_ppo_permutation(rows_ptr, int(n), int(seed) & ((1 << 64) - 1), int(update) & ((1 << 64) - 1), update_ptr, int(epoch), stream)
+    if rc:
+        _chk(rc)
+
+
+def adam_step(cfg, state, io, stream=None):
+    """rsx_adam_step: the global-norm clip and one Adam step on the three flat tensors, in two launches"""
+    rc = load().rsx_adam_step(None if cfg is None else C.byref(cfg), None if state is None else C.byref(state),
+                              None if io is None else C.byref(io), stream)
+    if rc:
+        _chk(rc)
+
+
+def adam_mark(state, end, stream=None):
+    """rsx_adam_mark: an update begins (end = False: applied and stopped are cleared) or ends (the update count advances)"""
+    rc = load().rsx_adam_mark(None if state is None else C.byref(state), 1 if end else 0, stream)
+    if rc:
+        _chk(rc)
 
 
 def _f64(a, shape):
@@ -605,6 +679,23 @@ class Sim:
                                              None if critic is None else C.byref(critic), critic_params_ptr,
                                              None if inp is None else C.byref(inp), None if cfg is None else C.byref(cfg),
                                              None if out is None else C.byref(out), stream)
+        if rc:
+            _chk(rc)
+
+    def ppo_update_workspace(self, actor, critic, n_batch_rows, minibatches, max_workgroups=0):
+        """rsx_ppo_update_workspace: (bytes of scratch rsx_task_ppo_update needs, the offset of its int32 rows in it)"""
+        n, off = C.c_int64(0), C.c_int64(0)
+        _chk(self._lib.rsx_ppo_update_workspace(self._h, None if actor is None else C.byref(actor), None if critic is None else C.byref(critic),
+                                                int(n_batch_rows), int(minibatches), int(max_workgroups), C.byref(n), C.byref(off)))
+        return int(n.value), int(off.value)
+
+    def task_ppo_update(self, actor, actor_params_ptr, log_std_ptr, critic, critic_params_ptr, inp, cfg, ucfg, adam, state, stats_ptr,
+                        workspace_ptr, stream=None):
+        """rsx_task_ppo_update: the whole update phase of PPO enqueued by one call — normalisation, per epoch a permutation, per minibatch
+        the gradients and the clip + Adam step; the parameters are updated in place.  Reads and writes nothing of the envs."""
+        b = lambda x: None if x is None else C.byref(x)   # noqa: E731
+        rc = self._lib.rsx_task_ppo_update(self._h, b(actor), actor_params_ptr, log_std_ptr, b(critic), critic_params_ptr, b(inp), b(cfg),
+                                           b(ucfg), b(adam), b(state), stats_ptr, workspace_ptr, stream)
         if rc:
             _chk(rc)
 

@@ -485,6 +485,115 @@ int rsx_task_ppo_gradient(rsx_sim* h, const rsx_policy_mlp* actor, const float* 
     return RSX_OK;
 }
 
+// ---- the update phase around it (rsx.h: rsx_ppo_normalize, rsx_ppo_permutation, rsx_adam_step, rsx_adam_mark, rsx_task_ppo_update) ----
+// what rsx_adam_step and rsx_task_ppo_update check of an optimiser's configuration and state
+static int adam_prologue(const rsx_adam_cfg* c, const rsx_adam_state* st) {
+    if (!c) return fail(RSX_ERR_ARG, "the optimiser's configuration (rsx_adam_cfg) must not be null");
+    if (!(std::isfinite(c->lr) && c->lr >= 0.0f)) return fail(RSX_ERR_ARG, "lr must be finite and >= 0");
+    if (!(std::isfinite(c->eps) && c->eps >= 0.0f)) return fail(RSX_ERR_ARG, "eps must be finite and >= 0");
+    if (!(c->beta1 >= 0.0 && c->beta1 < 1.0) || !(c->beta2 >= 0.0 && c->beta2 < 1.0)) return fail(RSX_ERR_ARG, "beta1 and beta2 must be in [0, 1)");
+    if (!std::isfinite(c->max_grad_norm)) return fail(RSX_ERR_ARG, "max_grad_norm must be finite (<= 0: no clipping)");
+    if (!(std::isfinite(c->target_kl) && c->target_kl >= 0.0f)) return fail(RSX_ERR_ARG, "target_kl must be finite and >= 0 (0: no KL stop)");
+    if (!st) return fail(RSX_ERR_ARG, "the optimiser's state (rsx_adam_state) must not be null");
+    if (!st->m_actor || !st->v_actor || !st->m_log_std || !st->v_log_std || !st->m_critic || !st->v_critic || !st->counters)
+        return fail(RSX_ERR_ARG, "the state's m, v and counters arrays must not be null");
+    if (st->n_actor < 1 || st->n_log_std < 1 || st->n_critic < 1 || st->n_actor > 0x7FFFFFFFll || st->n_log_std > 0x7FFFFFFFll ||
+        st->n_critic > 0x7FFFFFFFll || st->n_actor + st->n_log_std + st->n_critic > 0x7FFFFFFFll)
+        return fail(RSX_ERR_ARG, "n_actor, n_log_std and n_critic must be >= 1 and their sum at most 2^31 - 1");
+    return RSX_OK;
+}
+
+int rsx_ppo_normalize(const float* adv_dev, int64_t n, float eps, float* out_dev, float* mean_std_dev, void* workspace_dev, void* stream) {
+    (void)launch_status();
+    if (!adv_dev || !out_dev || !workspace_dev) return fail(RSX_ERR_ARG, "adv_dev, out_dev and workspace_dev must not be null");
+    if (n < 2 || n > 0x7FFFFFFFll) return fail(RSX_ERR_ARG, "n must be in 2 .. 2^31 - 1 (one entry has no standard deviation)");
+    if (!(std::isfinite(eps) && eps >= 0.0f)) return fail(RSX_ERR_ARG, "eps must be finite and >= 0");
+    launch_ppo_normalize(adv_dev, n, eps, out_dev, mean_std_dev, workspace_dev, (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
+int rsx_ppo_permutation(int32_t* rows_dev, int64_t n, uint64_t seed, uint64_t update, const int64_t* update_dev, int64_t epoch, void* stream) {
+    (void)launch_status();
+    if (!rows_dev) return fail(RSX_ERR_ARG, "rows_dev must not be null");
+    if (n < 1 || n > 0x7FFFFFFFll) return fail(RSX_ERR_ARG, "n must be in 1 .. 2^31 - 1");
+    if (epoch < 0 || epoch > 0xFFFFFFFFll) return fail(RSX_ERR_ARG, "epoch must be in 0 .. 2^32 - 1");
+    launch_ppo_permutation(rows_dev, n, seed, (uint32_t)update, reinterpret_cast<const long long*>(update_dev), (uint32_t)epoch, (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
+int rsx_adam_step(const rsx_adam_cfg* cfg, const rsx_adam_state* st, const rsx_adam_io* io, void* stream) {
+    (void)launch_status();
+    if (int rc = adam_prologue(cfg, st)) return rc;
+    if (!io || !io->actor_params || !io->log_std || !io->critic_params || !io->grad_actor || !io->grad_log_std || !io->grad_critic || !io->workspace)
+        return fail(RSX_ERR_ARG, "io and its parameter, gradient and workspace arrays must not be null");
+    launch_adam_step(*cfg, *st, *io, (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
+int rsx_adam_mark(const rsx_adam_state* st, int end, void* stream) {
+    (void)launch_status();
+    if (!st || !st->counters) return fail(RSX_ERR_ARG, "the state and its counters must not be null");
+    launch_update_mark(st->counters, end ? 1 : 0, (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
+// what both calls check of the batch's size and its split
+static int update_split(int64_t n_batch_rows, int minibatches) {
+    if (n_batch_rows < 1 || n_batch_rows > 0x7FFFFFFFll) return fail(RSX_ERR_ARG, "n_batch_rows must be in 1 .. 2^31 - 1");
+    if (minibatches < 1) return fail(RSX_ERR_ARG, "minibatches must be >= 1");
+    if ((int64_t)(minibatches - 1) * ppo_update_chunk(n_batch_rows, minibatches) >= n_batch_rows)
+        return fail(RSX_ERR_ARG, "minibatches: the last chunk of ceil(n / minibatches) rows would be empty");
+    return RSX_OK;
+}
+
+int rsx_ppo_update_workspace(const rsx_sim* h, const rsx_policy_mlp* actor, const rsx_policy_mlp* critic, int64_t n_batch_rows,
+                             int minibatches, int max_workgroups, int64_t* bytes_out, int64_t* rows_offset_out) {
+    if (!h) return fail(RSX_ERR_ARG, "null handle");
+    if (!bytes_out) return fail(RSX_ERR_ARG, "bytes_out must not be null");
+    PolicySpec SA, SC; int64_t na = 0, nc = 0;
+    if (int rc = ppo_prologue(h, actor, critic, &SA, &na, &SC, &nc)) return rc;
+    if (int rc = update_split(n_batch_rows, minibatches)) return rc;
+    if (max_workgroups < 0) return fail(RSX_ERR_ARG, "max_workgroups must be >= 0");
+    long long off = 0;
+    *bytes_out = ppo_update_workspace_bytes(na, nc, h->M.act_dim, n_batch_rows, minibatches, max_workgroups, &off);
+    if (rows_offset_out) *rows_offset_out = off;
+    return RSX_OK;
+}
+
+int rsx_task_ppo_update(rsx_sim* h, const rsx_policy_mlp* actor, float* actor_params_dev, float* log_std_dev, const rsx_policy_mlp* critic,
+                        float* critic_params_dev, const rsx_ppo_in* in, const rsx_ppo_cfg* cfg, const rsx_ppo_update_cfg* u,
+                        const rsx_adam_cfg* adam, const rsx_adam_state* st, float* stats_dev, void* workspace, void* stream) {
+    RSX_ENTER(h);   // (nothing the handle owns is read or written by the launches)
+    PolicySpec SA, SC; int64_t na = 0, nc = 0;
+    if (int rc = ppo_prologue(h, actor, critic, &SA, &na, &SC, &nc)) return rc;
+    if (!actor_params_dev || !log_std_dev || !critic_params_dev)
+        return fail(RSX_ERR_ARG, "actor_params_dev, log_std_dev and critic_params_dev must not be null");
+    if (!in || !in->obs || !in->sample || !in->old_log_prob || !in->advantage || !in->ret)
+        return fail(RSX_ERR_ARG, "in and its obs, sample, old_log_prob, advantage and ret arrays must not be null");
+    if (in->rows) return fail(RSX_ERR_ARG, "in->rows must be NULL: the update draws its own rows");
+    if (!cfg) return fail(RSX_ERR_ARG, "cfg must not be null");
+    if (!(std::isfinite(cfg->clip) && cfg->clip > 0.0f && cfg->clip < 1.0f)) return fail(RSX_ERR_ARG, "clip must be in (0, 1)");
+    if (!std::isfinite(cfg->vf_coef) || !std::isfinite(cfg->ent_coef)) return fail(RSX_ERR_ARG, "vf_coef and ent_coef must be finite");
+    if (cfg->max_workgroups < 0) return fail(RSX_ERR_ARG, "max_workgroups must be >= 0");
+    if (!u) return fail(RSX_ERR_ARG, "the update's configuration (rsx_ppo_update_cfg) must not be null");
+    if (u->epochs < 1) return fail(RSX_ERR_ARG, "epochs must be >= 1");
+    if (int rc = update_split(in->n_batch_rows, u->minibatches)) return rc;
+    if (u->normalize_advantage && in->n_batch_rows < 2) return fail(RSX_ERR_ARG, "normalize_advantage needs at least 2 rows");
+    if (!(std::isfinite(u->norm_eps) && u->norm_eps >= 0.0f)) return fail(RSX_ERR_ARG, "norm_eps must be finite and >= 0");
+    if (int rc = adam_prologue(adam, st)) return rc;
+    if (st->n_actor != na || st->n_log_std != h->M.act_dim || st->n_critic != nc)
+        return fail(RSX_ERR_ARG, "the optimiser state's sizes (n_actor, n_log_std, n_critic) are not those of the two networks and act_dim");
+    if (!stats_dev || !workspace) return fail(RSX_ERR_ARG, "stats_dev and workspace must not be null");
+    launch_ppo_update(SA, na, actor_params_dev, log_std_dev, SC, nc, critic_params_dev, h->P.obs_dim, h->M.act_dim, *in, *cfg, *u, *adam, *st,
+                      stats_dev, workspace, (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
 // ---- planning with candidates drawn on the device (rsx.h: rsx_plan_sampler) ----
 // what the three calls check alike; on success S is the sampler as the kernels take it and P the handle's parameters with the step
 // counter the next step would take (not advanced).  n_steps: what the counter limit is checked against (0: the call simulates nothing)

@@ -11,6 +11,10 @@ struct rsx_adv_out;
 struct rsx_ppo_in;
 struct rsx_ppo_cfg;
 struct rsx_ppo_out;
+struct rsx_ppo_update_cfg;
+struct rsx_adam_cfg;
+struct rsx_adam_state;
+struct rsx_adam_io;
 
 namespace rsx {
 
@@ -110,6 +114,22 @@ long long ppo_workspace_bytes(long long n_params_actor, long long n_params_criti
 void launch_ppo_gradient(const PolicySpec& actor, long long n_params_actor, const float* actor_params, const float* log_std,
                          const PolicySpec& critic, long long n_params_critic, const float* critic_params, int obs_dim, int act_dim,
                          const rsx_ppo_in& in, const rsx_ppo_cfg& cfg, const rsx_ppo_out& out, hipStream_t s);
+// rsx_ppo_update.hip: the update phase around launch_ppo_gradient (rsx_ppo_normalize, rsx_ppo_permutation, rsx_adam_step, rsx_adam_mark,
+// rsx_task_ppo_update); every argument checked by the caller.  Two launches each for the normalisation and the Adam step, one for the
+// permutation and the mark.  ppo_update_workspace_bytes: launch_ppo_update's workspace (rows_offset: where the int32 rows lie in it);
+// launch_ppo_update enqueues the whole phase and calls launch_ppo_gradient per minibatch
+void launch_ppo_normalize(const float* adv, long long n, float eps, float* out, float* mean_std, void* workspace, hipStream_t s);
+void launch_ppo_permutation(int32_t* rows, long long n, uint64_t seed, uint32_t update, const long long* update_dev, uint32_t epoch,
+                            hipStream_t s);
+void launch_adam_step(const rsx_adam_cfg& c, const rsx_adam_state& st, const rsx_adam_io& io, hipStream_t s);
+void launch_update_mark(int64_t* counters, int op, hipStream_t s);
+long long ppo_update_chunk(long long n_batch_rows, int minibatches);
+long long ppo_update_workspace_bytes(long long n_params_actor, long long n_params_critic, int act_dim, long long n_batch_rows,
+                                     int minibatches, int max_workgroups, long long* rows_offset);
+void launch_ppo_update(const PolicySpec& actor, long long n_params_actor, float* actor_params, float* log_std, const PolicySpec& critic,
+                       long long n_params_critic, float* critic_params, int obs_dim, int act_dim, const rsx_ppo_in& in,
+                       const rsx_ppo_cfg& cfg, const rsx_ppo_update_cfg& u, const rsx_adam_cfg& adam, const rsx_adam_state& st, float* stats,
+                       void* workspace, hipStream_t s);
 // rsx_render.hip: batched rgb frames (rsx_render_*).  render_check_view: nullptr when the view is valid (and the frame size), else the
 // message; render_field_host: the static field image [H][W][3]; RenderGeom: what the kernel needs of a view, in float32
 struct RenderGeom { int W, H; float s, cx, cy, r, rb; int square; };

@@ -440,27 +440,9 @@ class VecFusedEnv(RenderMixin):
             out["next_value"] = nxt
         return out
 
-    def ppo_gradient(self, batch, policy, params, log_std, critic, critic_params, rows=None, advantage=None, clip=0.2, vf_coef=0.5,
-                     ent_coef=0.0, max_workgroups=None, return_forward=False):
-        """Gradients of the PPO loss with respect to an MLP actor, its ``log_std`` and an MLP critic on a minibatch of a collected
-        batch, in three launches (``rsx_task_ppo_gradient``): what a PPO loop does per minibatch before ``opt.step()``.
-
-        ``batch``: ``collect(..., critic=...)``'s dict; ``obs`` ``[T, B, obs_dim]``, ``sample`` ``[T, B, act_dim]``, ``log_prob``,
-        ``advantage`` and ``return`` ``[T, B]`` are used, all float32 CUDA tensors on the env's device, contiguous (anything else is a
-        ``ValueError`` naming the offender).  ``advantage=`` overrides the batch's with a ``[T, B]`` tensor (a normalised one, say).
-        ``policy`` / ``params`` ``[P]`` / ``log_std`` ``[act_dim]`` and ``critic`` / ``critic_params`` ``[Pc]``: as for ``collect``, float32
-        device tensors.  ``rows``: the minibatch as a 1-D int32 / int64 tensor of flat indices into the ``T * B`` rows, repeats allowed
-        (int64 is converted by one torch op); ``None``: the whole batch.  Host-side ``rows`` (list, numpy, CPU tensor) are range-checked;
-        a device tensor is not — an index outside ``[0, T * B)`` contributes nothing and is counted in ``stats["rows_skipped"]``.
-
-        The loss is ``L_pi + vf_coef * L_v - ent_coef * entropy`` with the clipped surrogate of ``clip`` and means over the minibatch,
-        written out in ``include/rsx.h`` with its float32 arithmetic.  ``max_workgroups`` caps the grid of the row launches (``None``:
-        the build's default); the result bits depend on the inputs and that number only.
-
-        Returns fresh device tensors ``grad_params`` ``[P]``, ``grad_log_std`` ``[act_dim]``, ``grad_critic_params`` ``[Pc]`` and
-        ``stats``: a dict of 0-d views (``loss_pi``, ``loss_v``, ``entropy``, ``approx_kl``, ``clip_fraction``, ``ratio``, ``rows_used``,
-        ``rows_skipped``; no synchronisation); with ``return_forward=True`` also ``mean`` ``[M, act_dim]`` and ``value`` ``[M]``, bit for
-        bit ``batch["mean"]`` / ``batch["value"]`` at the rows.  Touches nothing of the env, never synchronises, capturable."""
+    def _ppo_args(self, batch, policy, params, log_std, critic, critic_params, advantage, clip, vf_coef, ent_coef, max_workgroups):
+        """what ppo_gradient() and ppo_update() check alike of the two networks, the loss's scalars, the batch and the parameter
+        tensors; returns the (detached) tensors, (T, B, N) and the scalars as the C structs take them"""
         torch = self._torch
         from rsoccer_amd.vec.policy import MLPCritic, MLPPolicy
         if not isinstance(policy, MLPPolicy) or isinstance(policy, MLPCritic):
@@ -512,6 +494,33 @@ class VecFusedEnv(RenderMixin):
         p = need("params", params, (policy.num_params,))
         ls = need("log_std", log_std, (AD,))
         cp = need("critic_params", critic_params, (critic.num_params,))
+        return (obs, smp, olp, ret, adv, p, ls, cp), (T, B, N), (clip, vf_coef, ent_coef, mw)
+
+    def ppo_gradient(self, batch, policy, params, log_std, critic, critic_params, rows=None, advantage=None, clip=0.2, vf_coef=0.5,
+                     ent_coef=0.0, max_workgroups=None, return_forward=False):
+        """Gradients of the PPO loss with respect to an MLP actor, its ``log_std`` and an MLP critic on a minibatch of a collected
+        batch, in three launches (``rsx_task_ppo_gradient``): what a PPO loop does per minibatch before ``opt.step()``.
+
+        ``batch``: ``collect(..., critic=...)``'s dict; ``obs`` ``[T, B, obs_dim]``, ``sample`` ``[T, B, act_dim]``, ``log_prob``,
+        ``advantage`` and ``return`` ``[T, B]`` are used, all float32 CUDA tensors on the env's device, contiguous (anything else is a
+        ``ValueError`` naming the offender).  ``advantage=`` overrides the batch's with a ``[T, B]`` tensor (a normalised one, say).
+        ``policy`` / ``params`` ``[P]`` / ``log_std`` ``[act_dim]`` and ``critic`` / ``critic_params`` ``[Pc]``: as for ``collect``, float32
+        device tensors.  ``rows``: the minibatch as a 1-D int32 / int64 tensor of flat indices into the ``T * B`` rows, repeats allowed
+        (int64 is converted by one torch op); ``None``: the whole batch.  Host-side ``rows`` (list, numpy, CPU tensor) are range-checked;
+        a device tensor is not — an index outside ``[0, T * B)`` contributes nothing and is counted in ``stats["rows_skipped"]``.
+
+        The loss is ``L_pi + vf_coef * L_v - ent_coef * entropy`` with the clipped surrogate of ``clip`` and means over the minibatch,
+        written out in ``include/rsx.h`` with its float32 arithmetic.  ``max_workgroups`` caps the grid of the row launches (``None``:
+        the build's default); the result bits depend on the inputs and that number only.
+
+        Returns fresh device tensors ``grad_params`` ``[P]``, ``grad_log_std`` ``[act_dim]``, ``grad_critic_params`` ``[Pc]`` and
+        ``stats``: a dict of 0-d views (``loss_pi``, ``loss_v``, ``entropy``, ``approx_kl``, ``clip_fraction``, ``ratio``, ``rows_used``,
+        ``rows_skipped``; no synchronisation); with ``return_forward=True`` also ``mean`` ``[M, act_dim]`` and ``value`` ``[M]``, bit for
+        bit ``batch["mean"]`` / ``batch["value"]`` at the rows.  Touches nothing of the env, never synchronises, capturable."""
+        torch = self._torch
+        dev, AD = self.device, self.sim.act_dim
+        (obs, smp, olp, ret, adv, p, ls, cp), (T, B, N), (clip, vf_coef, ent_coef, mw) = self._ppo_args(
+            batch, policy, params, log_std, critic, critic_params, advantage, clip, vf_coef, ent_coef, max_workgroups)
         if rows is None:
             r, M = None, N
         else:
@@ -550,6 +559,130 @@ class VecFusedEnv(RenderMixin):
         if return_forward:
             res["mean"], res["value"] = mean, val
         return res
+
+    # ---- the update phase around ppo_gradient (include/rsx.h: rsx_ppo_normalize, rsx_ppo_permutation, rsx_task_ppo_update) ----
+    def normalize_advantages(self, adv, eps=1e-8, return_moments=False):
+        """``(adv - adv.mean()) / (adv.std() + eps)`` over all entries of a float32 device tensor (any shape, at least two entries,
+        contiguous), in two launches with a fixed reduction order (``rsx_ppo_normalize``; ``std`` carries Bessel's correction like
+        ``torch.Tensor.std``; the sums are taken in float64, mean and std rounded to float32 once).  Returns a fresh tensor of
+        ``adv``'s shape, with ``return_moments=True`` also a ``[2]`` tensor ``(mean, std)``.  Never synchronises, capturable."""
+        torch = self._torch
+        eps = float(eps)
+        if not (np.isfinite(eps) and eps >= 0.0):
+            raise ValueError(f"eps must be finite and >= 0, got {eps}")
+        if not isinstance(adv, torch.Tensor):
+            raise ValueError(f"adv must be a torch tensor, got {type(adv).__name__}")
+        if adv.dtype != torch.float32:
+            raise ValueError(f"adv must be torch.float32, got {adv.dtype}")
+        if adv.numel() < 2:
+            raise ValueError(f"adv must have at least 2 entries (one has no standard deviation), got {adv.numel()}")
+        if adv.device != self.device:
+            raise ValueError(f"adv is on {adv.device}, the env on {self.device}")
+        if not adv.is_contiguous():
+            raise ValueError("adv must be contiguous")
+        adv = adv.detach()
+        out = torch.empty_like(adv)
+        ms = torch.empty((2,), dtype=torch.float32, device=self.device)
+        ws = torch.empty((_lib.PPO_NORMALIZE_WORKSPACE_BYTES // 8,), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.ppo_normalize(adv.data_ptr(), adv.numel(), eps, out.data_ptr(), ms.data_ptr(), ws.data_ptr(), self._stream())
+        self._keep_norm = ws   # alive until the launches have consumed it
+        return (out, ms) if return_moments else out
+
+    @staticmethod
+    def minibatch_chunks(n, minibatches):
+        """the ``(lo, hi)`` bounds of the ``minibatches`` chunks of ``n`` rows: ``c = ceil(n / minibatches)`` rows each, the last one
+        what is left — ``torch.chunk``'s sizes.  A ``minibatches`` for which the last chunk would be empty is a ``ValueError``."""
+        n, mb = int(n), int(minibatches)
+        if n < 1:
+            raise ValueError(f"n must be >= 1, got {n}")
+        if mb < 1:
+            raise ValueError(f"minibatches must be >= 1, got {minibatches}")
+        c = -(-n // mb)
+        if (mb - 1) * c >= n:
+            raise ValueError(f"minibatches = {mb} leaves the last chunk of ceil({n} / {mb}) = {c} rows empty")
+        return [(k * c, min((k + 1) * c, n)) for k in range(mb)]
+
+    def minibatch_rows(self, n, seed, update, epoch, minibatches=None):
+        """A fresh permutation of ``0 .. n - 1`` as an int32 device tensor, every entry computed independently from ``(seed, update,
+        epoch, i)`` — no sort, no generator state (``rsx_ppo_permutation``: a keyed Feistel network with cycle walking, integer
+        arithmetic written out in ``include/rsx.h``).  ``update``: an integer, or a ``PPOOptimizer`` — then the key is the update count
+        in its device counters, read when the launch runs, so a replayed graph draws a new permutation on every replay.  With
+        ``minibatches`` the list of that many chunk views (``minibatch_chunks``) is returned instead.  Never synchronises."""
+        torch = self._torch
+        from rsoccer_amd.vec.optim import PPOOptimizer
+        n, epoch = int(n), int(epoch)
+        if not 1 <= n <= 2 ** 31 - 1:
+            raise ValueError(f"n must be in 1 .. 2^31 - 1, got {n}")
+        if not 0 <= epoch < 2 ** 32:
+            raise ValueError(f"epoch must be in 0 .. 2^32 - 1, got {epoch}")
+        chunks = None if minibatches is None else self.minibatch_chunks(n, minibatches)
+        upd_ptr, upd = None, 0
+        if isinstance(update, PPOOptimizer):
+            if update.device != self.device:
+                raise ValueError(f"the optimiser is on {update.device}, the env on {self.device}")
+            upd_ptr = update.counters.data_ptr() + 8 * _lib.ADAM_COUNTERS.index("updates")
+        else:
+            upd = int(update)
+            if upd < 0:
+                raise ValueError(f"update must be >= 0, got {update}")
+        rows = torch.empty((n,), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.ppo_permutation(rows.data_ptr(), n, int(seed), upd, upd_ptr, epoch, self._stream())
+        return rows if chunks is None else [rows[lo:hi] for lo, hi in chunks]
+
+    def ppo_update(self, batch, policy, params, log_std, critic, critic_params, opt, epochs=4, minibatches=4, clip=0.2, vf_coef=0.5,
+                   ent_coef=0.0, normalize_advantage=True, target_kl=None, seed=0, max_workgroups=None):
+        """The whole update phase of PPO enqueued by ONE call (``rsx_task_ppo_update``): ``normalize_advantages`` once per batch, per
+        epoch one ``minibatch_rows(T * B, seed, opt, epoch)``, and per minibatch ``ppo_gradient(rows=chunk, advantage=normalised)``
+        followed by ``opt.step`` — bit for bit that sequence of calls, without the interpreter between them.
+
+        ``batch``, ``policy`` / ``params`` / ``log_std``, ``critic`` / ``critic_params``, ``clip``, ``vf_coef``, ``ent_coef``,
+        ``max_workgroups``: as for ``ppo_gradient``.  ``params``, ``log_std`` and ``critic_params`` are UPDATED IN PLACE; ``batch`` is
+        not written.  ``opt``: a ``rsoccer_amd.vec.optim.PPOOptimizer`` of these two networks on the env's device; its update count
+        (on the device) keys the permutations and advances by one.  ``minibatches``: chunks of ``ceil(T * B / minibatches)`` rows,
+        ``torch.chunk``'s sizes; a count for which the last chunk would be empty is refused.
+
+        ``target_kl``: ``None`` or > 0.  The stopped flag is cleared when the call starts; a minibatch whose ``approx_kl`` exceeds
+        ``target_kl`` sets it before its own step, and from then on no step of this call changes a parameter, a moment or ``t``.
+        The remaining launches STILL RUN and their work is wasted: that is the price of not asking the host, which is what keeps the
+        call free of synchronisation and capturable.
+
+        Returns ``{"stats": [epochs, minibatches, 10], "rows": [T * B] int32}``: per minibatch ``ppo_gradient``'s eight values, the
+        gradient norm before the clip and whether the step was applied (``_lib.PPO_UPDATE_STATS``); ``rows`` is a view of the call's
+        workspace holding the last epoch's permutation.  Touches nothing of the env, never synchronises, capturable into a
+        ``torch.cuda.CUDAGraph``: with ``collect()`` on a device-keyed env in the same graph, one replay is one PPO iteration."""
+        torch = self._torch
+        from rsoccer_amd.vec.optim import PPOOptimizer, check_target_kl
+        if not isinstance(opt, PPOOptimizer):
+            raise ValueError("opt must be an rsoccer_amd.vec.optim.PPOOptimizer")
+        epochs = int(epochs)
+        if epochs < 1:
+            raise ValueError(f"epochs must be >= 1, got {epochs}")
+        if int(minibatches) < 1:
+            raise ValueError(f"minibatches must be >= 1, got {minibatches}")
+        kl = check_target_kl(target_kl)
+        (obs, smp, olp, ret, adv, p, ls, cp), (T, B, N), (clip, vf_coef, ent_coef, mw) = self._ppo_args(
+            batch, policy, params, log_std, critic, critic_params, None, clip, vf_coef, ent_coef, max_workgroups)
+        mb = len(self.minibatch_chunks(N, minibatches))
+        if normalize_advantage and N < 2:
+            raise ValueError("normalize_advantage needs at least 2 rows")
+        if opt.device != self.device:
+            raise ValueError(f"the optimiser is on {opt.device}, the env on {self.device}")
+        if opt.sizes != (policy.num_params, self.sim.act_dim, critic.num_params):
+            raise ValueError(f"the optimiser's state tensors have sizes {opt.sizes}, the networks "
+                             f"{(policy.num_params, self.sim.act_dim, critic.num_params)}")
+        aspec, cspec = policy.spec(), critic.spec()
+        nbytes, rows_off = self.sim.ppo_update_workspace(aspec, cspec, N, mb, mw)
+        ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=self.device)
+        stats = torch.empty((epochs, mb, len(_lib.PPO_UPDATE_STATS)), dtype=torch.float32, device=self.device)
+        ptr = lambda t: t.data_ptr()   # noqa: E731
+        inp = _lib.PpoIn(ptr(obs), ptr(smp), ptr(olp), ptr(adv), ptr(ret), None, N, N)
+        ucfg = _lib.PpoUpdateCfg(int(seed) & ((1 << 64) - 1), epochs, mb, 1 if normalize_advantage else 0, 1e-8)
+        self.sim.task_ppo_update(aspec, ptr(p), ptr(ls), cspec, ptr(cp), inp, _lib.PpoCfg(clip, vf_coef, ent_coef, mw), ucfg,
+                                 opt.cfg(None, kl if kl > 0.0 else None), opt.state(), ptr(stats), ptr(ws), self._stream())
+        self._keep_update = ws   # the call's own tensor: alive until the launches have consumed it
+        return {"stats": stats, "rows": ws[rows_off // 4: rows_off // 4 + N].view(torch.int32)}
 
     # ---- planning with candidates drawn on the device (include/rsx.h: rsx_plan_sampler) ----
     def _plan_sampler(self, sigma, hold, seed, iteration):

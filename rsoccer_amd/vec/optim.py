@@ -1,0 +1,183 @@
+"""The optimiser of the on-device PPO update (include/rsx.h: rsx_adam_step): ``torch.nn.utils.clip_grad_norm_`` followed by
+``torch.optim.Adam`` on the three flat tensors ``VecFusedEnv.ppo_gradient`` differentiates — the actor's parameters, ``log_std`` and the
+critic's parameters — with its whole state on the device, the step count included, so that a step is stream-ordered and capturable."""
+import math
+
+import numpy as np
+
+from rsoccer_amd import _lib
+
+
+def _finite(name, v, lo=None, lo_open=False):
+    v = float(v)
+    if not math.isfinite(v) or (lo is not None and (v <= lo if lo_open else v < lo)):
+        raise ValueError(f"{name} must be finite" + ("" if lo is None else f" and {'>' if lo_open else '>='} {lo}") + f", got {v}")
+    return v
+
+
+def check_target_kl(target_kl):
+    """``None`` (no KL stop) or a finite value > 0; returns the float the C structs take (0.0 = none)"""
+    if target_kl is None:
+        return 0.0
+    return _finite("target_kl", target_kl, 0.0, lo_open=True)
+
+
+class PPOOptimizer:
+    """Global-norm clip + Adam (no amsgrad, no weight decay) for an ``MLPPolicy`` actor, its ``log_std`` ``[act_dim]`` and an
+    ``MLPCritic``, in two launches per step.
+
+    State, all on ``device``: ``m`` and ``v`` for the three flat tensors and ``counters``, int64 ``[4]`` — Adam's step count ``t``,
+    the updates finished, the steps applied since the current update began, and the stopped flag of the KL stop
+    (``_lib.ADAM_COUNTERS``).  The bias corrections ``1 - beta ** t`` are computed on the device from the device's ``t`` in float64,
+    the betas being passed as doubles, as torch keeps them in Python floats.
+
+    ``lr``: a float, or a float32 CUDA tensor ``[1]`` that is read on the device at every step (a schedule under graph replay: write
+    the tensor, replay the graph).  ``max_grad_norm``: ``None`` or ``<= 0`` for no clipping.  Invalid values are a ``ValueError``
+    naming the offender."""
+
+    def __init__(self, policy, critic, device=0, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.5):
+        import torch
+        from rsoccer_amd.vec.policy import MLPCritic, MLPPolicy
+        if not isinstance(policy, MLPPolicy) or isinstance(policy, MLPCritic):
+            raise ValueError("policy must be an rsoccer_amd.vec.policy.MLPPolicy")
+        if not isinstance(critic, MLPCritic):
+            raise ValueError("critic must be an rsoccer_amd.vec.policy.MLPCritic")
+        self._torch = torch
+        self.device = device if isinstance(device, torch.device) else torch.device("cuda", int(device))
+        self.sizes = (policy.num_params, policy.act_dim, critic.num_params)
+        self.lr = self._check_lr(lr)
+        if len(tuple(betas)) != 2:
+            raise ValueError(f"betas must be a pair, got {betas!r}")
+        self.betas = tuple(float(b) for b in betas)
+        for k, b in enumerate(self.betas):
+            if not (0.0 <= b < 1.0):   # (a NaN fails both comparisons)
+                raise ValueError(f"betas[{k}] must be in [0, 1), got {b}")
+        self.eps = _finite("eps", eps, 0.0)
+        self.max_grad_norm = 0.0 if max_grad_norm is None else _finite("max_grad_norm", max_grad_norm)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self.m = [torch.zeros((n,), **f32) for n in self.sizes]
+        self.v = [torch.zeros((n,), **f32) for n in self.sizes]
+        self.counters = torch.zeros((4,), dtype=torch.int64, device=self.device)
+        self._ws = torch.zeros((_lib.ADAM_WORKSPACE_BYTES // 8,), dtype=torch.float64, device=self.device)
+
+    def _check_lr(self, lr):
+        torch = self._torch
+        if isinstance(lr, torch.Tensor):
+            if lr.dtype != torch.float32 or lr.numel() != 1 or lr.device != self.device:
+                raise ValueError(f"lr as a tensor must be one float32 on {self.device}, got {lr.dtype} {list(lr.shape)} on {lr.device}")
+            return lr
+        return _finite("lr", lr, 0.0)
+
+    def _stream(self):
+        try:
+            return self._torch._C._cuda_getCurrentRawStream(self.device.index)
+        except AttributeError:
+            return self._torch.cuda.current_stream(self.device).cuda_stream
+
+    # ---- the C structs ----
+    def cfg(self, lr=None, target_kl=None):
+        """the ``rsx_adam_cfg`` of this optimiser (``lr``: an override for this call)"""
+        lr = self.lr if lr is None else self._check_lr(lr)
+        by_ptr = isinstance(lr, self._torch.Tensor)
+        return _lib.AdamCfg(self.betas[0], self.betas[1], lr.data_ptr() if by_ptr else None, 0.0 if by_ptr else lr, self.eps,
+                            self.max_grad_norm, check_target_kl(target_kl))
+
+    def state(self):
+        """the ``rsx_adam_state`` of this optimiser"""
+        (ma, ml, mc), (va, vl, vc) = self.m, self.v
+        return _lib.AdamState(ma.data_ptr(), va.data_ptr(), ml.data_ptr(), vl.data_ptr(), mc.data_ptr(), vc.data_ptr(),
+                              self.counters.data_ptr(), *self.sizes)
+
+    def _need(self, name, t, n):
+        torch = self._torch
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
+        if tuple(t.shape) != (n,):
+            raise ValueError(f"{name} must be [{n}], got {list(t.shape)}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be torch.float32, got {t.dtype}")
+        if t.device != self.device:
+            raise ValueError(f"{name} is on {t.device}, the optimiser on {self.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        return t.detach()
+
+    # ---- steps ----
+    def step(self, params, log_std, critic_params, grad_params, grad_log_std, grad_critic_params, approx_kl=None, target_kl=None,
+             lr=None):
+        """Clip the three gradients by their global norm and take one Adam step on ``params`` ``[P]``, ``log_std`` ``[act_dim]`` and
+        ``critic_params`` ``[Pc]`` IN PLACE (``rsx_adam_step``; the arithmetic is written out in ``include/rsx.h``).  The gradients
+        are ``ppo_gradient()``'s outputs and are not changed.
+
+        With ``target_kl`` and ``approx_kl`` (a 0-d or ``[1]`` float32 device tensor: ``ppo_gradient``'s ``stats["approx_kl"]``) a
+        step whose ``approx_kl`` exceeds ``target_kl`` sets the stopped flag before its own step, and a step that finds the flag set
+        changes nothing — no parameter, no moment, not ``t``; its launches still run.  ``begin_update()`` clears the flag.
+
+        Returns 0-d device views ``grad_norm`` (before the clip) and ``applied`` (1.0 or 0.0).  Never synchronises, capturable."""
+        torch = self._torch
+        names = ("params", "log_std", "critic_params")
+        ps = [self._need(k, t, n) for k, t, n in zip(names, (params, log_std, critic_params), self.sizes)]
+        gs = [self._need("grad_" + k, t, n) for k, t, n in zip(names, (grad_params, grad_log_std, grad_critic_params), self.sizes)]
+        cfg = self.cfg(lr, target_kl)
+        kl = None
+        if approx_kl is not None:
+            if not isinstance(approx_kl, torch.Tensor) or approx_kl.numel() != 1 or approx_kl.dtype != torch.float32 or approx_kl.device != self.device:
+                raise ValueError(f"approx_kl must be one float32 on {self.device}")
+            kl = approx_kl
+        stats = torch.empty((2,), dtype=torch.float32, device=self.device)
+        io = _lib.AdamIo(ps[0].data_ptr(), ps[1].data_ptr(), ps[2].data_ptr(), gs[0].data_ptr(), gs[1].data_ptr(), gs[2].data_ptr(),
+                         None if kl is None else kl.data_ptr(), stats.data_ptr(), self._ws.data_ptr())
+        with torch.cuda.device(self.device):
+            _lib.adam_step(cfg, self.state(), io, self._stream())
+        return {"grad_norm": stats[0], "applied": stats[1]}
+
+    def begin_update(self):
+        """an update begins: the steps-applied count and the stopped flag are cleared (what ``ppo_update()`` does first)"""
+        with self._torch.cuda.device(self.device):
+            _lib.adam_mark(self.state(), False, self._stream())
+
+    def end_update(self):
+        """an update ends: the update count, which keys ``minibatch_rows``, advances (what ``ppo_update()`` does last)"""
+        with self._torch.cuda.device(self.device):
+            _lib.adam_mark(self.state(), True, self._stream())
+
+    # ---- checkpoints ----
+    def state_dict(self):
+        """clones of ``m``, ``v`` (three tensors each) and ``counters``, and the hyper-parameters: a training checkpoint round-trips"""
+        lr = self.lr
+        return {"m": [t.clone() for t in self.m], "v": [t.clone() for t in self.v], "counters": self.counters.clone(),
+                "lr": lr.clone() if isinstance(lr, self._torch.Tensor) else lr, "betas": self.betas, "eps": self.eps,
+                "max_grad_norm": self.max_grad_norm}
+
+    def load_state_dict(self, sd):
+        """copies a ``state_dict()`` into this optimiser's own tensors (their addresses stay: a captured graph keeps working);
+        tensors of another size are a ``ValueError``"""
+        torch = self._torch
+        for key in ("m", "v", "counters"):
+            if key not in sd:
+                raise ValueError(f"state dict lacks {key!r}")
+        for key, mine in (("m", self.m), ("v", self.v)):
+            theirs = list(sd[key])
+            if len(theirs) != 3:
+                raise ValueError(f"state dict's {key!r} must hold three tensors, got {len(theirs)}")
+            for k, (a, b) in enumerate(zip(mine, theirs)):
+                if tuple(np.shape(b)) != tuple(a.shape):
+                    raise ValueError(f"state dict's {key}[{k}] must be {list(a.shape)}, got {list(np.shape(b))}")
+        if tuple(np.shape(sd["counters"])) != (4,):
+            raise ValueError(f"state dict's counters must be [4], got {list(np.shape(sd['counters']))}")
+        for key, mine in (("m", self.m), ("v", self.v)):
+            for a, b in zip(mine, sd[key]):
+                a.copy_(torch.as_tensor(b).to(device=self.device, dtype=torch.float32))
+        self.counters.copy_(torch.as_tensor(sd["counters"]).to(device=self.device, dtype=torch.int64))
+        if "lr" in sd:
+            lr = sd["lr"]
+            if isinstance(lr, torch.Tensor) and isinstance(self.lr, torch.Tensor):
+                self.lr.copy_(lr.to(self.device))
+            else:
+                self.lr = self._check_lr(lr.to(self.device) if isinstance(lr, torch.Tensor) else lr)
+        if "betas" in sd:
+            self.betas = tuple(float(b) for b in sd["betas"])
+        if "eps" in sd:
+            self.eps = _finite("eps", sd["eps"], 0.0)
+        if "max_grad_norm" in sd:
+            self.max_grad_norm = _finite("max_grad_norm", sd["max_grad_norm"])
