@@ -521,6 +521,48 @@ int rsx_task_collect_policy(rsx_sim* h, const rsx_policy_mlp* p, const float* pa
                             const float* sigma_dev /* [act_dim] >= 0, or NULL = deterministic */, uint64_t noise_seed,
                             int n_steps, const rsx_collect_out* out, void* stream);
 
+/* ---- self-play collection for VSS-v0: a policy-driven opponent inside the launch (additive extension of ABI 6) ---------------------
+ * rsx_task_collect_policy with ONE command replaced: yellow robot 0 (body index n_blue) is driven by a second MLP policy, the opponent
+ * — typically a frozen earlier copy of the learner — instead of its Ornstein-Uhlenbeck noise.  The opponent is evaluated inside the same
+ * launch from the mirrored observation.  Everything else is rsx_task_collect_policy's: the agent's batch, same-step auto-reset, the
+ * Gaussian head, the step counter, capture, and every handle shape that call serves.
+ *   scope            VSS-v0 with equal teams only (3v3, 5v5): every other task is refused.
+ *   actor ...        the agent (blue 0): rsx_task_collect_policy's p, params_dev and sigma_dev.
+ *   opponent ...     an rsx_policy_mlp of its own (layers and hidden may differ from the actor's), opponent_params_dev [P2] in the same
+ *                    layout for the same obs_dim and act_dim, opponent_sigma_dev [2] or NULL = deterministic; unchecked like the actor's.
+ *   mirrored obs     what VSS-v0's observation would be with the team colours swapped and the field turned by 180 degrees, in the same
+ *                    layout and obs_dim as the agent's row.  With n = n_blue = n_yellow: ball [0:4]; "own" robot i at 4 + 7 i as
+ *                    (x, y, sin, cos, vx, vy, w) holds YELLOW i; "other" robot j at 4 + 7 n + 5 j as (x, y, vx, vy, w) holds BLUE j
+ *                    (3v3: 25 + 5 j).  Positions and linear velocities are the float32 negations of the values the agent's normaliser
+ *                    produces for the same body (clamp(-v) == -clamp(v) exactly); the angular velocity is unchanged; sin and cos are the
+ *                    negations of the body's own sine and cosine (of the stored heading in degrees).  The row is written from the same
+ *                    registers, at the same point, as the agent's row: opponent row t and agent row t describe the same instant.  Row 0
+ *                    is computed from the state the call starts from.
+ *   opponent action  mean = the opponent's output accumulator in rsx_policy_mlp's arithmetic, unchanged; sample = mean + sigma * eps
+ *                    (or mean); action = out_act(sample).  eps follows the agent's recipe — the same key (noise_seed), global env id and
+ *                    step counter — under domain word 9 instead of 7: the two heads never share a draw.  The opponent's forward is
+ *                    computed BEFORE the agent's action is applied: both policies answer observation t.
+ *   the command      the two action components go through VSS-v0's action -> wheel-speed map (vss_gym.py:235-254) and replace the
+ *                    command of yellow 0 for that step, and only that.  Yellow 0's Ornstein-Uhlenbeck state keeps advancing on its usual
+ *                    draws, unused: the handle can be handed back to rsx_task_step or rsx_task_collect_policy at any time, and the
+ *                    checkpoint format and every other robot's stream are untouched.
+ *   rewards          reward, flags, metrics, final_obs and the handle's obs buffer stay the agent's (blue's). */
+typedef struct rsx_selfplay_out {
+    float* opp_obs;      /* [T][B][obs_dim] or NULL: the mirrored observation each opponent action answered */
+    float* opp_actions;  /* [T][B][2] or NULL: the action that drove yellow 0 */
+    float* opp_mean;     /* [T][B][2] or NULL: the opponent's output layer before noise and before out_act */
+    float* opp_sample;   /* [T][B][2] or NULL: mean + sigma * eps, before out_act */
+} rsx_selfplay_out;
+/* Commit: the call advances the handle exactly as n_steps steps of the engine with out->actions[t] for blue 0 and the wheel speeds of
+ * opp_actions[t] for yellow 0 would — the step is the engine's step with one command replaced.  `sp` may be NULL (nothing of the
+ * opponent is recorded).  LDS: both policies' images share a workgroup (two 40-64-64-2 policies at 8 lanes per env: 79 040 B, two workgroups per CU
+ * against the collector's three; 5v5 at 16 lanes per env: 84 608 B, one).
+ * Refusals (nothing is enqueued): all of rsx_task_collect_policy's, applied to both policies (the LDS limit is the CU's 160 KB for both
+ * images together), and RSX_ERR_ARG for a task other than VSS-v0, unequal teams, a null opponent or opponent_params_dev. */
+int rsx_task_collect_selfplay(rsx_sim* h, const rsx_policy_mlp* actor, const float* actor_params_dev, const float* sigma_dev,
+                              const rsx_policy_mlp* opponent, const float* opponent_params_dev, const float* opponent_sigma_dev,
+                              uint64_t noise_seed, int n_steps, const rsx_collect_out* out, const rsx_selfplay_out* sp, void* stream);
+
 /* ---- values and GAE advantages of a collected batch (additive extension of ABI 6) ------------------------------------------------
  * What an on-policy trainer does between rsx_task_collect_policy and its gradient step: evaluate a critic on the [T][B] batch and run
  * the reverse recurrence of generalised advantage estimation — two launches instead of a torch critic plus a Python loop over T.

@@ -52,7 +52,7 @@ SYMBOLS = (
     "rsx_task_transfer", "rsx_task_transfer_errors",
     "rsx_task_lookahead_sampled", "rsx_plan_candidates", "rsx_plan_update",
     "rsx_policy_num_params", "rsx_task_lookahead_policy",
-    "rsx_task_collect_policy",
+    "rsx_task_collect_policy", "rsx_task_collect_selfplay",
     "rsx_critic_num_params", "rsx_task_advantages",
     "rsx_ppo_gradient_workspace", "rsx_task_ppo_gradient",
     "rsx_ppo_normalize", "rsx_ppo_permutation", "rsx_adam_step", "rsx_adam_mark", "rsx_ppo_update_workspace", "rsx_task_ppo_update",
@@ -80,6 +80,11 @@ class CollectOut(C.Structure):
     """rsx_collect_out (include/rsx.h): the [T][B] record of rsx_task_collect_policy; device addresses, the last three may be None"""
     _fields_ = [("obs", C.c_void_p), ("actions", C.c_void_p), ("rewards", C.c_void_p), ("flags", C.c_void_p),
                 ("final_obs", C.c_void_p), ("mean", C.c_void_p), ("sample", C.c_void_p)]
+
+
+class SelfplayOut(C.Structure):
+    """rsx_selfplay_out (include/rsx.h): the opponent's [T][B] record of rsx_task_collect_selfplay; device addresses, each may be None"""
+    _fields_ = [("opp_obs", C.c_void_p), ("opp_actions", C.c_void_p), ("opp_mean", C.c_void_p), ("opp_sample", C.c_void_p)]
 
 
 class AdvIn(C.Structure):
@@ -249,6 +254,8 @@ def load():
     lib.rsx_policy_num_params.argtypes = [vp, C.POINTER(PolicyMLP), C.POINTER(C.c_int64)]
     lib.rsx_task_lookahead_policy.argtypes = [vp, C.POINTER(PolicyMLP), vp, ip, ip, C.c_float, vp, vp, vp, vp, vp, vp, vp]
     lib.rsx_task_collect_policy.argtypes = [vp, C.POINTER(PolicyMLP), vp, vp, C.c_uint64, ip, C.POINTER(CollectOut), vp]
+    lib.rsx_task_collect_selfplay.argtypes = [vp, C.POINTER(PolicyMLP), vp, vp, C.POINTER(PolicyMLP), vp, vp, C.c_uint64, ip,
+                                              C.POINTER(CollectOut), C.POINTER(SelfplayOut), vp]
     lib.rsx_critic_num_params.argtypes = [vp, C.POINTER(PolicyMLP), C.POINTER(C.c_int64)]
     lib.rsx_task_advantages.argtypes = [vp, C.POINTER(PolicyMLP), vp, C.c_float, C.c_float, ip, ip, C.POINTER(AdvIn), C.POINTER(AdvOut), vp]
     lib.rsx_ppo_gradient_workspace.argtypes = [vp, C.POINTER(PolicyMLP), C.POINTER(PolicyMLP), C.c_int64, ip, C.POINTER(C.c_int64)]
@@ -645,6 +652,17 @@ class Sim:
         pass NULL.  ``sigma_ptr``: [act_dim] f32 device address of the Gaussian head's standard deviations, or None = deterministic."""
         rc = self._lib.rsx_task_collect_policy(self._h, None if spec is None else C.byref(spec), params_ptr, sigma_ptr,
                                                int(noise_seed) & 0xFFFFFFFFFFFFFFFF, int(n_steps), None if out is None else C.byref(out), stream)
+        if rc:
+            _chk(rc)
+
+    def task_collect_selfplay(self, spec, params_ptr, sigma_ptr, opp_spec, opp_params_ptr, opp_sigma_ptr, noise_seed, n_steps, out, sp,
+                              stream=None):
+        """rsx_task_collect_selfplay: ``task_collect_policy`` on a VSS-v0 handle with yellow robot 0 driven by a second MLP policy
+        (``opp_spec``, params [P2] f32, ``opp_sigma_ptr`` [2] or None) from the mirrored observation; ``sp``: a SelfplayOut of device
+        addresses (the opponent's records), or None to pass NULL."""
+        ref = lambda v: None if v is None else C.byref(v)   # noqa: E731
+        rc = self._lib.rsx_task_collect_selfplay(self._h, ref(spec), params_ptr, sigma_ptr, ref(opp_spec), opp_params_ptr, opp_sigma_ptr,
+                                                 int(noise_seed) & 0xFFFFFFFFFFFFFFFF, int(n_steps), ref(out), ref(sp), stream)
         if rc:
             _chk(rc)
 

@@ -392,6 +392,43 @@ int rsx_task_collect_policy(rsx_sim* h, const rsx_policy_mlp* p, const float* pa
     return debug_finite(h, s, "rsx_task_collect_policy");
 }
 
+// ---- the same with yellow robot 0 of VSS-v0 driven by a second policy from the mirrored observation (rsx.h: rsx_task_collect_selfplay) ----
+int rsx_task_collect_selfplay(rsx_sim* h, const rsx_policy_mlp* actor, const float* actor_params_dev, const float* sigma_dev,
+                              const rsx_policy_mlp* opponent, const float* opponent_params_dev, const float* opponent_sigma_dev,
+                              uint64_t noise_seed, int n_steps, const rsx_collect_out* out, const rsx_selfplay_out* sp, void* stream) {
+    RSX_ENTER(h);
+    PolicySpec S, S2; int64_t n_params = 0, n_opp_params = 0;
+    if (int rc = policy_prologue(h, actor, &S, &n_params)) return rc;
+    if (h->P.task != RSX_TASK_VSS_V0)
+        return fail(RSX_ERR_ARG, "rsx_task_collect_selfplay serves VSS-v0 only: the opponent drives yellow robot 0 of that task");
+    if (h->P.n_blue != h->P.n_yellow)
+        return fail(RSX_ERR_ARG, "rsx_task_collect_selfplay needs equal teams: the mirrored observation has the agent's layout");
+    if (!opponent) return fail(RSX_ERR_ARG, "the opponent (rsx_policy_mlp) must not be null");
+    if (int rc = policy_prologue(h, opponent, &S2, &n_opp_params)) return rc;
+    RSX_NEED_RESET(h);
+    if (n_steps < 1 || n_steps > RSX_N_STEPS_MASK) return fail(RSX_ERR_ARG, "n_steps must be in 1 .. 2^30 - 1");
+    if (!actor_params_dev || !opponent_params_dev) return fail(RSX_ERR_ARG, "actor_params_dev and opponent_params_dev must not be null");
+    if (!out || !out->obs || !out->actions || !out->rewards || !out->flags)
+        return fail(RSX_ERR_ARG, "out and its obs, actions, rewards and flags arrays must not be null");
+    if (h->L > 32) return fail(RSX_ERR_ARG, "rsx_task_collect_selfplay has no 64-lanes-per-env kernels (unset RSX_LANES_PER_ENV)");
+    if (selfplay_lds_bytes(h->L, h->P.obs_dim, h->M.act_dim, S, S2) > 163840ll)
+        return fail(RSX_ERR_ARG, "the two policies' weights do not fit a CU's 160 KB of LDS at this observation width: use fewer or smaller hidden layers");
+    hipStream_t s = (hipStream_t)stream;
+    int fl = 0;
+    if (int rc = step_prologue(h, s, (uint64_t)n_steps, &fl)) return rc;   // capture of a host-keyed handle, counter limit
+    h->host_state_valid = false;
+    const int grid = grid_for(h);   // (the tick slots: as rsx_task_collect_policy, the launch has its grid)
+    if (h->tick_dev) launch_tick_fill(tick_slot0(h), h->tick_slots, grid, 0u, 1, s);
+    h->P.tick_base = h->tick; h->tick += (uint32_t)n_steps;
+    const rsx_selfplay_out none{nullptr, nullptr, nullptr, nullptr};
+    launch_task_collect_selfplay(h->P, buffers_of(h, nullptr), h->L, h->NR, h->d_phys, S, actor_params_dev, (int)n_params, S2,
+                                 opponent_params_dev, (int)n_opp_params, h->M.act_dim, sigma_dev, opponent_sigma_dev, noise_seed, n_steps | fl,
+                                 *out, sp ? *sp : none, s);
+    if (h->tick_dev) launch_tick_fill(tick_slot0(h), grid, h->tick_slots, 0u, 1, s);
+    HIP_TRY(launch_status());
+    return debug_finite(h, s, "rsx_task_collect_selfplay");
+}
+
 // ---- values and GAE advantages of a [T][B] batch (rsx.h: rsx_task_advantages).  The handle gives the device and obs_dim; nothing of it is touched ----
 // what both calls check of a critic; on success S is the spec as the kernels take it and *n_params the floats of one critic
 static int critic_prologue(const rsx_sim* h, const rsx_policy_mlp* c, PolicySpec* S, int64_t* n_params) {

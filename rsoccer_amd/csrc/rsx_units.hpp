@@ -6,6 +6,8 @@
 #include <cstdint>
 
 struct rsx_render_view;   // include/rsx.h
+struct rsx_collect_out;
+struct rsx_selfplay_out;
 struct rsx_adv_in;
 struct rsx_adv_out;
 struct rsx_ppo_in;
@@ -94,6 +96,15 @@ void launch_task_lookahead_policy(const Params& P, int L, int NR, const float* s
 void launch_task_collect_policy(const Params& P, const Buffers& b, int L, int NR, float* phys, const PolicySpec& p, const float* params,
                                 int n_params, int act_dim, const float* sigma, uint64_t noise_seed, int n_steps, float* obs, float* actions,
                                 float* rewards, uint8_t* flags, float* final_obs, float* mean, float* sample, hipStream_t s);
+// rsx_selfplay.hip: the same collection for VSS-v0 with yellow robot 0 driven by a second policy, the opponent, from the mirrored observation
+// (rsx_task_collect_selfplay).  p / params / sigma: the agent's, as above; opp / opp_params / opp_sigma: the opponent's (a shape of its own);
+// out: the agent's record, checked; sp: the opponent's, every member optional.  selfplay_lds_bytes: LDS of one workgroup of that launch
+// (Shared<L> and both images: the host refuses more than a CU's 160 KB; beyond 64 KB the launch raises the kernel's limit itself)
+long long selfplay_lds_bytes(int L, int obs_dim, int act_dim, const PolicySpec& agent, const PolicySpec& opponent);
+void launch_task_collect_selfplay(const Params& P, const Buffers& b, int L, int NR, float* phys, const PolicySpec& p, const float* params,
+                                  int n_params, const PolicySpec& opp, const float* opp_params, int n_opp_params, int act_dim,
+                                  const float* sigma, const float* opp_sigma, uint64_t noise_seed, int n_steps, const rsx_collect_out& out,
+                                  const rsx_selfplay_out& sp, hipStream_t s);
 // rsx_gae.hip: values and GAE advantages of a [T][B] batch (rsx_task_advantages).  critic: rsx_policy_mlp with act_dim = 1 and a linear
 // output, checked; params: [P]; gl: (float)gamma * (float)lam; in / out: the call's arrays, checked.  Two launches: the critic over
 // T * B + B rows (and the rows truncated only of final_obs), then the reverse scan.  form: which values kernel (GAE_FORM_ROWS: one row per

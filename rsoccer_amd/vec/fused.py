@@ -258,7 +258,7 @@ class VecFusedEnv(RenderMixin):
         return out
 
     def collect(self, policy, params, steps, log_std=None, noise_seed=None, iteration=0, return_final_obs=False,
-                critic=None, critic_params=None, gamma=0.99, lam=0.95):
+                critic=None, critic_params=None, gamma=0.99, lam=0.95, opponent=None, opponent_params=None, opponent_log_std=None):
         """Advance the envs ``steps`` steps under an MLP policy in ONE launch and return the on-policy batch
         (``rsx_task_collect_policy``): what a PPO / A2C loop calls between two updates.
 
@@ -285,6 +285,17 @@ class VecFusedEnv(RenderMixin):
         With ``critic`` (an ``MLPCritic``) and ``critic_params`` the batch also carries ``value``, ``advantage`` and ``return``
         ``[T, B]``: ``advantages(batch, critic, critic_params, gamma, lam)`` on the batch just collected (``final_obs`` is then always
         recorded and returned).  Without a critic the returned dict and the launches are what they were.
+
+        Self-play (VSS-v0 only, ``rsx_task_collect_selfplay``): with ``opponent`` (an ``MLPPolicy`` of this env's dims; its layers and
+        hidden may differ from the agent's) and ``opponent_params`` ``[P2]``, yellow robot 0 is driven by that policy inside the same
+        launch instead of by its Ornstein-Uhlenbeck noise.  The opponent sees the mirrored observation — team colours swapped, the
+        field turned by 180 degrees, the agent's layout — and answers the same instant as the agent; ``opponent_log_std`` gives it a
+        Gaussian head of its own (the agent's noise key under another domain word: the heads never share a draw).  Rewards, flags,
+        ``final_obs``, ``next_obs`` and the metrics stay the agent's.  The dict gains ``opponent_obs`` ``[T, B, obs_dim]``,
+        ``opponent_actions`` ``[T, B, 2]`` and, with a head, ``opponent_mean``, ``opponent_sample`` and ``opponent_log_prob``.  The env
+        can be handed back to ``step()`` or a plain ``collect()`` at any time: yellow 0's noise state kept advancing, unused.  A typical
+        loop copies the learner's parameters into ``opponent_params`` every few updates (``examples/selfplay_vss.py``).  With
+        ``opponent=None`` the call, its launches and its outputs are exactly what they are without these keywords.
         Capturable into a ``torch.cuda.CUDAGraph`` after ``enable_graph_capture()``: every replay draws fresh noise."""
         torch = self._torch
         from rsoccer_amd.vec.policy import MLPPolicy
@@ -303,27 +314,52 @@ class VecFusedEnv(RenderMixin):
         shape = tuple(np.shape(params))   # checked on the INPUT, as lookahead_policy() checks its parameters
         if shape != (policy.num_params,):
             raise ValueError(f"params must be [{policy.num_params}] (one policy), got {shape}")
+        if opponent is None:
+            for name, v in (("opponent_params", opponent_params), ("opponent_log_std", opponent_log_std)):
+                if v is not None:
+                    raise ValueError(f"{name} given without an opponent")
+        else:   # (refused before anything is enqueued)
+            if not isinstance(opponent, MLPPolicy):
+                raise ValueError("opponent must be an rsoccer_amd.vec.policy.MLPPolicy")
+            if self.TASK != _lib.TASK_VSS_V0 or self.N_BLUE != self.N_YELLOW:
+                raise ValueError(f"opponent: self-play drives yellow robot 0 of VSS-v0 with equal teams, this env is {type(self).__name__}")
+            if self.sim.act_dim != opponent.act_dim or self.sim.obs_dim != opponent.obs_dim:
+                raise ValueError(f"the opponent maps {opponent.obs_dim} -> {opponent.act_dim}, the env {self.sim.obs_dim} -> {self.sim.act_dim}")
+            if opponent_params is None:
+                raise ValueError("opponent_params must not be None")
+            oshape = tuple(np.shape(opponent_params))
+            if oshape != (opponent.num_params,):
+                raise ValueError(f"opponent_params must be [{opponent.num_params}] (one policy), got {oshape}")
         dev, B, OD, AD = self.device, self.num_envs, self.sim.obs_dim, self.sim.act_dim
-        if isinstance(params, torch.Tensor):
-            p = params.detach()
-            if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
-                p = p.to(device=dev, dtype=torch.float32).contiguous()
-        else:
-            p = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float32)).to(dev)
-        ls = sigma = None
-        if log_std is not None:
-            if isinstance(log_std, torch.Tensor):
-                ls = log_std.detach().to(device=dev, dtype=torch.float32)
+
+        def device_params(v):
+            if isinstance(v, torch.Tensor):
+                t = v.detach()
+                if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+                    t = t.to(device=dev, dtype=torch.float32).contiguous()
+                return t
+            return torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dev)
+
+        def head(v, name):
+            """(log_std [AD] on the device, sigma = exp(log_std)) of a Gaussian head, or (None, None)"""
+            if v is None:
+                return None, None
+            if isinstance(v, torch.Tensor):
+                t = v.detach().to(device=dev, dtype=torch.float32)
             else:
-                host = np.asarray(log_std, dtype=np.float32)
+                host = np.asarray(v, dtype=np.float32)
                 if not np.all(np.isfinite(host)):
-                    raise ValueError("log_std must be finite")
-                ls = torch.from_numpy(np.array(host, dtype=np.float32, copy=True)).to(dev)   # (keeps a scalar 0-dimensional)
-            if ls.dim() == 0:
-                ls = ls.expand(AD)
-            if tuple(ls.shape) != (AD,):
-                raise ValueError(f"log_std must be a scalar or [{AD}], got {tuple(ls.shape)}")
-            sigma = ls.exp().contiguous()
+                    raise ValueError(f"{name} must be finite")
+                t = torch.from_numpy(np.array(host, dtype=np.float32, copy=True)).to(dev)   # (keeps a scalar 0-dimensional)
+            if t.dim() == 0:
+                t = t.expand(AD)
+            if tuple(t.shape) != (AD,):
+                raise ValueError(f"{name} must be a scalar or [{AD}], got {tuple(t.shape)}")
+            return t, t.exp().contiguous()
+
+        p = device_params(params)
+        ls, sigma = head(log_std, "log_std")
+        ols, osigma = head(opponent_log_std, "opponent_log_std")
         if noise_seed is None:
             m = (1 << 64) - 1   # splitmix64 of (seed, iteration), as _plan_sampler
             z = (self._seed + 0x9E3779B97F4A7C15 * (int(iteration) + 1)) & m
@@ -340,10 +376,27 @@ class VecFusedEnv(RenderMixin):
         smp = torch.empty((T, B, AD), **f32) if sigma is not None else None
         ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
         rec = _lib.CollectOut(ptr(obs), ptr(acts), ptr(rew), ptr(flags), ptr(fobs), ptr(mean), ptr(smp))
-        self.sim.task_collect_policy(policy.spec(), p.data_ptr(), ptr(sigma), noise_seed, T, rec, self._stream())
-        self._keep_plan = (p, sigma)   # alive until the launch has consumed them
+        if opponent is None:
+            self.sim.task_collect_policy(policy.spec(), p.data_ptr(), ptr(sigma), noise_seed, T, rec, self._stream())
+            self._keep_plan = (p, sigma)   # alive until the launch has consumed them
+        else:
+            op = device_params(opponent_params)
+            oobs = torch.empty((T, B, OD), **f32)
+            oacts = torch.empty((T, B, AD), **f32)
+            omean = torch.empty((T, B, AD), **f32) if osigma is not None else None
+            osmp = torch.empty((T, B, AD), **f32) if osigma is not None else None
+            sp = _lib.SelfplayOut(ptr(oobs), ptr(oacts), ptr(omean), ptr(osmp))
+            self.sim.task_collect_selfplay(policy.spec(), p.data_ptr(), ptr(sigma), opponent.spec(), op.data_ptr(), ptr(osigma), noise_seed,
+                                           T, rec, sp, self._stream())
+            self._keep_plan = (p, sigma, op, osigma)
         out = {"obs": obs, "actions": acts, "reward": rew, "terminated": (flags & 1).bool(), "truncated": (flags & 2).bool(),
                "next_obs": self._t["obs"]}
+        if opponent is not None:
+            out["opponent_obs"], out["opponent_actions"] = oobs, oacts
+            if osigma is not None:
+                out["opponent_mean"], out["opponent_sample"] = omean, osmp
+                z = (osmp - omean) / osigma
+                out["opponent_log_prob"] = (-0.5 * z * z - ols - 0.9189385332046727).sum(-1)
         if return_final_obs:
             out["final_obs"] = fobs
         if sigma is not None:
