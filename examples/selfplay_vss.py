@@ -1,13 +1,16 @@
 """Self-play PPO on VSS-v0: the learner (blue 0) against a frozen earlier copy of itself (yellow 0), both evaluated inside one launch.
 
-    python examples/selfplay_vss.py [--envs 1024] [--steps 128] [--updates 20] [--snapshot 5] [--graph]
+    python examples/selfplay_vss.py [--envs 1024] [--steps 128] [--updates 20] [--snapshot 5] [--graph] [--team]
 
 The --device-update loop of examples/ppo_vss.py with one change: env.collect(..., opponent=pol, opponent_params=p_opponent) drives
 yellow robot 0 by a second copy of the policy, which sees the mirrored observation (team colours swapped, the field turned by 180
 degrees) and acts deterministically.  Every --snapshot N updates the learner's parameters are copied into the opponent's: ONE copy_
 between two device tensors, stream-ordered like everything else in the loop.  p_opponent keeps its address, so with --graph the copy
 needs no re-capture: the captured collect + ppo_update reads whatever the tensor holds when it is replayed.  The other four robots keep
-their Ornstein-Uhlenbeck noise.  A demonstration of the call pattern, not a tuned trainer."""
+their Ornstein-Uhlenbeck noise.  With --team the whole team learns against a snapshot team: collect(..., team=True, opponent_team=True)
+seats all three robots of each side (every seat sees its side's row with "own" slots 0 and i exchanged and shares its side's
+parameters), and rsoccer_amd.vec.policy.seat_rows turns the [T, B, S, ...] batch into the [T, B * S, ...] rows ppo_update takes: three
+samples per env step, one shared reward.  A demonstration of the call pattern, not a tuned trainer."""
 import argparse
 import os
 import sys
@@ -18,7 +21,7 @@ import torch
 
 from rsoccer_amd.vec import VecVSSEnv
 from rsoccer_amd.vec.optim import PPOOptimizer
-from rsoccer_amd.vec.policy import MLPCritic, MLPPolicy
+from rsoccer_amd.vec.policy import MLPCritic, MLPPolicy, seat_rows
 
 
 def main():
@@ -37,6 +40,7 @@ def main():
     ap.add_argument("--graph", action="store_true", help="capture collect + ppo_update once, replay it per iteration")
     ap.add_argument("--max-grad-norm", type=float, default=0.5, help="the global-norm clip (<= 0: none)")
     ap.add_argument("--target-kl", type=float, default=None, help="stop an update's steps once approx_kl exceeds this")
+    ap.add_argument("--team", action="store_true", help="seat every robot of both sides: the team learns against a snapshot team")
     args = ap.parse_args()
     if args.snapshot < 1:
         ap.error("--snapshot must be >= 1")
@@ -58,7 +62,10 @@ def main():
 
     def iteration():
         batch = env.collect(pol, p_actor, args.steps, log_std=log_std, noise_seed=args.seed + 1, critic=val, critic_params=p_critic,
-                            gamma=args.gamma, lam=args.lam, opponent=pol, opponent_params=p_opponent)
+                            gamma=args.gamma, lam=args.lam, opponent=pol, opponent_params=p_opponent, team=args.team,
+                            opponent_team=args.team)
+        if args.team:   # every (env, seat) pair becomes a column: [T, B * S, ...], reward and flags shared by an env's seats
+            batch = seat_rows(batch)
         out = env.ppo_update(batch, pol, p_actor, log_std, val, p_critic, opt, epochs=args.epochs, minibatches=args.minibatches,
                              clip=args.clip, vf_coef=0.5, target_kl=args.target_kl, seed=args.seed)
         return batch["reward"].mean(), out["stats"]

@@ -563,6 +563,54 @@ int rsx_task_collect_selfplay(rsx_sim* h, const rsx_policy_mlp* actor, const flo
                               const rsx_policy_mlp* opponent, const float* opponent_params_dev, const float* opponent_sigma_dev,
                               uint64_t noise_seed, int n_steps, const rsx_collect_out* out, const rsx_selfplay_out* sp, void* stream);
 
+/* ---- team play for VSS-v0: every robot of a side driven by that side's policy inside the launch (additive extension of ABI 6) ------
+ * rsx_task_collect_selfplay extended from one seat per side to all of them.  A SEAT is a robot driven by a policy: blue seat i is blue
+ * robot i, yellow seat i is yellow robot i (body index n_blue + i).  All blue seats share the actor's parameters, all yellow seats the
+ * opponent's.  Equal teams (n = n_blue = n_yellow), VSS-v0 only.
+ *   seat counts      actor_seats is 1 or n_blue; opponent_seats is 0 (opponent must then be NULL), 1 or n_yellow (opponent non-NULL).
+ *                    (1, 0) is rsx_task_collect_policy and (1, 1) rsx_task_collect_selfplay, bit for bit in every output and in the
+ *                    checkpoint afterwards.  Robots that are not seated keep their Ornstein-Uhlenbeck commands.
+ *   seat map         blue seat i sees VSS-v0's row with "own" slots 0 and i exchanged: entry j of the seat's row is entry
+ *                      j + 7 i   for 4 <= j < 11            (slot 0 <- slot i)
+ *                      j - 7 i   for 4 + 7 i <= j < 11 + 7 i  (slot i <- slot 0)
+ *                      j         otherwise                   (the ball [0:4], the remaining "own" slots, every "other" slot)
+ *                    of the side's row.  Seat 0's row is the engine's observation bit for bit.  Yellow seat i sees the mirrored row of
+ *                    rsx_task_collect_selfplay under the same exchange.  The exchange moves float32 values and does no arithmetic.
+ *   forward, head    the arithmetic is rsx_policy_mlp's, unchanged, once per seat on the seat's row.  The Gaussian head is
+ *                    rsx_task_collect_policy's with the seat in Philox counter word 1:
+ *                      counter = (global env id, seat, tick of that step, dom | (i >> 2) << 8),  key = (noise_seed lo, noise_seed hi)
+ *                    dom = 7 for the actor's seats and 9 for the opponent's; component i takes normal i & 3.  Seat 0 therefore draws
+ *                    exactly what rsx_task_collect_policy and rsx_task_collect_selfplay draw.  All seats answer observation t.
+ *   the commands     each seat's two outputs go through VSS-v0's action -> wheel-speed map and replace the command of its robot for
+ *                    that step (blue 0's action takes the engine's own path).  Every Ornstein-Uhlenbeck state keeps advancing on its
+ *                    usual draws, unused: the handle can go back to rsx_task_step, rsx_task_collect_policy or
+ *                    rsx_task_collect_selfplay at any time, and the checkpoint format is untouched.
+ *   everything else  stays the engine's: VSS-v0's ONE reward per env (its energy term on blue 0's command), flags, metrics, same-step
+ *                    auto-reset, the step counter, per-env physics redraws, and the handle's obs / final_obs buffers, which hold seat
+ *                    0's rows. */
+typedef struct rsx_team_side_out {   /* S = that side's seat count */
+    float* obs;       /* [T][B][S][obs_dim]  the row each seat's action answered; required for the actor */
+    float* actions;   /* [T][B][S][2]        required for the actor */
+    float* mean;      /* [T][B][S][2]  or NULL */
+    float* sample;    /* [T][B][S][2]  or NULL */
+    float* final_obs; /* [T][B][S][obs_dim] or NULL: rows of ended (t, env) only */
+    float* next_obs;  /* [B][S][obs_dim]    or NULL: the seats' rows after the last step */
+} rsx_team_side_out;
+typedef struct rsx_team_out {
+    float*   rewards;   /* [T][B]  required */
+    uint8_t* flags;     /* [T][B]  bit 0 terminated, bit 1 truncated; required */
+    rsx_team_side_out actor, opponent;   /* opponent: every member optional, ignored when opponent_seats == 0 */
+} rsx_team_out;
+/* LDS: one image per side in a workgroup, the seat rows made in place (two 40-64-64-2 policies at 8 lanes per env, 3v3: 79 040 B, two
+ * workgroups per CU, what rsx_task_collect_selfplay takes; 5v5 at 16 lanes per env: 84 736 B, one).
+ * Refusals (nothing is enqueued, RSX_ERR_ARG): everything rsx_task_collect_selfplay refuses (of the opponent only when it is seated),
+ * an actor_seats outside {1, n_blue}, an opponent_seats outside {0, 1, n_yellow}, opponent_seats > 0 with a NULL opponent or
+ * opponent_params_dev, opponent_seats == 0 with a non-NULL opponent, a NULL out, rewards, flags, actor.obs or actor.actions. */
+int rsx_task_collect_team(rsx_sim* h, const rsx_policy_mlp* actor, const float* actor_params_dev, const float* sigma_dev, int actor_seats,
+                          const rsx_policy_mlp* opponent /* NULL iff opponent_seats == 0 */, const float* opponent_params_dev,
+                          const float* opponent_sigma_dev, int opponent_seats, uint64_t noise_seed, int n_steps,
+                          const rsx_team_out* out, void* stream);
+
 /* ---- values and GAE advantages of a collected batch (additive extension of ABI 6) ------------------------------------------------
  * What an on-policy trainer does between rsx_task_collect_policy and its gradient step: evaluate a critic on the [T][B] batch and run
  * the reverse recurrence of generalised advantage estimation — two launches instead of a torch critic plus a Python loop over T.

@@ -52,7 +52,7 @@ SYMBOLS = (
     "rsx_task_transfer", "rsx_task_transfer_errors",
     "rsx_task_lookahead_sampled", "rsx_plan_candidates", "rsx_plan_update",
     "rsx_policy_num_params", "rsx_task_lookahead_policy",
-    "rsx_task_collect_policy", "rsx_task_collect_selfplay",
+    "rsx_task_collect_policy", "rsx_task_collect_selfplay", "rsx_task_collect_team",
     "rsx_critic_num_params", "rsx_task_advantages",
     "rsx_ppo_gradient_workspace", "rsx_task_ppo_gradient",
     "rsx_ppo_normalize", "rsx_ppo_permutation", "rsx_adam_step", "rsx_adam_mark", "rsx_ppo_update_workspace", "rsx_task_ppo_update",
@@ -85,6 +85,18 @@ class CollectOut(C.Structure):
 class SelfplayOut(C.Structure):
     """rsx_selfplay_out (include/rsx.h): the opponent's [T][B] record of rsx_task_collect_selfplay; device addresses, each may be None"""
     _fields_ = [("opp_obs", C.c_void_p), ("opp_actions", C.c_void_p), ("opp_mean", C.c_void_p), ("opp_sample", C.c_void_p)]
+
+
+class TeamSideOut(C.Structure):
+    """rsx_team_side_out (include/rsx.h): one side's [T][B][S] record of rsx_task_collect_team; device addresses.  The actor's obs and
+    actions are required, everything else may be None"""
+    _fields_ = [("obs", C.c_void_p), ("actions", C.c_void_p), ("mean", C.c_void_p), ("sample", C.c_void_p), ("final_obs", C.c_void_p),
+                ("next_obs", C.c_void_p)]
+
+
+class TeamOut(C.Structure):
+    """rsx_team_out (include/rsx.h): the record of rsx_task_collect_team: rewards and flags [T][B] and a TeamSideOut per side"""
+    _fields_ = [("rewards", C.c_void_p), ("flags", C.c_void_p), ("actor", TeamSideOut), ("opponent", TeamSideOut)]
 
 
 class AdvIn(C.Structure):
@@ -256,6 +268,8 @@ def load():
     lib.rsx_task_collect_policy.argtypes = [vp, C.POINTER(PolicyMLP), vp, vp, C.c_uint64, ip, C.POINTER(CollectOut), vp]
     lib.rsx_task_collect_selfplay.argtypes = [vp, C.POINTER(PolicyMLP), vp, vp, C.POINTER(PolicyMLP), vp, vp, C.c_uint64, ip,
                                               C.POINTER(CollectOut), C.POINTER(SelfplayOut), vp]
+    lib.rsx_task_collect_team.argtypes = [vp, C.POINTER(PolicyMLP), vp, vp, ip, C.POINTER(PolicyMLP), vp, vp, ip, C.c_uint64, ip,
+                                          C.POINTER(TeamOut), vp]
     lib.rsx_critic_num_params.argtypes = [vp, C.POINTER(PolicyMLP), C.POINTER(C.c_int64)]
     lib.rsx_task_advantages.argtypes = [vp, C.POINTER(PolicyMLP), vp, C.c_float, C.c_float, ip, ip, C.POINTER(AdvIn), C.POINTER(AdvOut), vp]
     lib.rsx_ppo_gradient_workspace.argtypes = [vp, C.POINTER(PolicyMLP), C.POINTER(PolicyMLP), C.c_int64, ip, C.POINTER(C.c_int64)]
@@ -663,6 +677,18 @@ class Sim:
         ref = lambda v: None if v is None else C.byref(v)   # noqa: E731
         rc = self._lib.rsx_task_collect_selfplay(self._h, ref(spec), params_ptr, sigma_ptr, ref(opp_spec), opp_params_ptr, opp_sigma_ptr,
                                                  int(noise_seed) & 0xFFFFFFFFFFFFFFFF, int(n_steps), ref(out), ref(sp), stream)
+        if rc:
+            _chk(rc)
+
+    def task_collect_team(self, spec, params_ptr, sigma_ptr, seats, opp_spec, opp_params_ptr, opp_sigma_ptr, opp_seats, noise_seed, n_steps,
+                          out, stream=None):
+        """rsx_task_collect_team: ``task_collect_selfplay`` with ``seats`` (1 or n_blue) blue robots driven by ``spec`` and ``opp_seats``
+        (0 with ``opp_spec`` None, 1 or n_yellow) yellow robots by ``opp_spec``, each seat from its own row; ``out``: a TeamOut of device
+        addresses (records with a seat axis behind B), or None to pass NULL."""
+        ref = lambda v: None if v is None else C.byref(v)   # noqa: E731
+        rc = self._lib.rsx_task_collect_team(self._h, ref(spec), params_ptr, sigma_ptr, int(seats), ref(opp_spec), opp_params_ptr,
+                                             opp_sigma_ptr, int(opp_seats), int(noise_seed) & 0xFFFFFFFFFFFFFFFF, int(n_steps), ref(out),
+                                             stream)
         if rc:
             _chk(rc)
 

@@ -429,6 +429,48 @@ int rsx_task_collect_selfplay(rsx_sim* h, const rsx_policy_mlp* actor, const flo
     return debug_finite(h, s, "rsx_task_collect_selfplay");
 }
 
+// ---- the same with every robot of a side seated under that side's policy (rsx.h: rsx_task_collect_team) ----
+int rsx_task_collect_team(rsx_sim* h, const rsx_policy_mlp* actor, const float* actor_params_dev, const float* sigma_dev, int actor_seats,
+                          const rsx_policy_mlp* opponent, const float* opponent_params_dev, const float* opponent_sigma_dev,
+                          int opponent_seats, uint64_t noise_seed, int n_steps, const rsx_team_out* out, void* stream) {
+    RSX_ENTER(h);
+    PolicySpec S, S2; int64_t n_params = 0, n_opp_params = 0;
+    if (int rc = policy_prologue(h, actor, &S, &n_params)) return rc;
+    if (h->P.task != RSX_TASK_VSS_V0)
+        return fail(RSX_ERR_ARG, "rsx_task_collect_team serves VSS-v0 only: a seat drives a robot of that task");
+    if (h->P.n_blue != h->P.n_yellow)
+        return fail(RSX_ERR_ARG, "rsx_task_collect_team needs equal teams: the mirrored observation has the agent's layout");
+    if (actor_seats != 1 && actor_seats != h->P.n_blue) return fail(RSX_ERR_ARG, "actor_seats must be 1 or n_blue");
+    if (opponent_seats != 0 && opponent_seats != 1 && opponent_seats != h->P.n_yellow)
+        return fail(RSX_ERR_ARG, "opponent_seats must be 0, 1 or n_yellow");
+    if ((opponent != nullptr) != (opponent_seats > 0))
+        return fail(RSX_ERR_ARG, "the opponent (rsx_policy_mlp) must be null exactly when opponent_seats is 0");
+    if (opponent)
+        if (int rc = policy_prologue(h, opponent, &S2, &n_opp_params)) return rc;
+    RSX_NEED_RESET(h);
+    if (n_steps < 1 || n_steps > RSX_N_STEPS_MASK) return fail(RSX_ERR_ARG, "n_steps must be in 1 .. 2^30 - 1");
+    if (!actor_params_dev || (opponent && !opponent_params_dev))
+        return fail(RSX_ERR_ARG, "actor_params_dev and, with an opponent, opponent_params_dev must not be null");
+    if (!out || !out->rewards || !out->flags || !out->actor.obs || !out->actor.actions)
+        return fail(RSX_ERR_ARG, "out and its rewards, flags, actor.obs and actor.actions arrays must not be null");
+    if (h->L > 32) return fail(RSX_ERR_ARG, "rsx_task_collect_team has no 64-lanes-per-env kernels (unset RSX_LANES_PER_ENV)");
+    if (team_lds_bytes(h->L, h->P.obs_dim, h->M.act_dim, h->P.n_blue, S, opponent ? &S2 : nullptr) > 163840ll)
+        return fail(RSX_ERR_ARG, "the policies' weights do not fit a CU's 160 KB of LDS at this observation width: use fewer or smaller hidden layers");
+    hipStream_t s = (hipStream_t)stream;
+    int fl = 0;
+    if (int rc = step_prologue(h, s, (uint64_t)n_steps, &fl)) return rc;   // capture of a host-keyed handle, counter limit
+    h->host_state_valid = false;
+    const int grid = grid_for(h);   // (the tick slots: as rsx_task_collect_policy, the launch has its grid)
+    if (h->tick_dev) launch_tick_fill(tick_slot0(h), h->tick_slots, grid, 0u, 1, s);
+    h->P.tick_base = h->tick; h->tick += (uint32_t)n_steps;
+    launch_task_collect_team(h->P, buffers_of(h, nullptr), h->L, h->NR, h->d_phys, S, actor_params_dev, (int)n_params, sigma_dev, actor_seats,
+                             opponent ? &S2 : nullptr, opponent_params_dev, (int)n_opp_params, opponent_sigma_dev, opponent_seats,
+                             h->M.act_dim, noise_seed, n_steps | fl, *out, s);
+    if (h->tick_dev) launch_tick_fill(tick_slot0(h), grid, h->tick_slots, 0u, 1, s);
+    HIP_TRY(launch_status());
+    return debug_finite(h, s, "rsx_task_collect_team");
+}
+
 // ---- values and GAE advantages of a [T][B] batch (rsx.h: rsx_task_advantages).  The handle gives the device and obs_dim; nothing of it is touched ----
 // what both calls check of a critic; on success S is the spec as the kernels take it and *n_params the floats of one critic
 static int critic_prologue(const rsx_sim* h, const rsx_policy_mlp* c, PolicySpec* S, int64_t* n_params) {

@@ -8,6 +8,7 @@
 struct rsx_render_view;   // include/rsx.h
 struct rsx_collect_out;
 struct rsx_selfplay_out;
+struct rsx_team_out;
 struct rsx_adv_in;
 struct rsx_adv_out;
 struct rsx_ppo_in;
@@ -105,6 +106,15 @@ void launch_task_collect_selfplay(const Params& P, const Buffers& b, int L, int 
                                   int n_params, const PolicySpec& opp, const float* opp_params, int n_opp_params, int act_dim,
                                   const float* sigma, const float* opp_sigma, uint64_t noise_seed, int n_steps, const rsx_collect_out& out,
                                   const rsx_selfplay_out& sp, hipStream_t s);
+// rsx_teamplay.hip: the same collection with every robot of a side driven by that side's policy (rsx_task_collect_team).  seats: 1 or
+// n_blue blue robots under p / params / sigma; opp_seats: 0 (opp is null: no opponent), 1 or n_yellow yellow robots under opp / opp_params /
+// opp_sigma; out: both sides' records with a seat axis, checked.  team_lds_bytes: LDS of one workgroup of that launch (Shared<L> and one
+// image per side, the action slot sized for n_blue seats: the host refuses more than a CU's 160 KB)
+long long team_lds_bytes(int L, int obs_dim, int act_dim, int n_blue, const PolicySpec& agent, const PolicySpec* opponent);
+void launch_task_collect_team(const Params& P, const Buffers& b, int L, int NR, float* phys, const PolicySpec& p, const float* params,
+                              int n_params, const float* sigma, int seats, const PolicySpec* opp, const float* opp_params, int n_opp_params,
+                              const float* opp_sigma, int opp_seats, int act_dim, uint64_t noise_seed, int n_steps, const rsx_team_out& out,
+                              hipStream_t s);
 // rsx_gae.hip: values and GAE advantages of a [T][B] batch (rsx_task_advantages).  critic: rsx_policy_mlp with act_dim = 1 and a linear
 // output, checked; params: [P]; gl: (float)gamma * (float)lam; in / out: the call's arrays, checked.  Two launches: the critic over
 // T * B + B rows (and the rows truncated only of final_obs), then the reverse scan.  form: which values kernel (GAE_FORM_ROWS: one row per

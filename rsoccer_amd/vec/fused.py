@@ -258,7 +258,8 @@ class VecFusedEnv(RenderMixin):
         return out
 
     def collect(self, policy, params, steps, log_std=None, noise_seed=None, iteration=0, return_final_obs=False,
-                critic=None, critic_params=None, gamma=0.99, lam=0.95, opponent=None, opponent_params=None, opponent_log_std=None):
+                critic=None, critic_params=None, gamma=0.99, lam=0.95, opponent=None, opponent_params=None, opponent_log_std=None,
+                team=False, opponent_team=False):
         """Advance the envs ``steps`` steps under an MLP policy in ONE launch and return the on-policy batch
         (``rsx_task_collect_policy``): what a PPO / A2C loop calls between two updates.
 
@@ -296,6 +297,20 @@ class VecFusedEnv(RenderMixin):
         can be handed back to ``step()`` or a plain ``collect()`` at any time: yellow 0's noise state kept advancing, unused.  A typical
         loop copies the learner's parameters into ``opponent_params`` every few updates (``examples/selfplay_vss.py``).  With
         ``opponent=None`` the call, its launches and its outputs are exactly what they are without these keywords.
+
+        Team play (VSS-v0 with equal teams, ``rsx_task_collect_team``): ``team=True`` seats ALL blue robots under ``policy`` /
+        ``params`` / ``log_std`` — blue seat ``i`` is blue robot ``i`` and sees the env's row with "own" slots 0 and ``i`` exchanged —
+        and ``opponent_team=True`` (needs ``opponent``) seats all yellow robots under the opponent's, each from the mirrored row under
+        the same exchange.  The flags combine freely: ``team=True`` alone, with the one-robot opponent, or with the opponent's team.
+        Each seat's head draws noise of its own (the seat index is part of the counter; seat 0 draws what it draws without the flags).
+        The reward stays VSS-v0's one reward per env.  When either flag is set, ``obs``, ``actions``, ``mean``, ``sample``,
+        ``log_prob`` and ``final_obs`` (with a critic also ``value``, ``advantage``, ``return``) and the ``opponent_*`` tensors gain a
+        seat axis behind ``B`` — ``obs`` ``[T, B, S, obs_dim]``, ``log_prob`` ``[T, B, S]`` — while ``reward``, ``terminated`` and
+        ``truncated`` stay ``[T, B]``; ``next_obs`` is a fresh ``[B, S, obs_dim]`` tensor (the env's own ``obs`` view still holds seat 0's) and the
+        dict also carries ``opponent_next_obs`` and, with ``return_final_obs``, ``opponent_final_obs``.  ``critic=`` evaluates the
+        critic on every seat's rows and runs GAE per (env, seat) with the shared reward and flags.
+        ``rsoccer_amd.vec.policy.seat_rows(batch)`` turns such a batch into the ``[T, B * S, ...]`` mapping ``advantages()``,
+        ``ppo_gradient()`` and ``ppo_update()`` take.  With both flags false nothing changes.
         Capturable into a ``torch.cuda.CUDAGraph`` after ``enable_graph_capture()``: every replay draws fresh noise."""
         torch = self._torch
         from rsoccer_amd.vec.policy import MLPPolicy
@@ -330,6 +345,12 @@ class VecFusedEnv(RenderMixin):
             oshape = tuple(np.shape(opponent_params))
             if oshape != (opponent.num_params,):
                 raise ValueError(f"opponent_params must be [{opponent.num_params}] (one policy), got {oshape}")
+        team, opponent_team = bool(team), bool(opponent_team)
+        if opponent_team and opponent is None:
+            raise ValueError("opponent_team given without an opponent")
+        if (team or opponent_team) and (self.TASK != _lib.TASK_VSS_V0 or self.N_BLUE != self.N_YELLOW):
+            raise ValueError(f"{'team' if team else 'opponent_team'}: team play seats the robots of VSS-v0 with equal teams, "
+                             f"this env is {type(self).__name__}")
         dev, B, OD, AD = self.device, self.num_envs, self.sim.obs_dim, self.sim.act_dim
 
         def device_params(v):
@@ -367,6 +388,16 @@ class VecFusedEnv(RenderMixin):
             z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
             noise_seed = z ^ (z >> 31)
         f32 = dict(dtype=torch.float32, device=dev)
+        if team or opponent_team:
+            op = None if opponent is None else device_params(opponent_params)
+            out = self._collect_team(policy, p, ls, sigma, self.N_BLUE if team else 1, opponent, op, ols, osigma,
+                                     0 if opponent is None else self.N_YELLOW if opponent_team else 1, noise_seed, T, return_final_obs)
+            if critic is not None:
+                from rsoccer_amd.vec.policy import seat_rows
+                S = out["obs"].shape[2]
+                adv = self._advantages(seat_rows(out), critic, cp, float(gamma), float(lam), False)
+                out.update({k: v.view(T, B, S) for k, v in adv.items()})
+            return out
         obs = torch.empty((T, B, OD), **f32)
         acts = torch.empty((T, B, AD), **f32)
         rew = torch.empty((T, B), **f32)
@@ -405,6 +436,46 @@ class VecFusedEnv(RenderMixin):
             out["log_prob"] = (-0.5 * z * z - ls - 0.9189385332046727).sum(-1)   # 0.5 * log(2 pi)
         if critic is not None:
             out.update(self._advantages(out, critic, cp, float(gamma), float(lam), False))
+        return out
+
+    def _collect_team(self, policy, p, ls, sigma, seats, opponent, op, ols, osigma, opp_seats, noise_seed, T, return_final_obs):
+        """collect()'s launch and batch with seats (rsx_task_collect_team); every argument checked and on the device already"""
+        torch = self._torch
+        dev, B, OD, AD = self.device, self.num_envs, self.sim.obs_dim, self.sim.act_dim
+        f32 = dict(dtype=torch.float32, device=dev)
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+
+        def side(S, sig):
+            """one side's record: (tensors by name, the TeamSideOut of their addresses)"""
+            if S == 0:
+                return {}, _lib.TeamSideOut()
+            t = {"obs": torch.empty((T, B, S, OD), **f32), "actions": torch.empty((T, B, S, AD), **f32),
+                 "mean": torch.empty((T, B, S, AD), **f32) if sig is not None else None,
+                 "sample": torch.empty((T, B, S, AD), **f32) if sig is not None else None,
+                 "final_obs": torch.zeros((T, B, S, OD), **f32) if return_final_obs else None,
+                 "next_obs": torch.empty((B, S, OD), **f32)}
+            return t, _lib.TeamSideOut(*(ptr(t[k]) for k in ("obs", "actions", "mean", "sample", "final_obs", "next_obs")))
+
+        rew = torch.empty((T, B), **f32)
+        flags = torch.empty((T, B), dtype=torch.uint8, device=dev)
+        a, a_out = side(seats, sigma)
+        o, o_out = side(opp_seats, osigma)
+        rec = _lib.TeamOut(ptr(rew), ptr(flags), a_out, o_out)
+        self.sim.task_collect_team(policy.spec(), p.data_ptr(), ptr(sigma), seats, None if opponent is None else opponent.spec(), ptr(op),
+                                   ptr(osigma), opp_seats, noise_seed, T, rec, self._stream())
+        self._keep_plan = (p, sigma, op, osigma)   # alive until the launch has consumed them
+        out = {"obs": a["obs"], "actions": a["actions"], "reward": rew, "terminated": (flags & 1).bool(), "truncated": (flags & 2).bool(),
+               "next_obs": a["next_obs"]}
+        for pre, t, lsd, sig in (("", a, ls, sigma), ("opponent_", o, ols, osigma)):
+            if not t:
+                continue
+            out[pre + "obs"], out[pre + "actions"], out[pre + "next_obs"] = t["obs"], t["actions"], t["next_obs"]
+            if return_final_obs:
+                out[pre + "final_obs"] = t["final_obs"]
+            if sig is not None:
+                out[pre + "mean"], out[pre + "sample"] = t["mean"], t["sample"]
+                z = (t["sample"] - t["mean"]) / sig
+                out[pre + "log_prob"] = (-0.5 * z * z - lsd - 0.9189385332046727).sum(-1)   # 0.5 * log(2 pi)
         return out
 
     def _critic_args(self, critic, params, gamma, lam):

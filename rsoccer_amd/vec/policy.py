@@ -123,3 +123,42 @@ class MLPCritic(MLPPolicy):
     def _torch_acts(self):
         hid, _ = super()._torch_acts()
         return hid, (lambda v: v)
+
+
+_SEAT_KEYS = ("obs", "actions", "mean", "sample", "log_prob", "final_obs", "value", "advantage", "return")
+
+
+def seat_rows(batch, opponent=False):
+    """A team batch of ``VecFusedEnv.collect(..., team=True)`` (or ``opponent_team=True``) as the ``[T, B * S, ...]`` mapping
+    ``advantages()``, ``ppo_gradient()`` and ``ppo_update()`` accept: every (env, seat) pair becomes a column of its own, column
+    ``e * S + s``.  The seat tensors ``[T, B, S, ...]`` (``obs``, ``actions``, ``mean``, ``sample``, ``log_prob``, ``final_obs`` and, if
+    present, ``value``, ``advantage``, ``return``) are viewed as ``[T, B * S, ...]`` and ``next_obs`` ``[B, S, obs_dim]`` as
+    ``[B * S, obs_dim]``; ``reward``, ``terminated`` and ``truncated`` ``[T, B]`` are expanded to ``[T, B * S]`` — the seats of an env
+    share its reward and its episode ends.  Everything returned is contiguous.  ``opponent=True`` takes the ``opponent_*`` tensors
+    instead (with the same shared reward and flags: negate the reward for a zero-sum learner)."""
+    pre = "opponent_" if opponent else ""
+    for key in (pre + "obs", pre + "next_obs", "reward", "terminated", "truncated"):
+        if key not in batch:
+            raise ValueError(f"batch lacks {key!r}")
+    obs = batch[pre + "obs"]
+    if obs.dim() != 4:
+        raise ValueError(f"batch[{pre + 'obs'!r}] must be [T, B, S, obs_dim] (a team batch), got {list(obs.shape)}")
+    T, B, S = int(obs.shape[0]), int(obs.shape[1]), int(obs.shape[2])
+    out = {}
+    for key in _SEAT_KEYS:
+        t = batch.get(pre + key)
+        if t is None:
+            continue
+        if tuple(t.shape[:3]) != (T, B, S):
+            raise ValueError(f"batch[{pre + key!r}] must start with [{T}, {B}, {S}], got {list(t.shape)}")
+        out[key] = t.reshape(T, B * S, *t.shape[3:]).contiguous()
+    nxt = batch[pre + "next_obs"]
+    if tuple(nxt.shape[:2]) != (B, S):
+        raise ValueError(f"batch[{pre + 'next_obs'!r}] must start with [{B}, {S}], got {list(nxt.shape)}")
+    out["next_obs"] = nxt.reshape(B * S, *nxt.shape[2:]).contiguous()
+    for key in ("reward", "terminated", "truncated"):
+        t = batch[key]
+        if tuple(t.shape) != (T, B):
+            raise ValueError(f"batch[{key!r}] must be [{T}, {B}], got {list(t.shape)}")
+        out[key] = t.unsqueeze(-1).expand(T, B, S).reshape(T, B * S).contiguous()
+    return out
