@@ -62,11 +62,27 @@ def lockstep_step(r, blue_actions, yellow_actions):
     return obs, np.float32(reward), ended or done
 
 
-def raw_team(torch, _lib, env, pol, params, sigma, seats, opp, opp_params, opp_sigma, opp_seats, noise_seed, steps, final_obs=True):
+def lockstep_episode_step(r, blue_actions, yellow_actions, opponent_rows=False):
+    """lockstep_step through episode ends (selfplay_helpers.episode_step) for any number of seats: blue seat 0 through task_step itself,
+    blue seats 1.. and every yellow seat by replaced commands.  One blue seat and no yellow seat: no command is replaced and the step
+    is task_step's own.  -> (obs row t + 1, reward, terminated, truncated, final_obs or None, dropped): seat 0's rows; the other
+    seats' are their seat_map, the opponent's the mirror (opponent_rows)."""
+    blue = np.asarray(blue_actions, dtype=np.float32).reshape(-1, 2)
+    yellow = np.asarray(yellow_actions, dtype=np.float32).reshape(-1, 2)
+    seated = [(i, blue[i]) for i in range(1, len(blue))] + [(r.n_blue + i, yellow[i]) for i in range(len(yellow))]
+    return SH.episode_step(r, blue[0], seated, opponent_rows)
+
+
+def raw_team(torch, _lib, env, pol, params, sigma, seats, opp, opp_params, opp_sigma, opp_seats, noise_seed, steps, final_obs=True, fill=None):
     """env.sim.task_collect_team with the seat counts as given — (1, 0) and (1, 1) included, which collect() never asks for — on tensors
-    made here; returns the batch under collect()'s names, seat axis behind B, device tensors."""
+    made here; returns the batch under collect()'s names, seat axis behind B, device tensors.  `fill`: a 32-bit pattern every output
+    word holds before the call (the flags its low byte), instead of torch.empty's memory and final_obs's zeros; "flags" is then
+    returned too."""
     dev, B, OD, AD = env.device, env.num_envs, env.sim.obs_dim, env.sim.act_dim
     f32 = dict(dtype=torch.float32, device=dev)
+    empty = zeros = SH.filled(torch, dev, fill)
+    if fill is None:
+        empty, zeros = (lambda s: torch.empty(s, **f32)), (lambda s: torch.zeros(s, **f32))   # noqa: E731
     ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
     keep = [params.to(dev), None if sigma is None else sigma.to(dev), None if opp_params is None else opp_params.to(dev),
             None if opp_sigma is None else opp_sigma.to(dev)]
@@ -74,20 +90,21 @@ def raw_team(torch, _lib, env, pol, params, sigma, seats, opp, opp_params, opp_s
     def side(S, sig):
         if S == 0:
             return {}, _lib.TeamSideOut()
-        t = {"obs": torch.empty((steps, B, S, OD), **f32), "actions": torch.empty((steps, B, S, AD), **f32),
-             "mean": None if sig is None else torch.empty((steps, B, S, AD), **f32),
-             "sample": None if sig is None else torch.empty((steps, B, S, AD), **f32),
-             "final_obs": torch.zeros((steps, B, S, OD), **f32) if final_obs else None, "next_obs": torch.empty((B, S, OD), **f32)}
+        t = {"obs": empty((steps, B, S, OD)), "actions": empty((steps, B, S, AD)),
+             "mean": None if sig is None else empty((steps, B, S, AD)), "sample": None if sig is None else empty((steps, B, S, AD)),
+             "final_obs": zeros((steps, B, S, OD)) if final_obs else None, "next_obs": empty((B, S, OD))}
         return t, _lib.TeamSideOut(*(ptr(t[k]) for k in ("obs", "actions", "mean", "sample", "final_obs", "next_obs")))
 
-    rew = torch.empty((steps, B), **f32)
-    flags = torch.empty((steps, B), dtype=torch.uint8, device=dev)
+    rew = empty((steps, B))
+    flags = torch.full((steps, B), (fill or 0) & 0xFF, dtype=torch.uint8, device=dev)
     a, a_out = side(seats, keep[1])
     o, o_out = side(opp_seats, keep[3])
     env.sim.task_collect_team(pol.spec(), keep[0].data_ptr(), ptr(keep[1]), seats, None if opp is None else opp.spec(), ptr(keep[2]),
                               ptr(keep[3]), opp_seats, noise_seed, steps, _lib.TeamOut(ptr(rew), ptr(flags), a_out, o_out), env._stream())
     torch.cuda.synchronize()   # (the parameter tensors above live until here)
     out = {"reward": rew, "terminated": (flags & 1).bool(), "truncated": (flags & 2).bool()}
+    if fill is not None:
+        out["flags"] = flags
     out.update({k: v for k, v in a.items() if v is not None})
     out.update({"opponent_" + k: v for k, v in o.items() if v is not None})
     return out

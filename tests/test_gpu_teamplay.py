@@ -387,7 +387,7 @@ def test_5v5_runs_the_native_16_lane_variant(oracle_mod):
     from rsoccer_amd import vec
     B = 5
     make = lambda: PL._make(vec, "VecVSS5v5", B, device=0, seed=2025)   # noqa: E731
-    assert SH.oracle_alone_ends(oracle_mod, B, 2025) * 8 <= B
+    assert SH.oracle_alone_ends(oracle_mod, B, 2025, nb=5) * 8 <= B
     env, _, out, _ = _lockstep(oracle_mod, torch, vec, B, SH.SHAPE_LARGE, SH.SHAPE_LARGE, 5, 5, n=5, make=make)   # check 5
     assert env.sim.obs_dim == 64 and env.sim.task_layout() == "16-lanes-per-env"
     assert out["obs"].shape == (T, B, 5, 64) and out["opponent_actions"].shape == (T, B, 5, 2)
