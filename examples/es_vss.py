@@ -1,12 +1,14 @@
 """Evolution strategies on VSS-v0 with whole episodes scored in one launch per generation.
 
-    python examples/es_vss.py [--envs 256] [--pairs 32] [--generations 5] [--sigma 0.05] [--lr 0.01] [--horizon N]
+    python examples/es_vss.py [--envs 256] [--pairs 32] [--generations 5] [--sigma 0.05] [--lr 0.01] [--horizon N] [--opponent]
 
 One generation: reset() gives every env a fresh start state; lookahead_policy(..., horizon=max_episode_steps) then runs the 2 * pairs
 perturbed policies theta +- sigma * eps closed-loop from exactly those states against exactly the same future draws (the other robots'
 OU noise is keyed by env and step, not by who asks): common random numbers for free, so the antithetic difference of two returns is
 the policy's doing.  Fitness = mean return over the envs; the update is the plain antithetic ES estimator on rank-centred fitness.
-The env is never stepped: a generation is two engine launches (reset, lookahead_policy) and a handful of torch ops."""
+The env is never stepped: a generation is two engine launches (reset, lookahead_policy) and a handful of torch ops.  With --opponent
+the population is scored against a frozen opponent instead of Ornstein-Uhlenbeck noise: yellow robot 0 plays the initial theta from the
+mirrored observation, in the same single launch (lookahead_match with K = population, M = 1)."""
 import argparse
 import os
 import sys
@@ -28,6 +30,7 @@ def main():
     ap.add_argument("--lr", type=float, default=0.01)
     ap.add_argument("--horizon", type=int, default=None, help="steps per evaluation (default: max_episode_steps, whole episodes)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--opponent", action="store_true", help="score the population against a frozen opponent (the initial theta on yellow 0)")
     args = ap.parse_args()
 
     env = VecVSSEnv(args.envs, device=0, seed=args.seed)
@@ -37,20 +40,26 @@ def main():
     theta = torch.nn.utils.parameters_to_vector(torch.nn.Sequential(
         torch.nn.Linear(pol.obs_dim, 64), torch.nn.Tanh(), torch.nn.Linear(64, 64), torch.nn.Tanh(),
         torch.nn.Linear(64, pol.act_dim), torch.nn.Tanh()).parameters()).detach().to(env.device)   # torch's own layout
+    frozen = theta.clone().unsqueeze(0)   # [1, P]: the opponent of --opponent
     n = args.pairs
     for g in range(args.generations):
         t0 = time.perf_counter()
         eps = torch.randn(n, pol.num_params, device=env.device, generator=gen)
         params = torch.cat([theta + args.sigma * eps, theta - args.sigma * eps, theta[None]])   # the last row: theta itself
         env.reset()
-        out = env.lookahead_policy(pol, params, H)
-        fitness = out["return"].mean(dim=0)   # [2 n + 1]: mean return over the envs
+        if args.opponent:   # the same launch shape with yellow 0 under the frozen policy: [B, 2 n + 1, 1]
+            out = env.lookahead_match(pol, params, pol, frozen, H)
+            wins = int((out["result"][:, -1, 0] > 0).sum())
+        else:
+            out = env.lookahead_policy(pol, params, H)
+        fitness = out["return"].reshape(args.envs, -1).mean(dim=0)   # [2 n + 1]: mean return over the envs
         ranks = fitness[:2 * n].argsort().argsort().float() / (2 * n - 1) - 0.5
         theta = theta + args.lr / (n * args.sigma) * ((ranks[:n] - ranks[n:]) @ eps)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         steps = int(out["steps"].sum())
-        print(f"generation {g}: fitness of theta {float(fitness[-1]):+.3f}, population mean {float(fitness[:2 * n].mean()):+.3f} "
+        versus = f" ({wins} of {args.envs} episodes won against the frozen opponent)" if args.opponent else ""
+        print(f"generation {g}: fitness of theta {float(fitness[-1]):+.3f}{versus}, population mean {float(fitness[:2 * n].mean()):+.3f} "
               f"best {float(fitness[:2 * n].max()):+.3f}; {steps} env-steps in {dt * 1e3:.1f} ms ({steps / dt / 1e6:.1f} M env-steps/s)")
     env.close()
 

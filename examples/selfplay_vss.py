@@ -1,6 +1,6 @@
 """Self-play PPO on VSS-v0: the learner (blue 0) against a frozen earlier copy of itself (yellow 0), both evaluated inside one launch.
 
-    python examples/selfplay_vss.py [--envs 1024] [--steps 128] [--updates 20] [--snapshot 5] [--graph] [--team]
+    python examples/selfplay_vss.py [--envs 1024] [--steps 128] [--updates 20] [--snapshot 5] [--graph] [--team] [--league M]
 
 The --device-update loop of examples/ppo_vss.py with one change: env.collect(..., opponent=pol, opponent_params=p_opponent) drives
 yellow robot 0 by a second copy of the policy, which sees the mirrored observation (team colours swapped, the field turned by 180
@@ -10,7 +10,11 @@ needs no re-capture: the captured collect + ppo_update reads whatever the tensor
 their Ornstein-Uhlenbeck noise.  With --team the whole team learns against a snapshot team: collect(..., team=True, opponent_team=True)
 seats all three robots of each side (every seat sees its side's row with "own" slots 0 and i exchanged and shares its side's
 parameters), and rsoccer_amd.vec.policy.seat_rows turns the [T, B, S, ...] batch into the [T, B * S, ...] rows ppo_update takes: three
-samples per env step, one shared reward.  A demonstration of the call pattern, not a tuned trainer."""
+samples per env step, one shared reward.  With --league M the last M snapshots are kept in ONE [M, P] device tensor, a ring written by
+copy_.  At every snapshot the learner plays whole episodes against all of them in one env.lookahead_match on a forked evaluation env
+straight after its reset() — the same start states and the same draws for every opponent, nothing committed — the win / draw / loss row
+is printed (rsoccer_amd.vec.policy.match_table), and the next opponent is drawn from that row: the more the learner loses or draws against
+a snapshot, the likelier it trains against it.  A demonstration of the call pattern, not a tuned trainer."""
 import argparse
 import os
 import sys
@@ -21,7 +25,7 @@ import torch
 
 from rsoccer_amd.vec import VecVSSEnv
 from rsoccer_amd.vec.optim import PPOOptimizer
-from rsoccer_amd.vec.policy import MLPCritic, MLPPolicy, seat_rows
+from rsoccer_amd.vec.policy import MLPCritic, MLPPolicy, match_table, seat_rows
 
 
 def main():
@@ -41,9 +45,14 @@ def main():
     ap.add_argument("--max-grad-norm", type=float, default=0.5, help="the global-norm clip (<= 0: none)")
     ap.add_argument("--target-kl", type=float, default=None, help="stop an update's steps once approx_kl exceeds this")
     ap.add_argument("--team", action="store_true", help="seat every robot of both sides: the team learns against a snapshot team")
+    ap.add_argument("--league", type=int, default=0, metavar="M", help="keep the last M snapshots, score the learner against all of them "
+                    "at every snapshot (one lookahead_match) and draw the next opponent from the result")
+    ap.add_argument("--eval-envs", type=int, default=256, help="envs of the forked evaluation env (--league)")
     args = ap.parse_args()
     if args.snapshot < 1:
         ap.error("--snapshot must be >= 1")
+    if args.league < 0 or args.eval_envs < 1:
+        ap.error("--league must be >= 0 and --eval-envs >= 1")
 
     torch.manual_seed(args.seed)
     env = VecVSSEnv(args.envs, device=0, seed=args.seed)
@@ -57,8 +66,25 @@ def main():
     log_std = torch.full((AD,), -0.5, device=dev)
     opt = PPOOptimizer(pol, val, device=dev, lr=args.lr, max_grad_norm=args.max_grad_norm)
     env.reset()
+    if args.league:
+        ring = p_actor.clone().unsqueeze(0).repeat(args.league, 1)   # [M, P]: the last M snapshots, slot `snapshots % M` is written next
+        snapshots = 1                                                # (slot 0 holds the initial copy)
+        evaluation = env.fork(args.eval_envs, seed=args.seed + 1000)
+        pick = torch.Generator().manual_seed(args.seed)
     if args.graph:
         env.enable_graph_capture()
+
+    def league_round():
+        """the learner against every kept snapshot from the same start states -> the slot of the next opponent"""
+        evaluation.reset()
+        kept = min(snapshots, args.league)
+        out = evaluation.lookahead_match(pol, p_actor.unsqueeze(0), pol, ring[:kept], evaluation.max_episode_steps, team=args.team,
+                                         opponent_team=args.team)
+        table = {k: v[0].cpu() for k, v in match_table(out).items()}   # the learner's row: [kept]
+        print("  league: " + ", ".join(f"slot {m}: {int(table['wins'][m])} / {int(table['draws'][m])} / {int(table['losses'][m])} "
+                                        f"(mean return {float(table['mean_return'][m]):+.2f})" for m in range(kept)) + "  (win / draw / loss)")
+        weight = (table["losses"] + 0.5 * table["draws"] + 1.0).double()   # never zero: every snapshot keeps a chance
+        return int(torch.multinomial(weight / weight.sum(), 1, generator=pick))
 
     def iteration():
         batch = env.collect(pol, p_actor, args.steps, log_std=log_std, noise_seed=args.seed + 1, critic=val, critic_params=p_critic,
@@ -74,7 +100,12 @@ def main():
     for update in range(args.updates):
         t0 = time.perf_counter()
         if update and update % args.snapshot == 0:
-            p_opponent.copy_(p_actor)   # one device copy; the captured graph reads the tensor it was captured with
+            if args.league:
+                ring[snapshots % args.league].copy_(p_actor)
+                snapshots += 1
+                p_opponent.copy_(ring[league_round()])
+            else:
+                p_opponent.copy_(p_actor)   # one device copy; the captured graph reads the tensor it was captured with
         if args.graph and update == 1:   # (iteration 0 ran eagerly: torch's warm-up before a capture)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
@@ -89,6 +120,8 @@ def main():
               f"{m['goals_for']} / {m['goals_against']}, sigma {log_std.exp().mean().item():.3f}, learner - opponent "
               f"{(p_actor - p_opponent).norm().item():.4f}, steps applied {int(stats[:, :, 9].sum())} / {stats.shape[0] * stats.shape[1]}; "
               f"{(time.perf_counter() - t0) * 1e3:.1f} ms{' (one graph replay)' if graph is not None else ''}")
+    if args.league:
+        evaluation.close()
     env.close()
 
 

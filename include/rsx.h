@@ -611,6 +611,58 @@ int rsx_task_collect_team(rsx_sim* h, const rsx_policy_mlp* actor, const float* 
                           const float* opponent_sigma_dev, int opponent_seats, uint64_t noise_seed, int n_steps,
                           const rsx_team_out* out, void* stream);
 
+/* ---- matches for VSS-v0: policy against policy inside the lookahead launch (additive extension of ABI 6) --------------------------
+ * What a self-play loop asks after every snapshot — did the learner get better, and against whom? — and what a population method
+ * needs to run against a frozen opponent: rsx_task_lookahead_policy with rsx_task_collect_team's opponent.  Triple (e, k, m) is env e
+ * played by actor k (blue) against opponent m (yellow) from where env e stands now to its first episode end, for all K x M pairs of
+ * every env in ONE launch, from the same start states and against the same future draws.  The handle is left exactly as it was.
+ *   scope            VSS-v0 with equal teams only (3v3, 5v5 and the run-time counts such as 2v2).  actor_seats is 1 or n_blue,
+ *                    opponent_seats is 1 or n_yellow.  There is no 0: without an opponent the call is rsx_task_lookahead_policy.
+ *   actor ...        an rsx_policy_mlp and actor_params_dev [K][P], K = n_actors: rsx_task_lookahead_policy's p and params_dev.
+ *   opponent ...     an rsx_policy_mlp of its own (layers and hidden may differ) and opponent_params_dev [M][P2], M = n_opponents, in
+ *                    the same layout for the same obs_dim and act_dim.  Device memory is not checked.
+ *   a step           rsx_task_collect_team's step with deterministic heads: sample = mean, action = out_act(mean).  Every seat of
+ *                    both sides answers observation t.  Blue seat i sees the side's row with "own" slots 0 and i exchanged (that
+ *                    section's seat map), yellow seats the mirrored row of rsx_task_collect_selfplay under the same exchange.  Each
+ *                    seated robot's command is replaced (blue 0's action takes the engine's own path); every Ornstein-Uhlenbeck state
+ *                    advances on its usual draws, unused.  The draws are the env's real future ones, at tick (current tick) + t, as in
+ *                    rsx_task_lookahead_policy.  No stochastic heads in this call: evaluation noise is the caller's parameter noise.
+ *   step 0           sees the env's row of the handle's obs buffer, as rsx_task_lookahead_policy does, and its mirror computed from
+ *                    the state the call starts from, as rsx_task_collect_selfplay does.
+ *   a pair           stops at its env's first episode end.  returns, steps, flags and last_obs follow rsx_task_lookahead's rules
+ *                    (the same float32 recurrence: ret = ret + disc * r_t; disc = disc * gamma; blue's reward).  result is what the task's
+ *                    reward reports of the ending step: the goal for (+1) or against (-1) that the metrics' goals_for /
+ *                    goals_against count, 0 for a pair that ran into the time limit or the horizon.  Recording rows behind a pair's
+ *                    end are not written. */
+typedef struct rsx_match_out {          /* pair index p = (e * K + k) * M + m;  S = actor_seats, S2 = opponent_seats */
+    float*   returns;      /* [B][K][M]  required: blue's return, rsx_task_lookahead's float32 recurrence */
+    int32_t* steps;        /* [B][K][M]  required */
+    uint8_t* flags;        /* [B][K][M]  required: bit 0 terminated, bit 1 truncated */
+    int8_t*  result;       /* [B][K][M]  or NULL: +1 a goal FOR blue (the actor) ended the pair, -1 a goal against it, 0 otherwise */
+    float*   last_obs;     /* [B][K][M][obs_dim] or NULL: blue seat 0's row after the pair's last step (terminal if it ended) */
+    float*   actions;      /* [B][K][M][H][S][2]  or NULL */
+    float*   obs;          /* [B][K][M][H][S][obs_dim] or NULL: the row each actor seat's action answered */
+    float*   opp_actions;  /* [B][K][M][H][S2][2] or NULL */
+    float*   opp_obs;      /* [B][K][M][H][S2][obs_dim] or NULL */
+} rsx_match_out;
+/* Exactness: from the same handle state, rsx_task_collect_team(actor = params[k], sigma = NULL, opponent = params2[m], sigma = NULL,
+ * the same seat counts, n_steps = H) produces per env the same bits in rows t < steps[e][k][m]: obs, actions, opp_obs, opp_actions,
+ * rewards (through the return recurrence) and flags at the last row; with final_obs recorded, last_obs of an ended pair equals it.
+ * This holds on every lane width (8, 16, 32), with and without per-env physics, on host-keyed and device-keyed handles.
+ * No side effects: the call reads what rsx_task_lookahead_policy reads (the state, the scalar arena, the obs buffer, the step counter)
+ * and both parameter arrays, and writes only `out`.  Stream-ordered, never synchronises, capturable under that call's conditions (a
+ * launch at the counter limit of a device-keyed handle simulates nothing).
+ * LDS: one image per side in a workgroup, as rsx_task_collect_team (two 40-64-64-2 policies at 8 lanes per env, 3v3: 79 040 B, two
+ * workgroups per CU; 5v5 at 16 lanes per env: 84 736 B, one).  One 64-lane workgroup per (tile of envs, k, m).
+ * Refusals (RSX_ERR_ARG, nothing is enqueued): everything rsx_task_lookahead_policy refuses of a handle and of each policy (the LDS
+ * limit is the CU's 160 KB for both images together, the check rsx_task_collect_team makes); a task other than VSS-v0, or unequal
+ * teams; an actor_seats outside {1, n_blue} or an opponent_seats outside {1, n_yellow}; n_actors or n_opponents < 1; a null opponent,
+ * actor_params_dev, opponent_params_dev, out, returns, steps or flags; lane_grid x K x M workgroups over the launch limit (2^31 - 1,
+ * the check rsx_task_lookahead makes for n_candidates). */
+int rsx_task_lookahead_match(rsx_sim* h, const rsx_policy_mlp* actor, const float* actor_params_dev /* [K][P] */, int n_actors, int actor_seats,
+                             const rsx_policy_mlp* opponent, const float* opponent_params_dev /* [M][P2] */, int n_opponents, int opponent_seats,
+                             int horizon, float gamma, const rsx_match_out* out, void* stream);
+
 /* ---- values and GAE advantages of a collected batch (additive extension of ABI 6) ------------------------------------------------
  * What an on-policy trainer does between rsx_task_collect_policy and its gradient step: evaluate a critic on the [T][B] batch and run
  * the reverse recurrence of generalised advantage estimation — two launches instead of a torch critic plus a Python loop over T.

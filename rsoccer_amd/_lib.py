@@ -51,7 +51,7 @@ SYMBOLS = (
     "rsx_render_view_reference", "rsx_render_size", "rsx_render_field", "rsx_render_open", "rsx_render", "rsx_render_errors",
     "rsx_task_transfer", "rsx_task_transfer_errors",
     "rsx_task_lookahead_sampled", "rsx_plan_candidates", "rsx_plan_update",
-    "rsx_policy_num_params", "rsx_task_lookahead_policy",
+    "rsx_policy_num_params", "rsx_task_lookahead_policy", "rsx_task_lookahead_match",
     "rsx_task_collect_policy", "rsx_task_collect_selfplay", "rsx_task_collect_team",
     "rsx_critic_num_params", "rsx_task_advantages",
     "rsx_ppo_gradient_workspace", "rsx_task_ppo_gradient",
@@ -97,6 +97,13 @@ class TeamSideOut(C.Structure):
 class TeamOut(C.Structure):
     """rsx_team_out (include/rsx.h): the record of rsx_task_collect_team: rewards and flags [T][B] and a TeamSideOut per side"""
     _fields_ = [("rewards", C.c_void_p), ("flags", C.c_void_p), ("actor", TeamSideOut), ("opponent", TeamSideOut)]
+
+
+class MatchOut(C.Structure):
+    """rsx_match_out (include/rsx.h): the [B][K][M] results and records of rsx_task_lookahead_match; device addresses, everything
+    behind flags may be None"""
+    _fields_ = [("returns", C.c_void_p), ("steps", C.c_void_p), ("flags", C.c_void_p), ("result", C.c_void_p), ("last_obs", C.c_void_p),
+                ("actions", C.c_void_p), ("obs", C.c_void_p), ("opp_actions", C.c_void_p), ("opp_obs", C.c_void_p)]
 
 
 class AdvIn(C.Structure):
@@ -268,6 +275,8 @@ def load():
     lib.rsx_task_collect_policy.argtypes = [vp, C.POINTER(PolicyMLP), vp, vp, C.c_uint64, ip, C.POINTER(CollectOut), vp]
     lib.rsx_task_collect_selfplay.argtypes = [vp, C.POINTER(PolicyMLP), vp, vp, C.POINTER(PolicyMLP), vp, vp, C.c_uint64, ip,
                                               C.POINTER(CollectOut), C.POINTER(SelfplayOut), vp]
+    lib.rsx_task_lookahead_match.argtypes = [vp, C.POINTER(PolicyMLP), vp, ip, ip, C.POINTER(PolicyMLP), vp, ip, ip, ip, C.c_float,
+                                             C.POINTER(MatchOut), vp]
     lib.rsx_task_collect_team.argtypes = [vp, C.POINTER(PolicyMLP), vp, vp, ip, C.POINTER(PolicyMLP), vp, vp, ip, C.c_uint64, ip,
                                           C.POINTER(TeamOut), vp]
     lib.rsx_critic_num_params.argtypes = [vp, C.POINTER(PolicyMLP), C.POINTER(C.c_int64)]
@@ -657,6 +666,17 @@ class Sim:
         rc = self._lib.rsx_task_lookahead_policy(self._h, None if spec is None else C.byref(spec), params_ptr, int(n_policies), int(horizon),
                                                  float(gamma), returns_ptr, steps_ptr, flags_ptr, last_obs_ptr, actions_out_ptr, obs_out_ptr,
                                                  stream)
+        if rc:
+            _chk(rc)
+
+    def task_lookahead_match(self, spec, params_ptr, n_actors, seats, opp_spec, opp_params_ptr, n_opponents, opp_seats, horizon, gamma, out,
+                             stream=None):
+        """rsx_task_lookahead_match: ``task_lookahead_policy`` on a VSS-v0 handle against an opponent: pair (env, k, m) is actor k of
+        ``spec`` (params [K][P] f32, ``seats`` = 1 or n_blue robots seated) against opponent m of ``opp_spec`` (params [M][P2] f32,
+        ``opp_seats`` = 1 or n_yellow); ``out``: a MatchOut of device addresses, or None to pass NULL."""
+        ref = lambda v: None if v is None else C.byref(v)   # noqa: E731
+        rc = self._lib.rsx_task_lookahead_match(self._h, ref(spec), params_ptr, int(n_actors), int(seats), ref(opp_spec), opp_params_ptr,
+                                                int(n_opponents), int(opp_seats), int(horizon), float(gamma), ref(out), stream)
         if rc:
             _chk(rc)
 

@@ -360,6 +360,45 @@ int rsx_task_lookahead_policy(rsx_sim* h, const rsx_policy_mlp* p, const float* 
     return RSX_OK;
 }
 
+// ---- the same against an opponent: K actors x M opponents per env of VSS-v0 in one launch (rsx.h: rsx_task_lookahead_match) ----
+int rsx_task_lookahead_match(rsx_sim* h, const rsx_policy_mlp* actor, const float* actor_params_dev, int n_actors, int actor_seats,
+                             const rsx_policy_mlp* opponent, const float* opponent_params_dev, int n_opponents, int opponent_seats,
+                             int horizon, float gamma, const rsx_match_out* out, void* stream) {
+    RSX_ENTER(h);   // (as rsx_task_lookahead: nothing the handle owns changes)
+    PolicySpec S, S2; int64_t n_params = 0, n_opp_params = 0;
+    if (int rc = policy_prologue(h, actor, &S, &n_params)) return rc;
+    if (h->P.task != RSX_TASK_VSS_V0)
+        return fail(RSX_ERR_ARG, "rsx_task_lookahead_match serves VSS-v0 only: a seat drives a robot of that task");
+    if (h->P.n_blue != h->P.n_yellow)
+        return fail(RSX_ERR_ARG, "rsx_task_lookahead_match needs equal teams: the mirrored observation has the agent's layout");
+    if (actor_seats != 1 && actor_seats != h->P.n_blue) return fail(RSX_ERR_ARG, "actor_seats must be 1 or n_blue");
+    if (opponent_seats != 1 && opponent_seats != h->P.n_yellow)
+        return fail(RSX_ERR_ARG, "opponent_seats must be 1 or n_yellow (without an opponent the call is rsx_task_lookahead_policy)");
+    if (!opponent) return fail(RSX_ERR_ARG, "the opponent (rsx_policy_mlp) must not be null");
+    if (int rc = policy_prologue(h, opponent, &S2, &n_opp_params)) return rc;
+    RSX_NEED_RESET(h);
+    if (n_actors < 1 || n_opponents < 1 || horizon < 1) return fail(RSX_ERR_ARG, "n_actors, n_opponents and horizon must be >= 1");
+    if (!actor_params_dev || !opponent_params_dev) return fail(RSX_ERR_ARG, "actor_params_dev and opponent_params_dev must not be null");
+    if (!out || !out->returns || !out->steps || !out->flags)
+        return fail(RSX_ERR_ARG, "out and its returns, steps and flags arrays must not be null");
+    if (!std::isfinite(gamma)) return fail(RSX_ERR_ARG, "gamma must be finite");
+    if (h->L > 32) return fail(RSX_ERR_ARG, "rsx_task_lookahead_match has no 64-lanes-per-env kernels (unset RSX_LANES_PER_ENV)");
+    const long long pairs = (long long)n_actors * (long long)n_opponents;
+    if (pairs > 0x7FFFFFFFll || lookahead_grid(h->L, h->P.num_envs, (int)pairs) > 0x7FFFFFFFll)
+        return fail(RSX_ERR_ARG, "num_envs x n_actors x n_opponents exceeds the launch limit (2^31 - 1 workgroups): split the policies over several calls");
+    if (match_lds_bytes(h->L, h->P.obs_dim, h->M.act_dim, h->P.n_blue, S, S2) > 163840ll)
+        return fail(RSX_ERR_ARG, "the policies' weights do not fit a CU's 160 KB of LDS at this observation width: use fewer or smaller hidden layers");
+    int fl = 0;
+    if (int rc = step_prologue(h, (hipStream_t)stream, (uint64_t)horizon, &fl)) return rc;   // capture of a host-keyed handle, counter limit
+    Params P = h->P;
+    P.tick_base = h->tick;   // the tick the next step would take; not advanced
+    launch_task_lookahead_match(P, h->L, h->NR, h->d_state, h->d_aux, h->d_obs, h->tick_dev ? tick_slot0(h) : nullptr, h->d_phys, S,
+                                actor_params_dev, (int)n_params, n_actors, actor_seats, S2, opponent_params_dev, (int)n_opp_params, n_opponents,
+                                opponent_seats, h->M.act_dim, horizon, gamma, *out, (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
 // ---- on-policy collection: n steps under the policy in one launch, the [T][B] batch written out (rsx.h: rsx_task_collect_policy) ----
 int rsx_task_collect_policy(rsx_sim* h, const rsx_policy_mlp* p, const float* params_dev, const float* sigma_dev, uint64_t noise_seed,
                             int n_steps, const rsx_collect_out* out, void* stream) {

@@ -34,6 +34,7 @@
 #include "rsx.h"
 #include "rsx_plan_common.hpp"
 #include "rsx_policy_mlp.hpp"
+#include "rsx_seats.hpp"
 #include "rsx_units.hpp"
 #include "rsx_variants.hpp"
 
@@ -66,39 +67,7 @@ struct SelfplayArgs {
     float* sample;         // [T][B][2] or nullptr
 };
 
-// The opponent's observation entries owned by this lane -> the mirrored row of its env: VSS-v0's observation (rsx_task.hpp:
-// write_obs_nb) with the team colours swapped and the field turned by 180 degrees.  "Own" slot i holds yellow i, "other" slot j blue j;
-// positions, linear velocities, sine and cosine are negated (clamp(-v) == -clamp(v) exactly), the angular velocity is unchanged.
-// Equal teams (checked by the host), so the layout and obs_dim are the agent's.
-__device__ __forceinline__ void write_obs_mirrored(const Params& P, float* __restrict__ row, const int b, const int nb, const bool is_robot,
-                                                   const bool is_ball, const float x, const float y, const float vx, const float vy,
-                                                   const float sn, const float cs, const float om_deg) {
-    using T = TC<RSX_TASK_VSS_V0>;
-    const float lo = -1.2f, hi = 1.2f;
-    if (is_ball) {
-        row[0] = -clampf(x * P.inv_max_pos, lo, hi);
-        row[1] = -clampf(y * P.inv_max_pos, lo, hi);
-        row[2] = -clampf(vx * T::inv_max_v, lo, hi);
-        row[3] = -clampf(vy * T::inv_max_v, lo, hi);
-    } else if (is_robot) {
-        if (b >= nb) {   // yellow b - nb: an "own" slot
-            float* r = row + 4 + 7 * (b - nb);
-            r[0] = -clampf(x * P.inv_max_pos, lo, hi);
-            r[1] = -clampf(y * P.inv_max_pos, lo, hi);
-            r[2] = -sn; r[3] = -cs;
-            r[4] = -clampf(vx * T::inv_max_v, lo, hi);
-            r[5] = -clampf(vy * T::inv_max_v, lo, hi);
-            r[6] = clampf(om_deg * T::inv_max_w, lo, hi);
-        } else {         // blue b: an "other" slot (behind the nb = ny own slots)
-            float* r = row + 4 + 7 * nb + 5 * b;
-            r[0] = -clampf(x * P.inv_max_pos, lo, hi);
-            r[1] = -clampf(y * P.inv_max_pos, lo, hi);
-            r[2] = -clampf(vx * T::inv_max_v, lo, hi);
-            r[3] = -clampf(vy * T::inv_max_v, lo, hi);
-            r[4] = clampf(om_deg * T::inv_max_w, lo, hi);
-        }
-    }
-}
+// (the mirrored row, write_obs_mirrored: rsx_seats.hpp)
 
 // one component of a Gaussian head (rsx_collect.hip's, with the domain word a parameter): component b takes normal b & 3 of block b >> 2
 __device__ __forceinline__ float head_sample(const float mean, const float sigma, const uint32_t env_id, const uint32_t t, const int b,

@@ -115,6 +115,15 @@ void launch_task_collect_team(const Params& P, const Buffers& b, int L, int NR, 
                               int n_params, const float* sigma, int seats, const PolicySpec* opp, const float* opp_params, int n_opp_params,
                               const float* opp_sigma, int opp_seats, int act_dim, uint64_t noise_seed, int n_steps, const rsx_team_out& out,
                               hipStream_t s);
+// rsx_match.hip: the policy lookahead with an opponent (rsx_task_lookahead_match): pair (env, k, m) under actor k of params [n_actors][n_params]
+// and opponent m of opp_params [n_opponents][n_opp_params], seats / opp_seats robots of a side seated; state / aux / obs / ticks / phys as for
+// launch_task_lookahead_policy, read only; out: the call's arrays, checked.  match_lds_bytes: LDS of one workgroup of that launch
+// (team_lds_bytes with both sides seated: the host refuses more than a CU's 160 KB)
+long long match_lds_bytes(int L, int obs_dim, int act_dim, int n_blue, const PolicySpec& actor, const PolicySpec& opponent);
+void launch_task_lookahead_match(const Params& P, int L, int NR, const float* state, const float* aux, const float* obs, const uint32_t* ticks,
+                                 const float* phys, const PolicySpec& p, const float* params, int n_params, int n_actors, int seats,
+                                 const PolicySpec& opp, const float* opp_params, int n_opp_params, int n_opponents, int opp_seats, int act_dim,
+                                 int horizon, float gamma, const rsx_match_out& out, hipStream_t s);
 // rsx_gae.hip: values and GAE advantages of a [T][B] batch (rsx_task_advantages).  critic: rsx_policy_mlp with act_dim = 1 and a linear
 // output, checked; params: [P]; gl: (float)gamma * (float)lam; in / out: the call's arrays, checked.  Two launches: the critic over
 // T * B + B rows (and the rows truncated only of final_obs), then the reverse scan.  form: which values kernel (GAE_FORM_ROWS: one row per

@@ -257,6 +257,88 @@ class VecFusedEnv(RenderMixin):
             out["policy_obs"] = pobs
         return out
 
+    def lookahead_match(self, policy, params, opponent, opponent_params, horizon, gamma=1.0, team=False, opponent_team=False,
+                        return_obs=False, return_actions=False, return_policy_obs=False):
+        """``lookahead_policy()`` against an opponent (VSS-v0 with equal teams, ``rsx_task_lookahead_match``): ``K`` actors against ``M``
+        opponents from every env's current state, in ONE launch.
+
+        ``policy`` / ``params`` ``[K, P]``: the actors (blue), as ``lookahead_policy()`` takes them; ``opponent`` / ``opponent_params``
+        ``[M, P2]``: the opponents (yellow), an ``MLPPolicy`` of this env's dims whose layers and hidden may differ.  Triple
+        (env, k, m) starts from where the env stands now and runs to the env's first episode end or ``horizon`` steps.  A step is
+        ``collect(opponent=...)``'s step with deterministic heads: the opponent answers the mirrored observation of the same instant;
+        ``team=True`` seats every blue robot under actor ``k`` and ``opponent_team=True`` every yellow robot under opponent ``m``, each
+        from its seat's row, as ``collect(team=..., opponent_team=...)`` does.  The draws are the env's real future ones and the env is
+        left exactly as it was.  ``horizon=max_episode_steps`` straight after ``reset()`` plays whole episodes: all ``K x M`` pairs
+        from the same ``B`` start states.
+
+        Returns a dict of fresh device tensors: ``return`` ``[B, K, M]`` (blue's), ``steps``, ``terminated``, ``truncated`` and
+        ``result`` (int8: +1 the pair ended on a goal for blue, -1 on one for yellow, 0 otherwise); with ``return_obs`` ``last_obs``
+        ``[B, K, M, obs_dim]``; with ``return_actions`` ``actions`` ``[B, K, M, H, 2]`` and ``opponent_actions``; with
+        ``return_policy_obs`` ``policy_obs`` ``[B, K, M, H, obs_dim]`` and ``opponent_obs``.  A side's recordings gain a seat axis
+        behind ``H`` when that side's flag is set (``[B, K, M, H, S, 2]``); entries behind a pair's end stay zero.
+        ``rsoccer_amd.vec.policy.match_table(out)`` folds the envs into ``[K, M]`` wins, draws, losses and mean return.
+        Capturable after ``enable_graph_capture()``."""
+        torch = self._torch
+        from rsoccer_amd.vec.policy import MLPPolicy
+        if not isinstance(policy, MLPPolicy):
+            raise ValueError("policy must be an rsoccer_amd.vec.policy.MLPPolicy")
+        if not isinstance(opponent, MLPPolicy):
+            raise ValueError("opponent must be an rsoccer_amd.vec.policy.MLPPolicy")
+        if self.TASK != _lib.TASK_VSS_V0 or self.N_BLUE != self.N_YELLOW:
+            raise ValueError(f"lookahead_match: a match is played on VSS-v0 with equal teams, this env is {type(self).__name__}")
+        H, gamma = int(horizon), float(gamma)
+        if H < 1:
+            raise ValueError(f"horizon must be >= 1, got {horizon}")
+        if not np.isfinite(gamma):
+            raise ValueError("gamma must be finite")
+        if self.sim.act_dim != policy.act_dim or self.sim.obs_dim != policy.obs_dim:
+            raise ValueError(f"the policy maps {policy.obs_dim} -> {policy.act_dim}, the env {self.sim.obs_dim} -> {self.sim.act_dim}")
+        if self.sim.act_dim != opponent.act_dim or self.sim.obs_dim != opponent.obs_dim:
+            raise ValueError(f"the opponent maps {opponent.obs_dim} -> {opponent.act_dim}, the env {self.sim.obs_dim} -> {self.sim.act_dim}")
+        if params is None or opponent_params is None:
+            raise ValueError("params and opponent_params must not be None")
+        shape, oshape = tuple(np.shape(params)), tuple(np.shape(opponent_params))   # checked on the INPUT: a 1-D vector is not promoted
+        if len(shape) != 2 or shape[0] < 1 or shape[1] != policy.num_params:
+            raise ValueError(f"params must be [K >= 1, {policy.num_params}], got {shape}")
+        if len(oshape) != 2 or oshape[0] < 1 or oshape[1] != opponent.num_params:
+            raise ValueError(f"opponent_params must be [M >= 1, {opponent.num_params}], got {oshape}")
+        K, M = int(shape[0]), int(oshape[0])
+        B, dev, OD, AD = self.num_envs, self.device, self.sim.obs_dim, self.sim.act_dim
+
+        def device_params(v):
+            if isinstance(v, torch.Tensor):
+                t = v.detach()
+                if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+                    t = t.to(device=dev, dtype=torch.float32).contiguous()
+                return t
+            return torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dev)
+
+        p, op = device_params(params), device_params(opponent_params)
+        S, S2 = (self.N_BLUE if team else 1), (self.N_YELLOW if opponent_team else 1)
+        f32 = dict(dtype=torch.float32, device=dev)
+        ret = torch.empty((B, K, M), **f32)
+        steps = torch.empty((B, K, M), dtype=torch.int32, device=dev)
+        flags = torch.empty((B, K, M), dtype=torch.uint8, device=dev)
+        result = torch.empty((B, K, M), dtype=torch.int8, device=dev)
+        last = torch.empty((B, K, M, OD), **f32) if return_obs else None
+        acts = torch.zeros((B, K, M, H, S, AD), **f32) if return_actions else None
+        oacts = torch.zeros((B, K, M, H, S2, AD), **f32) if return_actions else None
+        pobs = torch.zeros((B, K, M, H, S, OD), **f32) if return_policy_obs else None
+        oobs = torch.zeros((B, K, M, H, S2, OD), **f32) if return_policy_obs else None
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        rec = _lib.MatchOut(ptr(ret), ptr(steps), ptr(flags), ptr(result), ptr(last), ptr(acts), ptr(pobs), ptr(oacts), ptr(oobs))
+        self.sim.task_lookahead_match(policy.spec(), p.data_ptr(), K, S, opponent.spec(), op.data_ptr(), M, S2, H, gamma, rec, self._stream())
+        self._keep_plan = (p, op)   # alive until the launch has consumed them
+        out = {"return": ret, "steps": steps, "terminated": (flags & 1).bool(), "truncated": (flags & 2).bool(), "result": result}
+        if return_obs:
+            out["last_obs"] = last
+        seat = lambda t, flag: t if flag else t[:, :, :, :, 0]   # noqa: E731  (the seat axis only where that side's flag is set)
+        if return_actions:
+            out["actions"], out["opponent_actions"] = seat(acts, team), seat(oacts, opponent_team)
+        if return_policy_obs:
+            out["policy_obs"], out["opponent_obs"] = seat(pobs, team), seat(oobs, opponent_team)
+        return out
+
     def collect(self, policy, params, steps, log_std=None, noise_seed=None, iteration=0, return_final_obs=False,
                 critic=None, critic_params=None, gamma=0.99, lam=0.95, opponent=None, opponent_params=None, opponent_log_std=None,
                 team=False, opponent_team=False):

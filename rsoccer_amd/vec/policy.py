@@ -162,3 +162,17 @@ def seat_rows(batch, opponent=False):
             raise ValueError(f"batch[{key!r}] must be [{T}, {B}], got {list(t.shape)}")
         out[key] = t.unsqueeze(-1).expand(T, B, S).reshape(T, B * S).contiguous()
     return out
+
+
+def match_table(out):
+    """The ``[K, M]`` table of a ``VecFusedEnv.lookahead_match()`` result, folded over the envs: ``wins`` (pairs that ended on a goal
+    for the actor, ``result == 1``), ``losses`` (``result == -1``) and ``draws`` (everything else: time limit, horizon) as int64 counts
+    that sum to ``B`` per cell, and ``mean_return`` float32.  Pure torch on the tensors' device; does not synchronise."""
+    for key in ("result", "return"):
+        if key not in out:
+            raise ValueError(f"out lacks {key!r}")
+    res, ret = out["result"], out["return"]
+    if res.dim() != 3 or tuple(ret.shape) != tuple(res.shape):
+        raise ValueError(f"out['result'] and out['return'] must be [B, K, M], got {list(res.shape)} and {list(ret.shape)}")
+    wins, losses = (res > 0).sum(0), (res < 0).sum(0)
+    return {"wins": wins, "draws": res.shape[0] - wins - losses, "losses": losses, "mean_return": ret.float().mean(0)}
