@@ -84,6 +84,66 @@ def test_the_normalisation_restatement_is_float64s_to_rounding(n):
     assert np.abs(out - ref).max() <= 4.0 * 2.0 ** -24 * max(1.0, np.abs(ref).max())
 
 
+def _header_order_sum(x, cap):
+    """include/rsx.h's reduction order as the header words it, one scalar float64 addition at a time: thread j of workgroup w adds its
+    elements 256 w + j, + 256 G, ... from 0.0; the 64 lanes of a wave ascending from 0.0; the waves ((w0 + w1) + w2) + w3; the G
+    partials in workgroup order from 0.0"""
+    x = [float(v) for v in x]
+    n = len(x)
+    G = min((n + 255) // 256, cap)
+    total = 0.0
+    for w in range(G):
+        waves = []
+        for wave in range(4):
+            acc = 0.0
+            for lane in range(64):
+                mine, i = 0.0, 256 * w + 64 * wave + lane
+                while i < n:
+                    mine += x[i]
+                    i += 256 * G
+                acc += mine
+            waves.append(acc)
+        total += ((waves[0] + waves[1]) + waves[2]) + waves[3]
+    return total
+
+
+def _wide_input(n, seed):
+    """float64 entries of both signs spread over 30 binary orders of magnitude"""
+    rng = np.random.default_rng(seed)
+    return rng.uniform(1.0, 2.0, n) * np.exp2(rng.integers(-15, 16, n)) * rng.choice([-1.0, 1.0], n)
+
+
+FIXED_SUM_CASES = [(cap, n) for cap in (1, 2, 3) for n in (255, 256, 257, 513, 1500, 2049)] + [(128, 32769), (64, 16385)]
+
+
+@pytest.mark.parametrize("cap,n", FIXED_SUM_CASES)
+def test_fixed_sum_is_the_headers_order_beyond_one_trip(cap, n):
+    """fixed_sum's array code against the scalar loop above, on bit patterns, at sizes where a thread holds two and more elements;
+    both within the float64 bound of recursive summation in any order, (n - 1) u / (1 - (n - 1) u) * sum |x| with u = 2^-53"""
+    import math
+    for k, x in enumerate((_wide_input(n, 100 * cap + n), np.random.default_rng(n + cap).normal(3.0, 0.5, n).astype(np.float32).astype(np.float64))):
+        got, want = H.fixed_sum(x, cap), _header_order_sum(x, cap)
+        assert np.float64(got).tobytes() == np.float64(want).tobytes(), (cap, n, k, float(got), want)
+        u = 2.0 ** -53
+        bound = (n - 1) * u / (1.0 - (n - 1) * u) * math.fsum(abs(v) for v in x)
+        exact = math.fsum(x)
+        assert abs(float(got) - exact) <= bound and abs(want - exact) <= bound, (cap, n, k)
+
+
+def test_another_order_gives_other_bits():
+    """the proof that the comparison above can fail: on the wide input a plain ascending sum differs from the fixed order in bits"""
+    n, cap = 2049, 3
+    x = _wide_input(n, 100 * cap + n)
+    plain = 0.0
+    for v in x:
+        plain += float(v)
+    fixed = _header_order_sum(x, cap)
+    assert np.float64(plain).tobytes() != np.float64(fixed).tobytes()
+    assert np.float64(H.fixed_sum(x, cap)).tobytes() == np.float64(fixed).tobytes()
+    # one trip fewer (a cap that holds every element in a first trip) is another order as well
+    assert np.float64(_header_order_sum(x, 9)).tobytes() != np.float64(fixed).tobytes()
+
+
 def test_the_clip_adam_restatement_follows_torch():
     import torch
     rng = np.random.default_rng(3)
