@@ -925,6 +925,101 @@ int rsx_task_ppo_update(rsx_sim* h, const rsx_policy_mlp* actor, float* actor_pa
                         const rsx_ppo_update_cfg* u, const rsx_adam_cfg* adam, const rsx_adam_state* st, float* stats_dev,
                         void* workspace, void* stream);
 
+/* ---- TD3 / DDPG loss gradients of an MLP actor and one or two Q critics on replayed transitions (additive extension of ABI 6) ------
+ * What an off-policy trainer does with a minibatch between sampling it and its optimiser steps: the target actor and target critics
+ * on next_obs, the critics on (obs, action), the actor through critic 0, and the gradients of both losses — four launches instead of
+ * torch's gather, six MLP forwards and two backward().
+ *   the handle       supplies only the device, obs_dim (OD), act_dim (AD) and the error string, as for rsx_task_ppo_gradient: the call
+ *                    reads and writes NOTHING of the envs.
+ *   transitions      N flat rows: obs [N][OD], action [N][AD] (the executed action, after out_act), reward [N], next_obs [N][OD],
+ *                    terminated [N] bytes (non-zero = true).  A row that ended on a time limit carries terminated = 0 and its terminal
+ *                    observation as next_obs: the target bootstraps through it.
+ *   rows             the minibatch, rsx_ppo_in's rules: flat indices into the N rows, repeats allowed, NULL = rows 0 .. M - 1; an index
+ *                    outside [0, N) contributes nothing to any output, is counted in stats[8], and nothing outside the arrays is read for it.
+ *   actor            an rsx_policy_mlp with out_act RSX_ACT_TANH or RSX_ACT_CLIP, actor_params_dev [Pa] (rsx_policy_num_params) and
+ *                    target_actor_params_dev [Pa].
+ *   critics          C = cfg->n_critics in {1, 2} networks of ONE shape: an rsx_policy_mlp with out_act = RSX_ACT_NONE whose input row is
+ *                    the OD observation floats followed by the AD action floats — torch's Linear(OD + AD, hidden) layout, so
+ *                    Pc = hidden * (OD + AD) + hidden (+ hidden * hidden + hidden) + hidden + 1.  critic_params_dev and
+ *                    target_critic_params_dev are [C][Pc].
+ * The loss; mu is the actor's output accumulator before out_act, pi = out_act(mu), a mean is the sum over the M entries times the
+ * float32 1 / M (skipped entries do not change the divisor), t is an entry's POSITION in the minibatch:
+ *   noise_k          clamp(sigma * eps_k, -noise_clip, noise_clip) in float32.  eps: the collector's standard-normal recipe (Philox, 7
+ *                    rounds, the two-word Box-Muller pair of rsx_task_collect_policy) under domain word 10: counter (t, noise_step >> 32,
+ *                    noise_step & 0xFFFFFFFF, 10 | (k >> 2) << 8), key = noise_seed (lo, hi); component k takes normal k & 3 of its
+ *                    block.  A draw depends on the position in the minibatch — not on rows[t], the grid or the device.  noise_step is
+ *                    cfg->noise_step, or, with noise_step_dev non-NULL, the int64 it points to, read on the device when the launch
+ *                    runs: a replayed graph draws fresh noise when that counter was advanced.
+ *   a'_k             clamp(pi_targ(next_obs)_k + noise_k, -1, 1); with sigma == 0 no draw is made and a' = pi_targ(next_obs) (DDPG).
+ *   y                terminated ? reward : reward + gamma * min over c of Q_targ_c(next_obs, a')   (two roundings).  No gradient flows
+ *                    into y; min and both clamps are continuous, a tie of the two critics leaves y what either gives.
+ *   L_q              sum over c of 0.5 * mean((Q_c(obs, action) - y)^2): grad_critics[c] = dL_q / d(critic c's parameters).
+ *   L_pi             -mean(Q_0(obs, pi(obs))): grad_actor = dL_pi / d(actor's parameters).  Critic 0 is differentiated with respect to
+ *                    its action inputs, dQ/da_k = sum over j of W1[j][OD + k] * dz1[j], not its weights.  Through out_act: tanh passes
+ *                    1 - pi^2; clip follows torch's clamp: 1 where -1 <= mu <= 1, bounds included, else 0.
+ * With out->grad_actor == NULL the actor launch is skipped (TD3's delayed policy update): stats[4] is 0, out->action is not written and
+ * every other output has the bits it has with the actor launch.
+ * Arithmetic, all float32, the unit is built with -ffp-contract=off.  Forwards: rsx_policy_mlp's, bit for bit (per unit acc = bias,
+ * ascending fmaf over the OD observation floats, then over the AD action floats; the same tanh), so out->action equals what
+ * rsx_task_collect_policy records without noise.  Backward: rsx_task_ppo_gradient's rules — entries in blocks of 64, workgroup w of
+ * G = min(ceil(M / 64), max_workgroups) takes blocks w, w + G, ...; dL_q/dQ_c = (Q_c - y) * (1 / M), dL_pi/dQ_0 = -(1 / M);
+ * dz = (W^T d(next)) * act' with the second layer's product summed as four interleaved fmaf chains over the units, combined
+ * (s0 + s1) + (s2 + s3), and dQ/da_k summed the same way over the units j; a weight gradient is ONE fmaf chain per workgroup over all its
+ * entries in the order it met them, starting from 0 (v_mfma_f32_32x32x2_f32 for the hidden layers' weights); a bias gradient — unlike
+ * rsx_task_ppo_gradient's — adds, per block of 64 entries, the workgroup's running sum and the block's terms in ascending order in
+ * float64 and rounds to float32 once (a critic's output bias gradient is mean(Q - y), whose terms cancel); the per-workgroup partials
+ * are then added in workgroup order from 0; the stats are summed per lane (entry mod 64), then over
+ * the lanes in ascending order, then over the workgroups.  The result bits are a function of the inputs and of G alone.
+ *   stats            [9]: 0 / 1 L_q of critic 0 / 1 (0.5 * mean((Q_c - y)^2); 0 for an absent critic), 2 / 3 mean Q_0 / Q_1, 4 L_pi,
+ *                    5 mean y, 6 mean |a'| (the mean over the entries of sum_k |a'_k|, divided by AD), 7 entries used, 8 entries skipped
+ *   per entry        optional, 0 for a skipped entry: target [M] = y; q [C][M]; action [M][AD] = pi(obs) (actor launch only);
+ *                    target_noise [M][AD] = noise as added (0 with sigma == 0)
+ *   workspace        at least rsx_dpg_gradient_workspace bytes (y, one float per entry more, one partial per workgroup and network),
+ *                    16-byte aligned, for the same n_critics, n_rows and max_workgroups; its contents before the call do not matter
+ *   max_workgroups   0: the default, a constant of the build (256), not the device's CU count; > 0: caps G
+ * LDS per workgroup at the largest shape (2 x 64 units, OD = 64, AD = 5, C = 2): targets 128 000 B, critic 63 344 B, actor 136 080 B;
+ * gfx950 has 160 KB per CU.  A shape that needs more than 163 840 B in a launch is refused with the byte count in the error string.
+ * Stream-ordered, never synchronises, never allocates, capturable.  Refusals (nothing is enqueued, rsx_last_error says why), all
+ * RSX_ERR_ARG: a null actor, critic, parameter array, in, cfg, out or required array; n_rows < 1, n_batch_rows < 1 or either above
+ * 2^31 - 1; n_critics outside {1, 2}; gamma outside [0, 1]; sigma or noise_clip negative or non-finite; max_workgroups < 0; a spec
+ * outside rsx_policy_mlp's listed values (the actor's out_act neither tanh nor clip, the critic's not RSX_ACT_NONE); act_dim > 8; a
+ * handle without a task; the scrimmage task; a shape whose launches do not fit a CU's LDS. */
+typedef struct rsx_dpg_in {
+    const float*   obs;           /* [N][obs_dim]   required */
+    const float*   action;        /* [N][act_dim]   the executed action   required */
+    const float*   reward;        /* [N]            required */
+    const float*   next_obs;      /* [N][obs_dim]   the row's true successor   required */
+    const uint8_t* terminated;    /* [N] non-zero = true   required */
+    const int32_t* rows;          /* [M] flat row indices, repeats allowed, or NULL = rows 0 .. M - 1 */
+    int64_t        n_batch_rows;  /* N */
+    int64_t        n_rows;        /* M */
+} rsx_dpg_in;
+typedef struct rsx_dpg_cfg {
+    const int64_t* noise_step_dev;  /* NULL: noise_step; else the device address of the step */
+    uint64_t       noise_seed;
+    int64_t        noise_step;
+    float          gamma;           /* in [0, 1] */
+    float          sigma;           /* >= 0; 0: no smoothing noise */
+    float          noise_clip;      /* >= 0 */
+    int32_t        n_critics;       /* 1 or 2 */
+    int32_t        max_workgroups;  /* 0 = the build's default; > 0 caps the grid */
+} rsx_dpg_cfg;
+typedef struct rsx_dpg_out {
+    float* grad_actor;    /* [Pa] or NULL: no actor launch */
+    float* grad_critics;  /* [C][Pc]   required */
+    float* stats;         /* [9]       required */
+    float* target;        /* [M] or NULL */
+    float* q;             /* [C][M] or NULL */
+    float* action;        /* [M][act_dim] or NULL */
+    float* target_noise;  /* [M][act_dim] or NULL */
+    void*  workspace;     /* rsx_dpg_gradient_workspace bytes   required */
+} rsx_dpg_out;
+int rsx_dpg_gradient_workspace(const rsx_sim* h, const rsx_policy_mlp* actor, const rsx_policy_mlp* critic, int n_critics,
+                               int64_t n_rows, int max_workgroups, int64_t* bytes_out);
+int rsx_task_dpg_gradient(rsx_sim* h, const rsx_policy_mlp* actor, const float* actor_params_dev, const float* target_actor_params_dev,
+                          const rsx_policy_mlp* critic, const float* critic_params_dev, const float* target_critic_params_dev,
+                          const rsx_dpg_in* in, const rsx_dpg_cfg* cfg, const rsx_dpg_out* out, void* stream);
+
 /* Debugging aid: number of non-finite floats in the state rows and, with a task attached, in the
  * observations, rewards and info rows.  Synchronises `stream`.  With RSX_DEBUG_FINITE=1 in the
  * environment every stepping call (rsx_step_dev, rsx_task_step, rsx_task_step_n, rsx_task_rollout, rsx_task_collect_policy)

@@ -56,6 +56,7 @@ SYMBOLS = (
     "rsx_critic_num_params", "rsx_task_advantages",
     "rsx_ppo_gradient_workspace", "rsx_task_ppo_gradient",
     "rsx_ppo_normalize", "rsx_ppo_permutation", "rsx_adam_step", "rsx_adam_mark", "rsx_ppo_update_workspace", "rsx_task_ppo_update",
+    "rsx_dpg_gradient_workspace", "rsx_task_dpg_gradient",
 )
 # activations of rsx_policy_mlp (include/rsx.h: RSX_ACT_*)
 ACT_RELU, ACT_TANH, ACT_CLIP = 0, 1, 2
@@ -137,6 +138,31 @@ class PpoOut(C.Structure):
 
 # the slots of rsx_ppo_out.stats, in order
 PPO_STATS = ("loss_pi", "loss_v", "entropy", "approx_kl", "clip_fraction", "ratio", "rows_used", "rows_skipped")
+
+
+class DpgIn(C.Structure):
+    """rsx_dpg_in (include/rsx.h): the N flat transition rows rsx_task_dpg_gradient reads and the minibatch's rows; device addresses,
+    rows may be None (rows 0 .. M - 1)"""
+    _fields_ = [("obs", C.c_void_p), ("action", C.c_void_p), ("reward", C.c_void_p), ("next_obs", C.c_void_p), ("terminated", C.c_void_p),
+                ("rows", C.c_void_p), ("n_batch_rows", C.c_int64), ("n_rows", C.c_int64)]
+
+
+class DpgCfg(C.Structure):
+    """rsx_dpg_cfg (include/rsx.h): the smoothing noise's step (by value or as a device address), seed, sigma and clip, gamma, the number
+    of critics and the cap of the grid (0 = the build's default)"""
+    _fields_ = [("noise_step_dev", C.c_void_p), ("noise_seed", C.c_uint64), ("noise_step", C.c_int64), ("gamma", C.c_float),
+                ("sigma", C.c_float), ("noise_clip", C.c_float), ("n_critics", C.c_int32), ("max_workgroups", C.c_int32)]
+
+
+class DpgOut(C.Structure):
+    """rsx_dpg_out (include/rsx.h): the gradients (grad_actor None: no actor launch), the stats [9], the optional per-entry outputs and
+    the workspace; device addresses"""
+    _fields_ = [("grad_actor", C.c_void_p), ("grad_critics", C.c_void_p), ("stats", C.c_void_p), ("target", C.c_void_p), ("q", C.c_void_p),
+                ("action", C.c_void_p), ("target_noise", C.c_void_p), ("workspace", C.c_void_p)]
+
+
+# the slots of rsx_dpg_out.stats, in order
+DPG_STATS = ("loss_q0", "loss_q1", "q0", "q1", "loss_pi", "target", "abs_next_action", "rows_used", "rows_skipped")
 
 
 # the update phase (include/rsx.h: rsx_ppo_normalize, rsx_adam_step, rsx_task_ppo_update)
@@ -292,6 +318,9 @@ def load():
                                              C.POINTER(C.c_int64)]
     lib.rsx_task_ppo_update.argtypes = [vp, C.POINTER(PolicyMLP), vp, vp, C.POINTER(PolicyMLP), vp, C.POINTER(PpoIn), C.POINTER(PpoCfg),
                                         C.POINTER(PpoUpdateCfg), C.POINTER(AdamCfg), C.POINTER(AdamState), vp, vp, vp]
+    lib.rsx_dpg_gradient_workspace.argtypes = [vp, C.POINTER(PolicyMLP), C.POINTER(PolicyMLP), ip, C.c_int64, ip, C.POINTER(C.c_int64)]
+    lib.rsx_task_dpg_gradient.argtypes = [vp, C.POINTER(PolicyMLP), vp, vp, C.POINTER(PolicyMLP), vp, vp, C.POINTER(DpgIn), C.POINTER(DpgCfg),
+                                          C.POINTER(DpgOut), vp]
     lib.rsx_physics_defaults.argtypes = [ip, vp]
     lib.rsx_physics_derive.argtypes = [ip, ip, vp, vp]
     lib.rsx_physics_enable.argtypes = [vp, vp]
@@ -760,6 +789,24 @@ class Sim:
         b = lambda x: None if x is None else C.byref(x)   # noqa: E731
         rc = self._lib.rsx_task_ppo_update(self._h, b(actor), actor_params_ptr, log_std_ptr, b(critic), critic_params_ptr, b(inp), b(cfg),
                                            b(ucfg), b(adam), b(state), stats_ptr, workspace_ptr, stream)
+        if rc:
+            _chk(rc)
+
+    def dpg_gradient_workspace(self, actor, critic, n_critics, n_rows, max_workgroups=0):
+        """rsx_dpg_gradient_workspace: bytes of scratch rsx_task_dpg_gradient needs for a minibatch of ``n_rows`` rows"""
+        n = C.c_int64(0)
+        _chk(self._lib.rsx_dpg_gradient_workspace(self._h, None if actor is None else C.byref(actor), None if critic is None else C.byref(critic),
+                                                  int(n_critics), int(n_rows), int(max_workgroups), C.byref(n)))
+        return int(n.value)
+
+    def task_dpg_gradient(self, actor, actor_params_ptr, target_actor_params_ptr, critic, critic_params_ptr, target_critic_params_ptr, inp,
+                          cfg, out, stream=None):
+        """rsx_task_dpg_gradient: gradients of the TD3 / DDPG losses with respect to the actor's and the critics' parameters on a
+        minibatch of replayed transitions, in four launches.  ``actor`` / ``critic``: PolicyMLP specs, ``inp``: a DpgIn, ``cfg``: a
+        DpgCfg, ``out``: a DpgOut of device addresses (None passes NULL).  Reads and writes nothing of the envs."""
+        b = lambda x: None if x is None else C.byref(x)   # noqa: E731
+        rc = self._lib.rsx_task_dpg_gradient(self._h, b(actor), actor_params_ptr, target_actor_params_ptr, b(critic), critic_params_ptr,
+                                             target_critic_params_ptr, b(inp), b(cfg), b(out), stream)
         if rc:
             _chk(rc)
 

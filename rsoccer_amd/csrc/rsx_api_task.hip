@@ -603,6 +603,68 @@ int rsx_task_ppo_gradient(rsx_sim* h, const rsx_policy_mlp* actor, const float* 
     return RSX_OK;
 }
 
+// ---- TD3 / DDPG loss gradients of an actor and its Q critics on a minibatch (rsx.h: rsx_task_dpg_gradient).  The handle as above ----
+// what both calls check of the networks; on success the specs as the kernels take them and the floats of one network of each kind
+static int dpg_prologue(const rsx_sim* h, const rsx_policy_mlp* actor, const rsx_policy_mlp* critic, int n_critics, PolicySpec* SA,
+                        int64_t* n_actor, PolicySpec* SC, int64_t* n_critic) {
+    if (h->P.task == RSX_TASK_NONE) return fail(RSX_ERR_ARG, "no task attached (rsx_task_attach): obs_dim and act_dim are the task's");
+    if (int rc = policy_prologue(h, actor, SA, n_actor)) return rc;
+    if (int rc = critic_prologue(h, critic, SC, n_critic)) return rc;
+    if (n_critics != 1 && n_critics != 2) return fail(RSX_ERR_ARG, "n_critics must be 1 or 2");
+    const int OD = h->P.obs_dim, AD = h->M.act_dim;
+    if (AD > 8) return fail(RSX_ERR_ARG, "act_dim above 8 is not supported");
+    const int64_t H = critic->hidden;
+    *n_critic = H * (OD + AD) + H + (critic->n_hidden_layers == 2 ? H * H + H : 0) + H + 1;   // (the input row is [obs | action])
+    static const char* const names[3] = {"target", "critic", "actor"};
+    for (int l = 0; l < 3; ++l) {
+        const long long bytes = dpg_lds_bytes(l, OD, AD, *SA, *SC, n_critics);
+        if (bytes > 163840ll) {
+            char msg[200];
+            std::snprintf(msg, sizeof msg, "the %s launch needs %lld bytes of LDS per workgroup, a CU has 163840: use fewer or smaller hidden layers",
+                          names[l], bytes);
+            return fail(RSX_ERR_ARG, msg);
+        }
+    }
+    return RSX_OK;
+}
+
+int rsx_dpg_gradient_workspace(const rsx_sim* h, const rsx_policy_mlp* actor, const rsx_policy_mlp* critic, int n_critics, int64_t n_rows,
+                               int max_workgroups, int64_t* bytes_out) {
+    if (!h) return fail(RSX_ERR_ARG, "null handle");
+    if (!bytes_out) return fail(RSX_ERR_ARG, "bytes_out must not be null");
+    PolicySpec SA, SC; int64_t na = 0, nc = 0;
+    if (int rc = dpg_prologue(h, actor, critic, n_critics, &SA, &na, &SC, &nc)) return rc;
+    if (n_rows < 1 || n_rows > 0x7FFFFFFFll) return fail(RSX_ERR_ARG, "n_rows must be in 1 .. 2^31 - 1");
+    if (max_workgroups < 0) return fail(RSX_ERR_ARG, "max_workgroups must be >= 0");
+    *bytes_out = dpg_workspace_bytes(na, nc, n_critics, n_rows, max_workgroups);
+    return RSX_OK;
+}
+
+int rsx_task_dpg_gradient(rsx_sim* h, const rsx_policy_mlp* actor, const float* actor_params_dev, const float* target_actor_params_dev,
+                          const rsx_policy_mlp* critic, const float* critic_params_dev, const float* target_critic_params_dev,
+                          const rsx_dpg_in* in, const rsx_dpg_cfg* cfg, const rsx_dpg_out* out, void* stream) {
+    RSX_ENTER(h);   // (nothing the handle owns is read or written by the launches)
+    if (!cfg) return fail(RSX_ERR_ARG, "cfg must not be null");
+    PolicySpec SA, SC; int64_t na = 0, nc = 0;
+    if (int rc = dpg_prologue(h, actor, critic, cfg->n_critics, &SA, &na, &SC, &nc)) return rc;
+    if (!actor_params_dev || !target_actor_params_dev || !critic_params_dev || !target_critic_params_dev)
+        return fail(RSX_ERR_ARG, "actor_params_dev, target_actor_params_dev, critic_params_dev and target_critic_params_dev must not be null");
+    if (!in || !in->obs || !in->action || !in->reward || !in->next_obs || !in->terminated)
+        return fail(RSX_ERR_ARG, "in and its obs, action, reward, next_obs and terminated arrays must not be null");
+    if (in->n_rows < 1 || in->n_batch_rows < 1 || in->n_rows > 0x7FFFFFFFll || in->n_batch_rows > 0x7FFFFFFFll)
+        return fail(RSX_ERR_ARG, "n_rows and n_batch_rows must be in 1 .. 2^31 - 1");
+    if (!(std::isfinite(cfg->gamma) && cfg->gamma >= 0.0f && cfg->gamma <= 1.0f)) return fail(RSX_ERR_ARG, "gamma must be in [0, 1]");
+    if (!(std::isfinite(cfg->sigma) && cfg->sigma >= 0.0f)) return fail(RSX_ERR_ARG, "sigma must be finite and >= 0");
+    if (!(std::isfinite(cfg->noise_clip) && cfg->noise_clip >= 0.0f)) return fail(RSX_ERR_ARG, "noise_clip must be finite and >= 0");
+    if (cfg->max_workgroups < 0) return fail(RSX_ERR_ARG, "max_workgroups must be >= 0");
+    if (!out || !out->grad_critics || !out->stats || !out->workspace)
+        return fail(RSX_ERR_ARG, "out and its grad_critics, stats and workspace must not be null");
+    launch_dpg_gradient(SA, na, actor_params_dev, target_actor_params_dev, SC, nc, critic_params_dev, target_critic_params_dev, h->P.obs_dim,
+                        h->M.act_dim, *in, *cfg, *out, (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
 // ---- the update phase around it (rsx.h: rsx_ppo_normalize, rsx_ppo_permutation, rsx_adam_step, rsx_adam_mark, rsx_task_ppo_update) ----
 // what rsx_adam_step and rsx_task_ppo_update check of an optimiser's configuration and state
 static int adam_prologue(const rsx_adam_cfg* c, const rsx_adam_state* st) {

@@ -15,6 +15,9 @@ struct rsx_ppo_in;
 struct rsx_ppo_cfg;
 struct rsx_ppo_out;
 struct rsx_ppo_update_cfg;
+struct rsx_dpg_in;
+struct rsx_dpg_cfg;
+struct rsx_dpg_out;
 struct rsx_adam_cfg;
 struct rsx_adam_state;
 struct rsx_adam_io;
@@ -160,6 +163,20 @@ void launch_ppo_update(const PolicySpec& actor, long long n_params_actor, float*
                        long long n_params_critic, float* critic_params, int obs_dim, int act_dim, const rsx_ppo_in& in,
                        const rsx_ppo_cfg& cfg, const rsx_ppo_update_cfg& u, const rsx_adam_cfg& adam, const rsx_adam_state& st, float* stats,
                        void* workspace, hipStream_t s);
+// rsx_dpg.hip: gradients of the TD3 / DDPG losses with respect to an MLP actor and n_critics critics on [obs | action]
+// (rsx_task_dpg_gradient).  actor / critic: rsx_policy_mlp, checked; n_params_*: the floats of one network; *_params: the live and the
+// target parameters (critics: [n_critics][n_params_critic]); in / cfg / out: the call's structs, checked.  Four launches: the targets,
+// the critics (grid.y = critic), the actor through critic 0 (skipped without out.grad_actor), the reduce.  dpg_grid: workgroups of a row
+// launch (min(ceil(n_rows / 64), max_workgroups or the build's default)); dpg_workspace_bytes: the targets and one partial per workgroup
+// and network; dpg_lds_bytes: LDS of one workgroup of row launch `launch` (the host refuses more than a CU's 160 KB; beyond 64 KB the
+// launch raises the kernel's limit itself)
+enum : int { DPG_LAUNCH_TARGET = 0, DPG_LAUNCH_CRITIC = 1, DPG_LAUNCH_ACTOR = 2 };
+int dpg_grid(long long n_rows, int max_workgroups);
+long long dpg_lds_bytes(int launch, int obs_dim, int act_dim, const PolicySpec& actor, const PolicySpec& critic, int n_critics);
+long long dpg_workspace_bytes(long long n_params_actor, long long n_params_critic, int n_critics, long long n_rows, int max_workgroups);
+void launch_dpg_gradient(const PolicySpec& actor, long long n_params_actor, const float* actor_params, const float* target_actor_params,
+                         const PolicySpec& critic, long long n_params_critic, const float* critic_params, const float* target_critic_params,
+                         int obs_dim, int act_dim, const rsx_dpg_in& in, const rsx_dpg_cfg& cfg, const rsx_dpg_out& out, hipStream_t s);
 // rsx_render.hip: batched rgb frames (rsx_render_*).  render_check_view: nullptr when the view is valid (and the frame size), else the
 // message; render_field_host: the static field image [H][W][3]; RenderGeom: what the kernel needs of a view, in float32
 struct RenderGeom { int W, H; float s, cx, cy, r, rb; int square; };

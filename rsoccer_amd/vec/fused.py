@@ -766,6 +766,139 @@ class VecFusedEnv(RenderMixin):
             res["mean"], res["value"] = mean, val
         return res
 
+    # ---- off-policy updates (include/rsx.h: rsx_task_dpg_gradient) ----
+    def dpg_gradient(self, data, policy, params, target_params, critic, critic_params, target_critic_params, rows=None, gamma=0.99,
+                     target_noise=0.0, noise_clip=0.5, noise_seed=0, noise_step=0, actor=True, max_workgroups=None, return_rows=False):
+        """Gradients of the TD3 / DDPG losses with respect to an MLP actor and its one or two Q critics on a minibatch of replayed
+        transitions, in four launches (``rsx_task_dpg_gradient``): what an off-policy loop does per gradient step before
+        ``opt.step()`` and the Polyak update.
+
+        ``data``: a mapping of flat transition rows — ``ReplayBuffer.data()`` or any tensors ``obs`` ``[N, obs_dim]``, ``actions``
+        ``[N, act_dim]``, ``reward`` ``[N]``, ``next_obs`` ``[N, obs_dim]`` (float32) and ``terminated`` ``[N]`` (bool / uint8) on the
+        env's device, contiguous (anything else is a ``ValueError`` naming the offender).  ``policy`` / ``params`` ``[P]`` /
+        ``target_params`` ``[P]``: an ``MLPPolicy`` and its live and target parameters.  ``critic``: an ``MLPQCritic``;
+        ``critic_params`` and ``target_critic_params`` ``[C, Pc]`` with ``C`` in (1, 2).  ``rows``: as for ``ppo_gradient``.
+
+        ``target_noise`` (sigma) and ``noise_clip``: TD3's target policy smoothing; 0 draws nothing (DDPG).  The draw of minibatch
+        position ``t`` depends on ``(noise_seed, noise_step, t)`` only; ``noise_step`` may be an int64 device tensor ``[1]``, read when
+        the launch runs, so a replayed graph draws fresh noise once the tensor was advanced.  ``actor=False`` skips the actor launch
+        (TD3's delayed policy update); every other output keeps its bits.  The losses and their float32 arithmetic are written out in
+        ``include/rsx.h``; the result bits depend on the inputs and ``max_workgroups`` only.
+
+        Returns fresh device tensors ``grad_params`` ``[P]`` (absent with ``actor=False``), ``grad_critic_params`` ``[C, Pc]`` and
+        ``stats``: a dict of 0-d views (``_lib.DPG_STATS``; ``loss_pi`` absent with ``actor=False``; no synchronisation); with
+        ``return_rows=True`` also ``target`` ``[M]``, ``q`` ``[C, M]``, ``target_noise`` ``[M, act_dim]`` and, with the actor,
+        ``action`` ``[M, act_dim]``.  Touches nothing of the env, never synchronises, capturable."""
+        torch = self._torch
+        from rsoccer_amd.vec.policy import MLPCritic, MLPPolicy, MLPQCritic
+        if not isinstance(policy, MLPPolicy) or isinstance(policy, (MLPCritic, MLPQCritic)):
+            raise ValueError("policy must be an rsoccer_amd.vec.policy.MLPPolicy")
+        if not isinstance(critic, MLPQCritic):
+            raise ValueError("critic must be an rsoccer_amd.vec.policy.MLPQCritic")
+        OD, AD, dev = self.sim.obs_dim, self.sim.act_dim, self.device
+        if policy.obs_dim != OD or policy.act_dim != AD:
+            raise ValueError(f"the policy maps {policy.obs_dim} -> {policy.act_dim}, the env {OD} -> {AD}")
+        if critic.state_dim != OD or critic.action_dim != AD:
+            raise ValueError(f"the critic reads ({critic.state_dim}, {critic.action_dim}) floats, the env has ({OD}, {AD})")
+        gamma, sigma, noise_clip = float(gamma), float(target_noise), float(noise_clip)
+        if not (np.isfinite(gamma) and 0.0 <= gamma <= 1.0):
+            raise ValueError(f"gamma must be in [0, 1], got {gamma}")
+        for name, v in (("target_noise", sigma), ("noise_clip", noise_clip)):
+            if not (np.isfinite(v) and v >= 0.0):
+                raise ValueError(f"{name} must be finite and >= 0, got {v}")
+        mw = 0 if max_workgroups is None else int(max_workgroups)
+        if mw < 0 or (max_workgroups is not None and mw < 1):
+            raise ValueError(f"max_workgroups must be >= 1 or None, got {max_workgroups}")
+
+        def need(name, t, shape, dtypes=(torch.float32,)):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
+            if tuple(t.shape) != tuple(shape):
+                raise ValueError(f"{name} must be {list(shape)}, got {list(t.shape)}")
+            if t.dtype not in dtypes:
+                raise ValueError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+            if t.device != dev:
+                raise ValueError(f"{name} is on {t.device}, the env on {dev}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+            return t.detach()
+
+        for key in ("obs", "actions", "reward", "next_obs", "terminated"):
+            if key not in data:
+                raise ValueError(f"data lacks {key!r}")
+        obs = data["obs"]
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or obs.shape[0] < 1 or obs.shape[1] != OD:
+            raise ValueError(f"data['obs'] must be a [N >= 1, {OD}] tensor, got {tuple(np.shape(obs))}")
+        N = int(obs.shape[0])
+        obs = need("data['obs']", obs, (N, OD))
+        act = need("data['actions']", data["actions"], (N, AD))
+        rew = need("data['reward']", data["reward"], (N,))
+        nxt = need("data['next_obs']", data["next_obs"], (N, OD))
+        term = need("data['terminated']", data["terminated"], (N,), (torch.bool, torch.uint8))
+        p = need("params", params, (policy.num_params,))
+        tp = need("target_params", target_params, (policy.num_params,))
+        if not isinstance(critic_params, torch.Tensor) or critic_params.dim() != 2 or critic_params.shape[0] not in (1, 2):
+            raise ValueError(f"critic_params must be a [C, {critic.num_params}] tensor with C in (1, 2), got {tuple(np.shape(critic_params))}")
+        C = int(critic_params.shape[0])
+        cp = need("critic_params", critic_params, (C, critic.num_params))
+        tcp = need("target_critic_params", target_critic_params, (C, critic.num_params))
+        step_ptr, step = None, 0
+        if isinstance(noise_step, torch.Tensor):
+            step_t = need("noise_step", noise_step, (1,), (torch.int64,))
+            step_ptr = step_t.data_ptr()
+        else:
+            step_t, step = None, int(noise_step)
+        if rows is None:
+            r, M = None, N
+        else:
+            if not isinstance(rows, torch.Tensor) or not rows.is_cuda:   # host data: checked, then uploaded
+                host = np.asarray(rows.numpy() if isinstance(rows, torch.Tensor) else rows)
+                if host.ndim != 1 or host.size < 1 or host.dtype.kind not in "iu":
+                    raise ValueError(f"rows must be a 1-D integer array with at least one entry, got shape {host.shape} dtype {host.dtype}")
+                if int(host.min()) < 0 or int(host.max()) >= N:
+                    raise ValueError(f"rows must lie in [0, {N}), got {int(host.min())} .. {int(host.max())}")
+                rows = torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32)).to(dev)
+            if rows.dim() != 1 or rows.shape[0] < 1:
+                raise ValueError(f"rows must be 1-D with at least one entry, got {list(rows.shape)}")
+            if rows.dtype not in (torch.int32, torch.int64):
+                raise ValueError(f"rows must be torch.int32 or torch.int64, got {rows.dtype}")
+            if rows.device != dev:
+                raise ValueError(f"rows is on {rows.device}, the env on {dev}")
+            r = rows.to(torch.int32) if rows.dtype == torch.int64 else rows
+            if not r.is_contiguous():
+                raise ValueError("rows must be contiguous")
+            M = int(r.shape[0])
+        aspec, cspec = policy.spec(), critic.spec()
+        f32 = dict(dtype=torch.float32, device=dev)
+        # the workspace, cached per (shape, C, M, max_workgroups): calls on one stream are ordered, so they may share it
+        key = (policy.layers, policy.hidden, critic.layers, critic.hidden, C, M, mw)
+        cache = self.__dict__.setdefault("_dpg_ws", {})
+        ws = cache.get(key)
+        if ws is None:
+            ws = cache[key] = torch.empty(((self.sim.dpg_gradient_workspace(aspec, cspec, C, M, mw) + 3) // 4,), **f32)
+        ga = torch.empty((policy.num_params,), **f32) if actor else None
+        gc = torch.empty((C, critic.num_params), **f32)
+        stats = torch.empty((len(_lib.DPG_STATS),), **f32)
+        tgt = torch.empty((M,), **f32) if return_rows else None
+        q = torch.empty((C, M), **f32) if return_rows else None
+        pi = torch.empty((M, AD), **f32) if return_rows and actor else None
+        nz = torch.empty((M, AD), **f32) if return_rows else None
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731  (a bool tensor is one byte per element, 0 or 1)
+        inp = _lib.DpgIn(ptr(obs), ptr(act), ptr(rew), ptr(nxt), ptr(term), ptr(r), N, M)
+        cfg = _lib.DpgCfg(step_ptr, int(noise_seed) & 0xFFFFFFFFFFFFFFFF, step, gamma, sigma, noise_clip, C, mw)
+        out = _lib.DpgOut(ptr(ga), ptr(gc), ptr(stats), ptr(tgt), ptr(q), ptr(pi), ptr(nz), ptr(ws))
+        self.sim.task_dpg_gradient(aspec, ptr(p), ptr(tp), cspec, ptr(cp), ptr(tcp), inp, cfg, out, self._stream())
+        self._keep_dpg = (r, step_t, term)   # the call's own tensors: alive until the launches have consumed them
+        res = {"grad_critic_params": gc,
+               "stats": {name: stats[k] for k, name in enumerate(_lib.DPG_STATS) if actor or name != "loss_pi"}}
+        if actor:
+            res["grad_params"] = ga
+        if return_rows:
+            res["target"], res["q"], res["target_noise"] = tgt, q, nz
+            if actor:
+                res["action"] = pi
+        return res
+
     # ---- the update phase around ppo_gradient (include/rsx.h: rsx_ppo_normalize, rsx_ppo_permutation, rsx_task_ppo_update) ----
     def normalize_advantages(self, adv, eps=1e-8, return_moments=False):
         """``(adv - adv.mean()) / (adv.std() + eps)`` over all entries of a float32 device tensor (any shape, at least two entries,

@@ -125,6 +125,38 @@ class MLPCritic(MLPPolicy):
         return hid, (lambda v: v)
 
 
+class MLPQCritic(MLPPolicy):
+    """``obs_dim + act_dim -> hidden [-> hidden] -> 1`` with a linear output: the action-value critic ``VecFusedEnv.dpg_gradient``
+    differentiates (``rsx_task_dpg_gradient``).  ``MLPCritic``'s layout with input width ``obs_dim + act_dim``, the observation
+    columns first: the flat parameters equal ``parameters_to_vector`` of ``Sequential(Linear(obs_dim + act_dim, hidden), act,
+    [Linear(hidden, hidden), act,] Linear(hidden, 1))``.  Several critics of one shape (TD3's twins) form a ``[C, P]`` tensor."""
+
+    def __init__(self, obs_dim, act_dim, hidden=64, layers=2, hidden_act="tanh"):
+        if int(obs_dim) < 1 or int(act_dim) < 1:
+            raise ValueError(f"obs_dim and act_dim must be >= 1, got {obs_dim}, {act_dim}")
+        super().__init__(int(obs_dim) + int(act_dim), 1, hidden=hidden, layers=layers, hidden_act=hidden_act, out_act="tanh")
+        self.out_act = "none"
+        self.state_dim, self.action_dim = int(obs_dim), int(act_dim)   # (obs_dim is the input width, as the layout has it)
+
+    def spec(self):
+        """the rsx_policy_mlp of this shape, with out_act = RSX_ACT_NONE"""
+        return _lib.PolicyMLP(self.layers, self.hidden, _HIDDEN_ACTS[self.hidden_act], _lib.ACT_NONE)
+
+    def _torch_acts(self):
+        hid, _ = super()._torch_acts()
+        return hid, (lambda v: v)
+
+    def forward(self, obs, action, params, dtype=None):
+        """``Q(obs, action)``: ``obs [..., obs_dim]`` and ``action [..., act_dim]`` are concatenated along the last axis; returns
+        ``[..., 1]``, like the module.  ``params [P]`` or ``[..., P]`` as for ``MLPPolicy.forward``."""
+        import torch
+        dtype = torch.float64 if dtype is None else dtype
+        obs, action = torch.as_tensor(obs).to(dtype), torch.as_tensor(action).to(dtype)
+        if obs.shape[-1] != self.state_dim or action.shape[-1] != self.action_dim:
+            raise ValueError(f"expected obs [..., {self.state_dim}] and action [..., {self.action_dim}], got {list(obs.shape)} and {list(action.shape)}")
+        return super().forward(torch.cat([obs, action.to(obs.device)], dim=-1), params, dtype=dtype)
+
+
 _SEAT_KEYS = ("obs", "actions", "mean", "sample", "log_prob", "final_obs", "value", "advantage", "return")
 
 
