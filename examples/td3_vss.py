@@ -1,6 +1,7 @@
 """TD3 / DDPG on VSS-v0 with the rollouts collected in one launch and the gradients of a replayed minibatch computed by the engine.
 
     python examples/td3_vss.py [--envs 256] [--steps 16] [--updates 10] [--grad-steps 8] [--batch 256] [--ddpg] [--torch]
+                               [--device-update] [--graph]
 
 One update: env.collect(...) advances the envs `steps` steps under the current actor with Gaussian exploration noise of standard
 deviation --exploration (the engine clips the noisy sample: that is the executed action), ReplayBuffer.add() stores the T * B transitions
@@ -8,7 +9,9 @@ with their true successors, and `grad-steps` gradient steps follow.  A gradient 
 the device, env.dpg_gradient(...) returns the gradients of the critic loss and — every --policy-delay-th step — of the actor loss in
 four launches, torch's Adam steps on the flat parameter vectors (the leaves), and lerp_ moves the targets.  --ddpg: one critic, no
 target smoothing, no delay.  --torch runs the same update with torch modules and autograd instead (torch_losses below: what
-tools/bench_dpg_grad.py times the engine against).  A demonstration of the call pattern, not a tuned trainer."""
+tools/bench_dpg_grad.py times the engine against).  --device-update replaces the whole gradient-step loop by ONE call, env.dpg_update
+with a DPGOptimizer (rows from the engine's generator, Adam and the Polyak step on the device); --graph captures collect + add +
+dpg_update once and replays them (device_update below).  A demonstration of the call pattern, not a tuned trainer."""
 import argparse
 import math
 import os
@@ -56,6 +59,55 @@ def torch_losses(actor, critics, target_actor, target_critics, data, idx, gamma,
     return loss_q, loss_pi
 
 
+def device_update(args, C, sigma, delay):
+    """--device-update: the loop body is collect, buf.add, env.dpg_update — rows drawn by the engine's generator, Adam and the Polyak
+    step on the device, no interpreter between the gradient steps.  --graph: those three calls captured once on a device-keyed env
+    and replayed; the optimiser's step count on the device keys every replay's rows and noise."""
+    from rsoccer_amd.vec.optim import DPGOptimizer
+    if args.grad_steps % delay:
+        raise SystemExit(f"--grad-steps ({args.grad_steps}) must be a multiple of --policy-delay ({delay})")
+    torch.manual_seed(args.seed)
+    env = VecVSSEnv(args.envs, device=0, seed=args.seed)
+    dev, OD, AD = env.device, env.sim.obs_dim, env.sim.act_dim
+    pol = MLPPolicy(OD, AD, hidden=64, layers=2, hidden_act="tanh", out_act="tanh")
+    qnet = MLPQCritic(OD, AD, hidden=64, layers=2, hidden_act="tanh")
+    p_actor = pol.from_module(mlp(OD, AD, True)).to(dev)
+    p_critics = torch.stack([qnet.from_module(mlp(OD + AD, 1, False)) for _ in range(C)]).to(dev)
+    t_actor, t_critics = p_actor.clone(), p_critics.clone()
+    opt = DPGOptimizer(pol, qnet, C, device=dev, lr_actor=args.lr, lr_critic=args.lr, tau=args.tau)
+    buf = ReplayBuffer(args.capacity, OD, AD, dev)
+    log_std = torch.full((AD,), math.log(args.exploration), device=dev)
+    env.reset()
+    if args.graph:
+        env.enable_graph_capture()
+
+    def iteration():
+        batch = env.collect(pol, p_actor, args.steps, log_std=log_std, noise_seed=args.seed + 2, return_final_obs=True)
+        buf.add(batch)
+        out = env.dpg_update(buf, pol, p_actor, t_actor, qnet, p_critics, t_critics, opt, grad_steps=args.grad_steps, batch_size=args.batch,
+                             policy_delay=delay, gamma=args.gamma, target_noise=sigma, noise_clip=args.noise_clip, seed=args.seed + 1)
+        return batch["reward"].mean(), out["stats"]
+
+    graph = None
+    for update in range(args.updates):
+        t0 = time.perf_counter()
+        if graph is not None:
+            graph.replay()
+        else:
+            reward, stats = iteration()   # (eager; with --graph also the warm-up before the capture)
+        torch.cuda.synchronize()
+        m, last = env.metrics(), stats[-1]
+        print(f"update {update}: mean reward / step {float(reward):+.5f}, episodes {m['episodes']}, goals for / against "
+              f"{m['goals_for']} / {m['goals_against']}, buffer {int(buf.fill)} rows, gradient steps {int(opt.steps)}, loss_q "
+              f"{float(last[0] + last[1]):.5f}, loss_pi {float(last[4]):+.5f}; collect + add + {args.grad_steps} gradient steps "
+              f"{(time.perf_counter() - t0) * 1e3:.1f} ms")
+        if args.graph and graph is None:   # captured once (a capture records, it runs nothing): every further update is one replay
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                reward, stats = iteration()
+    env.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=256)
@@ -74,8 +126,14 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--ddpg", action="store_true", help="one critic, no target smoothing, no delay")
     ap.add_argument("--torch", action="store_true", help="the same update in torch autograd")
+    ap.add_argument("--device-update", action="store_true", help="the whole update phase in one call: env.dpg_update with a DPGOptimizer")
+    ap.add_argument("--graph", action="store_true", help="--device-update with collect + add + dpg_update captured once and replayed")
     args = ap.parse_args()
     C, sigma, delay = (1, 0.0, 1) if args.ddpg else (2, args.target_noise, args.policy_delay)
+    if args.device_update or args.graph:
+        if args.torch:
+            ap.error("--device-update / --graph and --torch exclude each other")
+        return device_update(args, C, sigma, delay)
 
     torch.manual_seed(args.seed)
     env = VecVSSEnv(args.envs, device=0, seed=args.seed)

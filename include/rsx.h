@@ -1020,6 +1020,126 @@ int rsx_task_dpg_gradient(rsx_sim* h, const rsx_policy_mlp* actor, const float* 
                           const rsx_policy_mlp* critic, const float* critic_params_dev, const float* target_critic_params_dev,
                           const rsx_dpg_in* in, const rsx_dpg_cfg* cfg, const rsx_dpg_out* out, void* stream);
 
+/* ---- the TD3 / DDPG update phase on the device: sample, Adam, Polyak (additive extension of ABI 6) ---------------------------------
+ * What an off-policy trainer does around rsx_task_dpg_gradient, per gradient step: draw the minibatch's rows, clip and step the critics
+ * (and, every policy_delay-th step, the actor) with Adam, and move the targets — here stream-ordered and keyed by counters that live on
+ * the device, so that rsx_task_collect_policy + the ring's writes + rsx_task_dpg_update captured once is one whole off-policy iteration
+ * per replay.  rsx_replay_sample_rows and rsx_dpg_adam_step take no handle: they run on the thread's current device.  Every call is
+ * stream-ordered, never synchronises, never allocates and is capturable; invalid arguments are refused with RSX_ERR_ARG before anything
+ * is enqueued (rsx_last_error says why); no float atomics: the result bits are a function of the inputs (and, for rsx_task_dpg_update,
+ * of max_workgroups) alone.
+ *
+ * rsx_replay_sample_rows:  rows_dev [m] int32 := indices uniform over the first `fill` rows of a ring of n_batch_rows rows, with
+ * repeats, every entry computed on its own from (seed, step, t) — no generator state, no floating point.  One launch.
+ *   word     entry t takes word t & 3 of philox4x32-7(counter = (t >> 2, step >> 32, step & 0xFFFFFFFF, 11), key = (seed lo, seed hi));
+ *            11 is this draw's own domain word (1 and 3 .. 10 are the engine's other draws)
+ *   rows[t]  (uint32_t)(((uint64_t)word * (uint64_t)fill) >> 32): exact integer arithmetic.  Of the 2^32 words, floor(2^32 / fill) or
+ *            one more map to each index, so every index has a probability within 2^-32 of 1 / fill.  A draw depends on (seed, step, t)
+ *            and fill — not on m, the grid or the device.
+ *   fill     the argument, or, with fill_dev != NULL, the int64 it points to, read on the device when the launch runs (the ring's own
+ *            fill count); either is clamped to [0, n_batch_rows].  fill == 0 writes -1 to every entry: rsx_task_dpg_gradient skips
+ *            such an entry and counts it.
+ *   step     the argument, or, with step_dev != NULL, the int64 it points to, read on the device: pass
+ *            rsx_dpg_adam_state.counters + RSX_DPG_STEPS and a replayed graph draws new rows once the counter has advanced.
+ * Refused: a null rows_dev; m < 1 or m > 2^31 - 1; n_batch_rows < 1 or > 2^31 - 1; a negative `fill` argument (with fill_dev == NULL). */
+int rsx_replay_sample_rows(int32_t* rows_dev, int64_t m, int64_t n_batch_rows, int64_t fill, const int64_t* fill_dev, uint64_t seed,
+                           int64_t step, const int64_t* step_dev, void* stream);
+/* rsx_dpg_adam_step:  the optimiser step of TD3 — two torch.optim.Adam (no amsgrad, no weight decay), one on the critics' flat tensor
+ * [C * Pc] and one on the actor's [Pa], each behind its own torch.nn.utils.clip_grad_norm_, and the Polyak step of the two target
+ * tensors — in two launches (the norms, then the update).
+ *   counters   int64 [4] device memory, part of the optimiser state (zero at the start of training): */
+#define RSX_DPG_T_CRITIC 0   /* the critics' Adam step count t */
+#define RSX_DPG_T_ACTOR  1   /* the actor's: it advances on actor steps only, so its bias corrections are its own */
+#define RSX_DPG_STEPS    2   /* gradient steps finished (calls of rsx_dpg_adam_step): the key of the row draws and the smoothing noise */
+#define RSX_DPG_SPARE    3   /* not read, not written */
+/*   groups   the critics always step; the actor steps when io->grad_actor != NULL.  A call without grad_actor leaves the actor's
+ *          parameters, its moments and counters[RSX_DPG_T_ACTOR] exactly as they were.
+ *   per group, rsx_adam_step's arithmetic, word for word, on that group's tensor alone:
+ *     norm   = (float)sqrt(sum g^2), the float64 reduction in rsx_adam_step's fixed order (G = min(ceil(n / 256), 64) workgroups of the
+ *              GROUP's n; each g widened, g * g exact)
+ *     coef   = min(1, max_grad_norm / (norm + 1e-6f)) in float32;  max_grad_norm <= 0: coef = 1 (no clipping)
+ *     t := t + 1 (the group's own);  bc1 = 1 - beta1^t, bc2 = 1 - beta2^t in float64 from the device's t, beta^t by squaring
+ *     g' = g * coef;   m = b1 * m + omb1 * g';   v = b2 * v + (omb2 * g') * g';   p = p - step * (m / (sqrtf(v) / s2 + eps))
+ *              in float32, every operation rounded, with b = (float)beta, omb = (float)(1.0 - beta), step = (float)((double)lr / bc1),
+ *              s2 = (float)sqrt(bc2).  A gradient entry that is 0 while its m is 0 leaves its parameter as it was.
+ *     lr     the group's: lr_actor / lr_critic, or with the matching *_dev != NULL the float it points to, read on the device.
+ *   Polyak   with io->update_targets != 0, after the Adam step of the same call, on the NEW parameters, per entry of both target
+ *          tensors:  d = p - targ;  targ = targ + tau * d   in float32, each of the three operations rounded.  Without a grad_actor
+ *          the actor's target moves towards the unchanged actor.  With update_targets == 0 no target is read or written.
+ *   counters[RSX_DPG_STEPS] advances by one per call.
+ *   stats  [3] or NULL: the critics' norm before the clip; the actor's (0.0f without an actor step); 1.0f when the targets moved,
+ *          else 0.0f.
+ *   workspace   RSX_DPG_ADAM_WORKSPACE_BYTES, 8-byte aligned.
+ * Refused: a null cfg, st, io, counters, workspace, critic array (parameters, gradient, m, v) or actor array (parameters, m, v); a
+ * size < 1 or above 2^31 - 1; lr_actor, lr_critic or eps negative or non-finite; a beta outside [0, 1); max_grad_norm non-finite; tau
+ * outside [0, 1] or non-finite; update_targets != 0 with a null target. */
+#define RSX_DPG_ADAM_WORKSPACE_BYTES 2048
+typedef struct rsx_dpg_adam_cfg {
+    double       beta1;          /* in [0, 1) */
+    double       beta2;          /* in [0, 1) */
+    const float* lr_actor_dev;   /* [1] device memory, or NULL = lr_actor */
+    const float* lr_critic_dev;  /* [1] device memory, or NULL = lr_critic */
+    float        lr_actor;       /* >= 0, finite */
+    float        lr_critic;      /* >= 0, finite */
+    float        eps;            /* >= 0, finite */
+    float        max_grad_norm;  /* <= 0: no clipping; else the bound of EACH group's own norm */
+    float        tau;            /* in [0, 1] */
+} rsx_dpg_adam_cfg;
+typedef struct rsx_dpg_adam_state {
+    float*   m_actor;     /* [n_actor] */
+    float*   v_actor;
+    float*   m_critic;    /* [n_critic] */
+    float*   v_critic;
+    int64_t* counters;    /* [4], RSX_DPG_* */
+    int64_t  n_actor;     /* Pa */
+    int64_t  n_critic;    /* C * Pc */
+} rsx_dpg_adam_state;
+typedef struct rsx_dpg_adam_io {
+    float*       actor_params;          /* [n_actor]   updated in place on an actor step   required */
+    float*       target_actor_params;   /* [n_actor]   required with update_targets */
+    float*       critic_params;         /* [n_critic]  updated in place   required */
+    float*       target_critic_params;  /* [n_critic]  required with update_targets */
+    const float* grad_actor;            /* [n_actor] or NULL: no actor step */
+    const float* grad_critic;           /* [n_critic]  required */
+    float*       stats;                 /* [3] or NULL */
+    void*        workspace;             /* RSX_DPG_ADAM_WORKSPACE_BYTES   required */
+    int32_t      update_targets;        /* != 0: the Polyak step */
+} rsx_dpg_adam_io;
+int rsx_dpg_adam_step(const rsx_dpg_adam_cfg* cfg, const rsx_dpg_adam_state* st, const rsx_dpg_adam_io* io, void* stream);
+/* rsx_task_dpg_update:  the whole update phase in one call.  For j = 0 .. grad_steps - 1 it enqueues, in this order:
+ * rsx_replay_sample_rows(m = in->n_rows, n_batch_rows = in->n_batch_rows, fill / fill_dev = u's, seed = u->seed, step_dev = the DEVICE's
+ * counters[RSX_DPG_STEPS]) into the workspace;  rsx_task_dpg_gradient on those rows with noise_step_dev = the same counter
+ * (cfg->noise_step and cfg->noise_step_dev are ignored) and grad_actor only on an actor step;  rsx_dpg_adam_step with grad_actor and
+ * update_targets on an actor step only.  Step j is an actor step when (j + 1) % policy_delay == 0 — decided on the host from the index;
+ * grad_steps must be a multiple of policy_delay, so every call has the same launch sequence, a captured call replays exactly what
+ * an eager one does, and no launch is wasted.  policy_delay = 1, one critic and sigma = 0 is DDPG.  The results equal that sequence of
+ * calls bit for bit.
+ *   the handle, actor, critic, in, cfg    as for rsx_task_dpg_gradient; in->rows must be NULL, in->n_rows is the minibatch size m.
+ *   the four parameter tensors   updated in place.  Nothing `in` points to is written.
+ *   stats_dev   [grad_steps][RSX_DPG_UPDATE_STATS]: rsx_task_dpg_gradient's nine, then rsx_dpg_adam_step's three
+ *   workspace   rsx_dpg_update_workspace bytes, 16-byte aligned: rsx_task_dpg_gradient's for m rows, the rows, the two gradient tensors
+ *               and the optimiser's partials.  rows_offset_out (or NULL): where in it the int32 rows [m] of the last step lie.
+ *   an empty ring   with a device fill of 0 every row is -1 and skipped, every gradient is 0, and no PARAMETER moves (a zero gradient on
+ *               a zero moment leaves its parameter alone; with moments from earlier steps Adam goes on as torch's would); the counters
+ *               advance and the targets take their Polyak steps as always.
+ * Refused: everything rsx_replay_sample_rows, rsx_task_dpg_gradient and rsx_dpg_adam_step refuse; a null u, stats_dev or workspace; a
+ * non-NULL in->rows; grad_steps < 1; policy_delay < 1; grad_steps % policy_delay != 0; a negative u->fill with fill_dev == NULL; state
+ * sizes (st->n_actor, st->n_critic) that are not Pa and C * Pc. */
+#define RSX_DPG_UPDATE_STATS 12
+typedef struct rsx_dpg_update_cfg {
+    const int64_t* fill_dev;      /* the ring's fill count on the device, or NULL = fill */
+    uint64_t       seed;          /* the row draws' key */
+    int64_t        fill;          /* >= 0 */
+    int32_t        grad_steps;    /* >= 1, a multiple of policy_delay */
+    int32_t        policy_delay;  /* >= 1 */
+} rsx_dpg_update_cfg;
+int rsx_dpg_update_workspace(const rsx_sim* h, const rsx_policy_mlp* actor, const rsx_policy_mlp* critic, int n_critics, int64_t n_rows,
+                             int max_workgroups, int64_t* bytes_out, int64_t* rows_offset_out);
+int rsx_task_dpg_update(rsx_sim* h, const rsx_policy_mlp* actor, float* actor_params_dev, float* target_actor_params_dev,
+                        const rsx_policy_mlp* critic, float* critic_params_dev, float* target_critic_params_dev, const rsx_dpg_in* in,
+                        const rsx_dpg_cfg* cfg, const rsx_dpg_update_cfg* u, const rsx_dpg_adam_cfg* adam, const rsx_dpg_adam_state* st,
+                        float* stats_dev, void* workspace, void* stream);
+
 /* Debugging aid: number of non-finite floats in the state rows and, with a task attached, in the
  * observations, rewards and info rows.  Synchronises `stream`.  With RSX_DEBUG_FINITE=1 in the
  * environment every stepping call (rsx_step_dev, rsx_task_step, rsx_task_step_n, rsx_task_rollout, rsx_task_collect_policy)

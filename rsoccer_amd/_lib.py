@@ -57,6 +57,7 @@ SYMBOLS = (
     "rsx_ppo_gradient_workspace", "rsx_task_ppo_gradient",
     "rsx_ppo_normalize", "rsx_ppo_permutation", "rsx_adam_step", "rsx_adam_mark", "rsx_ppo_update_workspace", "rsx_task_ppo_update",
     "rsx_dpg_gradient_workspace", "rsx_task_dpg_gradient",
+    "rsx_replay_sample_rows", "rsx_dpg_adam_step", "rsx_dpg_update_workspace", "rsx_task_dpg_update",
 )
 # activations of rsx_policy_mlp (include/rsx.h: RSX_ACT_*)
 ACT_RELU, ACT_TANH, ACT_CLIP = 0, 1, 2
@@ -200,6 +201,42 @@ class PpoUpdateCfg(C.Structure):
                 ("norm_eps", C.c_float)]
 
 
+# the off-policy update phase (include/rsx.h: rsx_replay_sample_rows, rsx_dpg_adam_step, rsx_task_dpg_update)
+DPG_ADAM_WORKSPACE_BYTES = 2048
+# the slots of rsx_dpg_adam_state.counters (RSX_DPG_*), of rsx_dpg_adam_io.stats, and of one row of rsx_task_dpg_update's stats
+DPG_COUNTERS = ("t_critic", "t_actor", "steps", "spare")
+DPG_ADAM_STATS = ("grad_norm_critic", "grad_norm_actor", "targets_moved")
+DPG_UPDATE_STATS = DPG_STATS + DPG_ADAM_STATS
+
+
+class DpgAdamCfg(C.Structure):
+    """rsx_dpg_adam_cfg (include/rsx.h): the betas as doubles, each group's lr by value or as a device address (None = by value), eps,
+    the bound of each group's own gradient norm (<= 0: none) and the Polyak step's tau"""
+    _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("lr_actor_dev", C.c_void_p), ("lr_critic_dev", C.c_void_p),
+                ("lr_actor", C.c_float), ("lr_critic", C.c_float), ("eps", C.c_float), ("max_grad_norm", C.c_float), ("tau", C.c_float)]
+
+
+class DpgAdamState(C.Structure):
+    """rsx_dpg_adam_state (include/rsx.h): m and v of the actor's and the critics' flat tensors, the int64 counters [4] and the two
+    sizes; device addresses"""
+    _fields_ = [("m_actor", C.c_void_p), ("v_actor", C.c_void_p), ("m_critic", C.c_void_p), ("v_critic", C.c_void_p),
+                ("counters", C.c_void_p), ("n_actor", C.c_int64), ("n_critic", C.c_int64)]
+
+
+class DpgAdamIo(C.Structure):
+    """rsx_dpg_adam_io (include/rsx.h): the live and target tensors of both groups (updated in place), the gradients (grad_actor None:
+    no actor step), the optional stats [3], the workspace and whether the targets move; device addresses"""
+    _fields_ = [("actor_params", C.c_void_p), ("target_actor_params", C.c_void_p), ("critic_params", C.c_void_p),
+                ("target_critic_params", C.c_void_p), ("grad_actor", C.c_void_p), ("grad_critic", C.c_void_p), ("stats", C.c_void_p),
+                ("workspace", C.c_void_p), ("update_targets", C.c_int32)]
+
+
+class DpgUpdateCfg(C.Structure):
+    """rsx_dpg_update_cfg (include/rsx.h): the ring's fill count (by device address, or None and by value), the row draws' seed, the
+    gradient steps of the call and the actor's delay"""
+    _fields_ = [("fill_dev", C.c_void_p), ("seed", C.c_uint64), ("fill", C.c_int64), ("grad_steps", C.c_int32), ("policy_delay", C.c_int32)]
+
+
 class DevView(C.Structure):
     _fields_ = [("num_envs", C.c_int32), ("n_robots", C.c_int32), ("state_dim", C.c_int32),
                 ("cmd_dim", C.c_int32), ("state", C.c_void_p), ("cmds", C.c_void_p), ("row_stride", C.c_int32)]
@@ -321,6 +358,12 @@ def load():
     lib.rsx_dpg_gradient_workspace.argtypes = [vp, C.POINTER(PolicyMLP), C.POINTER(PolicyMLP), ip, C.c_int64, ip, C.POINTER(C.c_int64)]
     lib.rsx_task_dpg_gradient.argtypes = [vp, C.POINTER(PolicyMLP), vp, vp, C.POINTER(PolicyMLP), vp, vp, C.POINTER(DpgIn), C.POINTER(DpgCfg),
                                           C.POINTER(DpgOut), vp]
+    lib.rsx_replay_sample_rows.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, vp, C.c_uint64, C.c_int64, vp, vp]
+    lib.rsx_dpg_adam_step.argtypes = [C.POINTER(DpgAdamCfg), C.POINTER(DpgAdamState), C.POINTER(DpgAdamIo), vp]
+    lib.rsx_dpg_update_workspace.argtypes = [vp, C.POINTER(PolicyMLP), C.POINTER(PolicyMLP), ip, C.c_int64, ip, C.POINTER(C.c_int64),
+                                             C.POINTER(C.c_int64)]
+    lib.rsx_task_dpg_update.argtypes = [vp, C.POINTER(PolicyMLP), vp, vp, C.POINTER(PolicyMLP), vp, vp, C.POINTER(DpgIn), C.POINTER(DpgCfg),
+                                        C.POINTER(DpgUpdateCfg), C.POINTER(DpgAdamCfg), C.POINTER(DpgAdamState), vp, vp, vp]
     lib.rsx_physics_defaults.argtypes = [ip, vp]
     lib.rsx_physics_derive.argtypes = [ip, ip, vp, vp]
     lib.rsx_physics_enable.argtypes = [vp, vp]
@@ -384,6 +427,23 @@ def adam_step(cfg, state, io, stream=None):
 def adam_mark(state, end, stream=None):
     """rsx_adam_mark: an update begins (end = False: applied and stopped are cleared) or ends (the update count advances)"""
     rc = load().rsx_adam_mark(None if state is None else C.byref(state), 1 if end else 0, stream)
+    if rc:
+        _chk(rc)
+
+
+def replay_sample_rows(rows_ptr, m, n_batch_rows, fill, fill_ptr, seed, step, step_ptr, stream=None):
+    """rsx_replay_sample_rows: rows [m] int32 := indices uniform over the first fill rows (fill, or the int64 at fill_ptr), keyed by
+    (seed, step or the int64 at step_ptr); -1 everywhere on an empty ring"""
+    rc = load().rsx_replay_sample_rows(rows_ptr, int(m), int(n_batch_rows), int(fill), fill_ptr, int(seed) & ((1 << 64) - 1), int(step),
+                                       step_ptr, stream)
+    if rc:
+        _chk(rc)
+
+
+def dpg_adam_step(cfg, state, io, stream=None):
+    """rsx_dpg_adam_step: clip + Adam on the critics and (with a grad_actor) the actor, each group on its own, and the Polyak step"""
+    rc = load().rsx_dpg_adam_step(None if cfg is None else C.byref(cfg), None if state is None else C.byref(state),
+                                  None if io is None else C.byref(io), stream)
     if rc:
         _chk(rc)
 
@@ -807,6 +867,25 @@ class Sim:
         b = lambda x: None if x is None else C.byref(x)   # noqa: E731
         rc = self._lib.rsx_task_dpg_gradient(self._h, b(actor), actor_params_ptr, target_actor_params_ptr, b(critic), critic_params_ptr,
                                              target_critic_params_ptr, b(inp), b(cfg), b(out), stream)
+        if rc:
+            _chk(rc)
+
+    def dpg_update_workspace(self, actor, critic, n_critics, n_rows, max_workgroups=0):
+        """rsx_dpg_update_workspace: (bytes of scratch rsx_task_dpg_update needs, the offset of its int32 rows in it)"""
+        n, off = C.c_int64(0), C.c_int64(0)
+        _chk(self._lib.rsx_dpg_update_workspace(self._h, None if actor is None else C.byref(actor), None if critic is None else C.byref(critic),
+                                                int(n_critics), int(n_rows), int(max_workgroups), C.byref(n), C.byref(off)))
+        return int(n.value), int(off.value)
+
+    def task_dpg_update(self, actor, actor_params_ptr, target_actor_params_ptr, critic, critic_params_ptr, target_critic_params_ptr, inp,
+                        cfg, ucfg, adam, state, stats_ptr, workspace_ptr, stream=None):
+        """rsx_task_dpg_update: the whole update phase of TD3 / DDPG enqueued by one call — per gradient step the row draw, the
+        gradients and the clip + Adam + Polyak step; the four parameter tensors are updated in place.  Reads and writes nothing of
+        the envs."""
+        b = lambda x: None if x is None else C.byref(x)   # noqa: E731
+        rc = self._lib.rsx_task_dpg_update(self._h, b(actor), actor_params_ptr, target_actor_params_ptr, b(critic), critic_params_ptr,
+                                           target_critic_params_ptr, b(inp), b(cfg), b(ucfg), b(adam), b(state), stats_ptr, workspace_ptr,
+                                           stream)
         if rc:
             _chk(rc)
 

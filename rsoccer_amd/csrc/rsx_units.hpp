@@ -21,6 +21,10 @@ struct rsx_dpg_out;
 struct rsx_adam_cfg;
 struct rsx_adam_state;
 struct rsx_adam_io;
+struct rsx_dpg_update_cfg;
+struct rsx_dpg_adam_cfg;
+struct rsx_dpg_adam_state;
+struct rsx_dpg_adam_io;
 
 namespace rsx {
 
@@ -177,6 +181,19 @@ long long dpg_workspace_bytes(long long n_params_actor, long long n_params_criti
 void launch_dpg_gradient(const PolicySpec& actor, long long n_params_actor, const float* actor_params, const float* target_actor_params,
                          const PolicySpec& critic, long long n_params_critic, const float* critic_params, const float* target_critic_params,
                          int obs_dim, int act_dim, const rsx_dpg_in& in, const rsx_dpg_cfg& cfg, const rsx_dpg_out& out, hipStream_t s);
+// rsx_dpg_update.hip: the update phase around launch_dpg_gradient (rsx_replay_sample_rows, rsx_dpg_adam_step, rsx_task_dpg_update); every
+// argument checked by the caller.  One launch for the rows, two for the optimiser step (the norms of both groups, then Adam with the
+// Polyak step).  dpg_update_workspace_bytes: launch_dpg_update's workspace (rows_offset: where the int32 rows lie in it);
+// launch_dpg_update enqueues the whole phase and calls launch_dpg_gradient per gradient step
+void launch_replay_sample_rows(int32_t* rows, long long m, long long n_batch_rows, long long fill, const long long* fill_dev, uint64_t seed,
+                               long long step, const long long* step_dev, hipStream_t s);
+void launch_dpg_adam_step(const rsx_dpg_adam_cfg& c, const rsx_dpg_adam_state& st, const rsx_dpg_adam_io& io, hipStream_t s);
+long long dpg_update_workspace_bytes(long long n_params_actor, long long n_params_critic, int n_critics, long long n_rows,
+                                     int max_workgroups, long long* rows_offset);
+void launch_dpg_update(const PolicySpec& actor, long long n_params_actor, float* actor_params, float* target_actor_params,
+                       const PolicySpec& critic, long long n_params_critic, float* critic_params, float* target_critic_params, int obs_dim,
+                       int act_dim, const rsx_dpg_in& in, const rsx_dpg_cfg& cfg, const rsx_dpg_update_cfg& u, const rsx_dpg_adam_cfg& adam,
+                       const rsx_dpg_adam_state& st, float* stats, void* workspace, hipStream_t s);
 // rsx_render.hip: batched rgb frames (rsx_render_*).  render_check_view: nullptr when the view is valid (and the frame size), else the
 // message; render_field_host: the static field image [H][W][3]; RenderGeom: what the kernel needs of a view, in float32
 struct RenderGeom { int W, H; float s, cx, cy, r, rb; int square; };

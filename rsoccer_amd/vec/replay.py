@@ -73,6 +73,40 @@ class ReplayBuffer:
         u = torch.rand((m,), dtype=torch.float64, device=self.device, generator=generator)
         return torch.minimum((u * self.fill).to(torch.int64), self.fill - 1).to(torch.int32)
 
+    def sample_rows_device(self, m, seed=0, step=0):
+        """``m`` int32 row indices, uniform over the filled part with repeats, drawn by the engine's own counter-based generator in
+        one launch (``rsx_replay_sample_rows``; the integer arithmetic is written out in ``include/rsx.h``): entry ``t`` depends on
+        ``(seed, step, t)`` and the device's fill count only.  ``step``: an int, or an int64 device tensor ``[1]`` read when the launch
+        runs — ``DPGOptimizer.steps``, so that a replayed graph draws new rows after every gradient step.  On an empty buffer every
+        index is -1.  Needs the buffer on a GPU; never synchronises, capturable."""
+        import torch
+        from rsoccer_amd import _lib
+        m = int(m)
+        if m < 1 or m > 2 ** 31 - 1:
+            raise ValueError(f"m must be in 1 .. 2^31 - 1, got {m}")
+        if self.capacity > 2 ** 31 - 1:
+            raise ValueError(f"capacity must be at most 2^31 - 1, got {self.capacity}")
+        if self.device.type != "cuda":
+            raise ValueError(f"the buffer is on {self.device}: sample_rows_device needs it on a GPU (sample_rows works anywhere)")
+        step_ptr, step_v = None, 0
+        if isinstance(step, torch.Tensor):
+            if step.dtype != torch.int64 or tuple(step.shape) != (1,) or step.device != self.fill.device:
+                raise ValueError(f"step as a tensor must be int64 [1] on {self.fill.device}, got {step.dtype} {list(step.shape)} on {step.device}")
+            step_ptr = step.data_ptr()
+        else:
+            step_v = int(step)
+            if not -2 ** 63 <= step_v < 2 ** 63:
+                raise ValueError(f"step must fit 64 bits, got {step}")
+        rows = torch.empty((m,), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            try:
+                stream = torch._C._cuda_getCurrentRawStream(self.fill.device.index)
+            except AttributeError:
+                stream = torch.cuda.current_stream(self.device).cuda_stream
+            _lib.replay_sample_rows(rows.data_ptr(), m, self.capacity, 0, self.fill.data_ptr(), int(seed), step_v, step_ptr, stream)
+        self._keep_step = step   # alive until the launch has consumed it
+        return rows
+
     def data(self):
         """the mapping ``VecFusedEnv.dpg_gradient`` takes: views of the whole ring (``N = capacity``); rows behind the fill count
         hold zeros and are never drawn by ``sample_rows``"""
