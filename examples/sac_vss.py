@@ -1,0 +1,117 @@
+"""Soft actor-critic on VSS-v0 with the rollouts collected in one launch under the actor itself.
+
+    python examples/sac_vss.py [--envs 256] [--steps 16] [--updates 10] [--grad-steps 8] [--batch 256] [--torch]
+
+One update: env.collect(MLPGaussianPolicy, ...) advances the envs `steps` steps under the current actor — mean and log-std per state,
+the sample squashed by tanh, all inside the launch (rsx_task_collect_gaussian) — ReplayBuffer.add() stores the T * B transitions with
+their true successors, and `grad-steps` gradient steps follow.  A gradient step: ReplayBuffer.sample_rows() draws the minibatch on the
+device, env.sac_gradient(...) returns the gradients of the critic loss, the actor loss and the temperature loss in six launches
+(rsx_task_sac_gradient), three torch Adam optimisers step on the flat tensors (the leaves), and lerp_ moves the target critics.
+--torch runs the same losses in torch autograd instead (sac_losses below, on the same flat vectors: MLPGaussianPolicy.sample and
+MLPQCritic.forward are plain torch; what tools/bench_sac_grad.py times the engine against).  A demonstration of the call pattern, not a
+tuned trainer."""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from rsoccer_amd.vec import VecVSSEnv
+from rsoccer_amd.vec.policy import MLPGaussianPolicy, MLPQCritic
+from rsoccer_amd.vec.replay import ReplayBuffer
+
+
+def mlp(n_in, n_out):
+    return torch.nn.Sequential(torch.nn.Linear(n_in, 64), torch.nn.Tanh(), torch.nn.Linear(64, 64), torch.nn.Tanh(), torch.nn.Linear(64, n_out))
+
+
+def sac_losses(pol, p_actor, qnet, p_critics, t_critics, log_alpha, data, idx, gamma, target_entropy):
+    """(loss_q, loss_pi, loss_alpha, mean log_prob) on the flat parameters, float32; eps drawn by torch"""
+    f32 = torch.float32
+    obs, act, nxt = data["obs"][idx], data["actions"][idx], data["next_obs"][idx]
+    alpha = log_alpha.detach().exp()
+    q_all = lambda params, o, a: torch.stack([qnet.forward(o, a, p, dtype=f32).squeeze(-1) for p in params])   # noqa: E731  [C, M]
+    with torch.no_grad():
+        a2, logp2, _ = pol.sample(nxt, p_actor, torch.randn_like(act), dtype=f32)
+        r = data["reward"][idx]
+        y = torch.where(data["terminated"][idx], r, r + gamma * (q_all(t_critics, nxt, a2).min(0).values - alpha * logp2))
+    loss_q = (0.5 * (q_all(p_critics, obs, act) - y).pow(2).mean(-1)).sum()
+    a, logp, _ = pol.sample(obs, p_actor, torch.randn_like(act), dtype=f32)
+    loss_pi = (alpha * logp - q_all(p_critics.detach(), obs, a).min(0).values).mean()
+    loss_alpha = -(log_alpha * (logp.detach() + target_entropy).mean()).sum()
+    return loss_q, loss_pi, loss_alpha, logp.detach().mean()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=256)
+    ap.add_argument("--steps", type=int, default=16, help="T: steps per env and update")
+    ap.add_argument("--updates", type=int, default=10)
+    ap.add_argument("--grad-steps", type=int, default=8, help="gradient steps per update")
+    ap.add_argument("--batch", type=int, default=256, help="rows of a minibatch")
+    ap.add_argument("--capacity", type=int, default=1 << 18)
+    ap.add_argument("--lr", type=float, default=3e-4)
+    ap.add_argument("--gamma", type=float, default=0.99)
+    ap.add_argument("--tau", type=float, default=0.005)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--torch", action="store_true", help="the same losses in torch autograd")
+    args = ap.parse_args()
+
+    torch.manual_seed(args.seed)
+    env = VecVSSEnv(args.envs, device=0, seed=args.seed)
+    dev, OD, AD = env.device, env.sim.obs_dim, env.sim.act_dim
+    pol = MLPGaussianPolicy(OD, AD, hidden=64, layers=2, hidden_act="tanh")
+    qnet = MLPQCritic(OD, AD, hidden=64, layers=2, hidden_act="tanh")
+    # the flat vectors are the leaves: the engine reads them as they are, autograd differentiates them as they are
+    p_actor = torch.nn.Parameter(pol.from_module(mlp(OD, 2 * AD)).to(dev))
+    p_critics = torch.nn.Parameter(torch.stack([qnet.from_module(mlp(OD + AD, 1)) for _ in range(2)]).to(dev))
+    log_alpha = torch.nn.Parameter(torch.zeros(1, device=dev))
+    t_critics = p_critics.detach().clone()
+    opt_a, opt_c, opt_t = (torch.optim.Adam([p], lr=args.lr) for p in (p_actor, p_critics, log_alpha))
+    buf = ReplayBuffer(args.capacity, OD, AD, dev)
+    env.reset()
+    step = 0
+    for update in range(args.updates):
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            batch = env.collect(pol, p_actor.detach(), args.steps, iteration=update, return_final_obs=True)
+            buf.add(batch)
+        data = buf.data()
+        torch.cuda.synchronize()
+        t_collect = time.perf_counter() - t0
+        for _ in range(args.grad_steps):
+            rows = buf.sample_rows(args.batch)
+            if args.torch:
+                loss_q, loss_pi, loss_alpha, logp = sac_losses(pol, p_actor, qnet, p_critics, t_critics, log_alpha, data, rows.long(), args.gamma,
+                                                               -float(AD))
+                for opt in (opt_c, opt_a, opt_t):
+                    opt.zero_grad(set_to_none=True)
+                for loss in (loss_q, loss_pi, loss_alpha):   # (every backward() before the first step: loss_pi reads the critics' values)
+                    loss.backward()
+                for opt in (opt_c, opt_a, opt_t):
+                    opt.step()
+            else:
+                out = env.sac_gradient(data, pol, p_actor, qnet, p_critics, t_critics, log_alpha, rows=rows, gamma=args.gamma,
+                                       noise_seed=args.seed + 1, noise_step=step)
+                p_actor.grad, p_critics.grad, log_alpha.grad = out["grad_params"], out["grad_critic_params"], out["grad_log_alpha"]
+                for opt in (opt_c, opt_a, opt_t):
+                    opt.step()
+                st = out["stats"]
+                loss_q, loss_pi, loss_alpha, logp = st["loss_q0"] + st["loss_q1"], st["loss_pi"], st["loss_alpha"], st["log_prob"]
+            with torch.no_grad():
+                t_critics.lerp_(p_critics, args.tau)
+            step += 1
+        torch.cuda.synchronize()
+        m = env.metrics()
+        print(f"update {update}: mean reward / step {float(batch['reward'].mean()):+.5f}, collected log_prob {float(batch['log_prob'].mean()):+.3f}, "
+              f"mean log_std {float(batch['log_std'].mean()):+.3f}, episodes {m['episodes']}, goals for / against {m['goals_for']} / "
+              f"{m['goals_against']}, buffer {int(buf.fill)} rows, loss_q {float(loss_q.detach()):.5f}, loss_pi {float(loss_pi.detach()):+.5f}, alpha "
+              f"{float(log_alpha.detach().exp()):.4f}, log_prob {float(logp):+.3f}; collect + add {t_collect * 1e3:.1f} ms, {args.grad_steps} gradient "
+              f"steps {((time.perf_counter() - t0) - t_collect) * 1e3:.1f} ms")
+    env.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -521,6 +521,52 @@ int rsx_task_collect_policy(rsx_sim* h, const rsx_policy_mlp* p, const float* pa
                             const float* sigma_dev /* [act_dim] >= 0, or NULL = deterministic */, uint64_t noise_seed,
                             int n_steps, const rsx_collect_out* out, void* stream);
 
+/* ---- collection under a state-dependent, tanh-squashed Gaussian head (additive extension of ABI 6) ---------------------------------
+ * rsx_task_collect_policy with another action source: the actor of soft actor-critic, whose output layer gives a mean AND a log-std per
+ * state and whose sample is squashed by tanh.  Everything else is that call's: the multi-step trip with same-step auto-reset inside
+ * one launch, rsx_collect_out (mean = mu, sample = u, actions = a), the step counter on host-keyed and device-keyed handles, capture on
+ * device-keyed handles, and the commit guarantee — the handle ends up bit for bit where n_steps calls of rsx_task_step(h,
+ * out->actions[t]) leave it, checkpoint, metrics and the per-env physics block included.
+ *   p, params_dev    an rsx_policy_mlp with out_act = RSX_ACT_NONE whose OUTPUT LAYER IS 2 * act_dim UNITS WIDE: rows [0, AD) of Wo / bo
+ *                    are the mean mu, rows [AD, 2 AD) the raw log-std.  P = rsx_policy_num_params of the shape + act_dim * hidden + act_dim.
+ *                    Hidden layers and arithmetic are rsx_policy_mlp's (bias, ascending fmaf, float32): mu_k and raw_k are output
+ *                    units k and AD + k as every other evaluation of these parameters computes them, bit for bit.
+ *   the head         all float32, each operation rounded (the unit is built with -ffp-contract=off):
+ *                      ls_k    = clamp(raw_k, log_std_min, log_std_max)       gradient as torch.clamp: 1 inside, bounds included, else 0
+ *                      sigma_k = exp(ls_k)
+ *                      u_k     = mu_k + sigma_k * eps_k                       a multiplication and an addition (two roundings)
+ *                      a_k     = tanh(u_k)                                    RSX_ACT_TANH's tanh, unchanged
+ *                      logp    = sum_k [ -0.5 eps_k^2 - ls_k - 0.5 ln(2 pi) - 2 (ln 2 - u_k - softplus(-2 u_k)) ]
+ *                      softplus(z) = max(z, 0) + log1p(exp(-|z|))
+ *                    The tanh correction is in the stable form and not log(1 - a^2 + 1e-6): the tanh has an absolute error near 1e-7,
+ *                    so 1 - a^2 is useless near saturation.  With the reparameterisation (eps a constant), d logp / d u_k = 2 a_k.
+ *                    This call computes ls, sigma, u and a; logp is the caller's, from mean, log_std and sample (eps_k = (u_k - mu_k) /
+ *                    sigma_k), in whatever precision it wants.
+ *   exp              exp(x) = e + e * (r * ln 2) with t = fl(x * c), c = fl(log2 e), r = fmaf(x, log2 e - c, fmaf(x, c, -t)), e =
+ *                    exp2(t) on the hardware (1 ulp): the exponent's rounding error is carried in r, so the relative error does not
+ *                    grow with |x|.  Relative error below 5e-7 for |x| <= 80.
+ *   cfg->deterministic != 0   u_k = mu_k, no draw; log_std_out is still written.
+ *   eps              the collector's own draw, unchanged: domain word 7, counter (global env id, 0, tick of that step, 7 | (k >> 2) << 8),
+ *                    key noise_seed, component k takes normal k & 3.  For one noise_seed the recorded sample differs from
+ *                    rsx_task_collect_policy's only by the state-dependent sigma.
+ *   log_std_out      [T][B][act_dim] f32 or NULL: ls, the clamped log-std.
+ * Handles: every handle rsx_task_collect_policy serves — lane widths 8 / 16 / 32, handles whose single steps run one lane per env, with
+ * and without per-env physics.  Lane b < act_dim of an env computes output units b and act_dim + b, so act_dim <= lanes per env stays
+ * the only lane condition.
+ * LDS: the policy image with the wider output layer (pitch (2 act_dim) | 1, a bias slot of 16 floats) plus the step's own block.  VSS-v0
+ * 3v3 with 2 x 64 units: 36 928 B of image (rsx_task_collect_policy: 36 384 B) + 6 272 B = 43 200 B, three workgroups per CU, as there.
+ * Refusals (nothing is enqueued): all of rsx_task_collect_policy's, and RSX_ERR_ARG for a null cfg, out_act != RSX_ACT_NONE, log-std
+ * bounds that are not finite or not log_std_min < log_std_max, and reserved != 0. */
+typedef struct rsx_collect_gaussian_cfg {
+    uint64_t noise_seed;
+    float    log_std_min, log_std_max;
+    int32_t  deterministic;   /* != 0: a = tanh(mu), no draw */
+    int32_t  reserved;        /* 0 */
+} rsx_collect_gaussian_cfg;
+int rsx_task_collect_gaussian(rsx_sim* h, const rsx_policy_mlp* p, const float* params_dev /* [P], 2 * act_dim outputs */,
+                              const rsx_collect_gaussian_cfg* cfg, int n_steps, const rsx_collect_out* out,
+                              float* log_std_out /* [T][B][act_dim] or NULL */, void* stream);
+
 /* ---- self-play collection for VSS-v0: a policy-driven opponent inside the launch (additive extension of ABI 6) ---------------------
  * rsx_task_collect_policy with ONE command replaced: yellow robot 0 (body index n_blue) is driven by a second MLP policy, the opponent
  * — typically a frozen earlier copy of the learner — instead of its Ornstein-Uhlenbeck noise.  The opponent is evaluated inside the same
@@ -1019,6 +1065,85 @@ int rsx_dpg_gradient_workspace(const rsx_sim* h, const rsx_policy_mlp* actor, co
 int rsx_task_dpg_gradient(rsx_sim* h, const rsx_policy_mlp* actor, const float* actor_params_dev, const float* target_actor_params_dev,
                           const rsx_policy_mlp* critic, const float* critic_params_dev, const float* target_critic_params_dev,
                           const rsx_dpg_in* in, const rsx_dpg_cfg* cfg, const rsx_dpg_out* out, void* stream);
+
+/* ---- soft actor-critic loss gradients of a squashed Gaussian actor, one or two Q critics and the temperature (additive extension of ABI 6) ----
+ * rsx_task_dpg_gradient's counterpart for SAC: the handle, the transitions, `rows` and the critics are that call's (rsx_dpg_in is reused as
+ * it is: repeats allowed, NULL = rows 0 .. M - 1, an index outside [0, N) contributes nothing, is counted in stats[11] and nothing outside
+ * the arrays is read for it, the divisor stays M).  There is no target actor.
+ *   actor            the policy of rsx_task_collect_gaussian: out_act = RSX_ACT_NONE, an output layer of 2 * act_dim units (rows [0, AD)
+ *                    the mean, rows [AD, 2 AD) the raw log-std), actor_params_dev [Pa]; the head is the one stated there.
+ *   log_alpha_dev    [1] f32 on the device; alpha = exp(*log_alpha_dev) (that section's exp), read when the launches run.
+ * The losses; t is an entry's POSITION in the minibatch, a mean is the sum over the M entries times the float32 1 / M:
+ *   eps', eps        the collector's standard-normal recipe under domain word 12 (eps', on next_obs) and 13 (eps, on obs), the next two
+ *                    free ones (1 and 3 .. 11 are taken): counter (t, noise_step >> 32, noise_step & 0xFFFFFFFF, dom | (k >> 2) << 8), key =
+ *                    noise_seed (lo, hi); component k takes normal k & 3 of its block.  noise_step as in rsx_dpg_cfg.
+ *   a', logp'        head(actor(next_obs), eps')                                       no gradient
+ *   y                terminated ? reward : reward + gamma * (min_c Q_targ_c(next_obs, a') - alpha * logp')
+ *   L_q              sum over c of 0.5 * mean((Q_c(obs, action) - y)^2): grad_critics[c]
+ *   a~, logp         head(actor(obs), eps)
+ *   L_pi             mean(alpha * logp - min_c Q_c(obs, a~)): grad_actor.  Both critics are differentiated with respect to their action
+ *                    inputs, not their weights; per entry the critic that gives the minimum passes its dQ/da, on an exact tie critic 0.
+ *                    The gradient flows through tanh, the reparameterisation (eps a constant) and the log-std clamp into all 2 AD output
+ *                    rows:  dL/du_k = (alpha * 2 a_k - dQ/da_k * (1 - a_k^2)) / M  with 1 - a_k^2 computed as fmaf(-a_k, a_k, 1);
+ *                    dL/dmu_k = dL/du_k;  dL/dls_k = dL/du_k * (sigma_k * eps_k) - alpha / M;  dL/draw_k = dL/dls_k where
+ *                    log_std_min <= raw_k <= log_std_max (bounds included, as torch.clamp), else 0.  alpha and y carry no gradient.
+ *   L_alpha          -log_alpha * mean(logp + target_entropy): grad_log_alpha[0] = -mean(logp + target_entropy)
+ *   log1p            on [0, 1]: w = fl(1 + y), d = w - 1 (exact), log2(w) * ln 2 * (y / d) on the hardware's log2 and reciprocal, y itself
+ *                    when d == 0.  Absolute error below 3e-7.  logp sums its AD terms in ascending k.
+ * Forwards are rsx_policy_mlp's arithmetic bit for bit, so out->mean and out->log_std equal what rsx_task_collect_gaussian records for
+ * the same observation.  Backward: rsx_task_dpg_gradient's rules, word for word (blocks of 64 entries, G = min(ceil(M / 64),
+ * max_workgroups) workgroups with default cap 256, one fmaf chain per workgroup for a weight gradient — the f32 MFMA for the hidden
+ * layers —, float64 block sums rounded once for bias gradients, dz and dQ/da as four interleaved chains combined (s0 + s1) + (s2 + s3),
+ * per-workgroup partials added in workgroup order from 0, stats per lane, then over the lanes, then over the workgroups; no float
+ * atomics).  The result bits are a function of the inputs and of G alone.
+ * Six launches: (1) the targets — the actor and the C target critics in one workgroup's LDS; (2) the critics' gradients, grid.y = critic;
+ * (3) the actor's sample a~, logp into the workspace; (4) each critic on (obs, a~) with its dQ/da, grid.y = critic; (5) the actor's
+ * backward pass with the selected dQ/da; (6) the reduce.  The actor and the online critics never share a workgroup's LDS.  LDS per
+ * workgroup at the largest shape (2 x 64 units, OD = 64, AD = 5, C = 2): targets 129 568 B, critic 63 344 B, sample 55 616 B,
+ * critic-on-sample 54 640 B, actor 67 136 B.  A shape that needs more than 163 840 B in a launch is refused with the byte count in the
+ * error string.  No kernel uses scratch memory.
+ *   stats            [12]: 0 / 1 L_q of critic 0 / 1 (0 for an absent critic), 2 / 3 mean Q_0 / Q_1 (obs, action), 4 L_pi, 5 L_alpha,
+ *                    6 mean y, 7 mean logp, 8 mean logp', 9 alpha, 10 entries used, 11 entries skipped
+ *   per entry        optional, 0 for a skipped entry: target [M]; q [C][M]; action [M][AD] = a~; log_prob [M]; next_log_prob [M];
+ *                    eps, next_eps, mean, log_std [M][AD]
+ *   workspace        at least rsx_sac_gradient_workspace bytes, 16-byte aligned; its contents before the call do not matter
+ * Stream-ordered, never synchronises, never allocates, capturable; a replayed graph draws fresh noise when noise_step_dev's counter was
+ * advanced.  Refusals (nothing is enqueued), all RSX_ERR_ARG: rsx_task_dpg_gradient's, and a null log_alpha_dev, grad_actor or
+ * grad_log_alpha, a non-finite target_entropy, log-std bounds that are not finite or not ordered, an actor whose out_act is not
+ * RSX_ACT_NONE. */
+typedef struct rsx_sac_cfg {
+    const int64_t* noise_step_dev;  /* NULL: noise_step; else the device address of the step */
+    uint64_t       noise_seed;
+    int64_t        noise_step;
+    float          gamma;           /* in [0, 1] */
+    float          target_entropy;  /* finite; SAC's usual choice is -act_dim */
+    float          log_std_min;
+    float          log_std_max;
+    int32_t        n_critics;       /* 1 or 2 */
+    int32_t        max_workgroups;  /* 0 = the build's default; > 0 caps the grid */
+} rsx_sac_cfg;
+typedef struct rsx_sac_out {
+    float* grad_actor;      /* [Pa]      required */
+    float* grad_critics;    /* [C][Pc]   required */
+    float* grad_log_alpha;  /* [1]       required */
+    float* stats;           /* [12]      required */
+    float* target;          /* [M] or NULL */
+    float* q;               /* [C][M] or NULL */
+    float* action;          /* [M][act_dim] or NULL */
+    float* log_prob;        /* [M] or NULL */
+    float* next_log_prob;   /* [M] or NULL */
+    float* eps;             /* [M][act_dim] or NULL */
+    float* next_eps;        /* [M][act_dim] or NULL */
+    float* mean;            /* [M][act_dim] or NULL */
+    float* log_std;         /* [M][act_dim] or NULL */
+    void*  workspace;       /* rsx_sac_gradient_workspace bytes   required */
+} rsx_sac_out;
+int rsx_sac_gradient_workspace(const rsx_sim* h, const rsx_policy_mlp* actor, const rsx_policy_mlp* critic, int n_critics,
+                               int64_t n_rows, int max_workgroups, int64_t* bytes_out);
+int rsx_task_sac_gradient(rsx_sim* h, const rsx_policy_mlp* actor, const float* actor_params_dev,
+                          const rsx_policy_mlp* critic, const float* critic_params_dev, const float* target_critic_params_dev,
+                          const float* log_alpha_dev /* [1] */, const rsx_dpg_in* in, const rsx_sac_cfg* cfg,
+                          const rsx_sac_out* out, void* stream);
 
 /* ---- the TD3 / DDPG update phase on the device: sample, Adam, Polyak (additive extension of ABI 6) ---------------------------------
  * What an off-policy trainer does around rsx_task_dpg_gradient, per gradient step: draw the minibatch's rows, clip and step the critics

@@ -52,11 +52,12 @@ SYMBOLS = (
     "rsx_task_transfer", "rsx_task_transfer_errors",
     "rsx_task_lookahead_sampled", "rsx_plan_candidates", "rsx_plan_update",
     "rsx_policy_num_params", "rsx_task_lookahead_policy", "rsx_task_lookahead_match",
-    "rsx_task_collect_policy", "rsx_task_collect_selfplay", "rsx_task_collect_team",
+    "rsx_task_collect_policy", "rsx_task_collect_selfplay", "rsx_task_collect_team", "rsx_task_collect_gaussian",
     "rsx_critic_num_params", "rsx_task_advantages",
     "rsx_ppo_gradient_workspace", "rsx_task_ppo_gradient",
     "rsx_ppo_normalize", "rsx_ppo_permutation", "rsx_adam_step", "rsx_adam_mark", "rsx_ppo_update_workspace", "rsx_task_ppo_update",
     "rsx_dpg_gradient_workspace", "rsx_task_dpg_gradient",
+    "rsx_sac_gradient_workspace", "rsx_task_sac_gradient",
     "rsx_replay_sample_rows", "rsx_dpg_adam_step", "rsx_dpg_update_workspace", "rsx_task_dpg_update",
 )
 # activations of rsx_policy_mlp (include/rsx.h: RSX_ACT_*)
@@ -82,6 +83,12 @@ class CollectOut(C.Structure):
     """rsx_collect_out (include/rsx.h): the [T][B] record of rsx_task_collect_policy; device addresses, the last three may be None"""
     _fields_ = [("obs", C.c_void_p), ("actions", C.c_void_p), ("rewards", C.c_void_p), ("flags", C.c_void_p),
                 ("final_obs", C.c_void_p), ("mean", C.c_void_p), ("sample", C.c_void_p)]
+
+
+class CollectGaussianCfg(C.Structure):
+    """rsx_collect_gaussian_cfg (include/rsx.h): the squashed Gaussian head of rsx_task_collect_gaussian"""
+    _fields_ = [("noise_seed", C.c_uint64), ("log_std_min", C.c_float), ("log_std_max", C.c_float), ("deterministic", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 class SelfplayOut(C.Structure):
@@ -164,6 +171,26 @@ class DpgOut(C.Structure):
 
 # the slots of rsx_dpg_out.stats, in order
 DPG_STATS = ("loss_q0", "loss_q1", "q0", "q1", "loss_pi", "target", "abs_next_action", "rows_used", "rows_skipped")
+
+
+class SacCfg(C.Structure):
+    """rsx_sac_cfg (include/rsx.h): the draws' step (by value or as a device address) and seed, gamma, the target entropy, the log-std
+    bounds, the number of critics and the cap of the grid (0 = the build's default)"""
+    _fields_ = [("noise_step_dev", C.c_void_p), ("noise_seed", C.c_uint64), ("noise_step", C.c_int64), ("gamma", C.c_float),
+                ("target_entropy", C.c_float), ("log_std_min", C.c_float), ("log_std_max", C.c_float), ("n_critics", C.c_int32),
+                ("max_workgroups", C.c_int32)]
+
+
+class SacOut(C.Structure):
+    """rsx_sac_out (include/rsx.h): the three gradients, the stats [12], the optional per-entry outputs and the workspace; device addresses"""
+    _fields_ = [("grad_actor", C.c_void_p), ("grad_critics", C.c_void_p), ("grad_log_alpha", C.c_void_p), ("stats", C.c_void_p),
+                ("target", C.c_void_p), ("q", C.c_void_p), ("action", C.c_void_p), ("log_prob", C.c_void_p), ("next_log_prob", C.c_void_p),
+                ("eps", C.c_void_p), ("next_eps", C.c_void_p), ("mean", C.c_void_p), ("log_std", C.c_void_p), ("workspace", C.c_void_p)]
+
+
+# the slots of rsx_sac_out.stats, in order
+SAC_STATS = ("loss_q0", "loss_q1", "q0", "q1", "loss_pi", "loss_alpha", "target", "log_prob", "next_log_prob", "alpha", "rows_used",
+             "rows_skipped")
 
 
 # the update phase (include/rsx.h: rsx_ppo_normalize, rsx_adam_step, rsx_task_ppo_update)
@@ -336,6 +363,7 @@ def load():
     lib.rsx_policy_num_params.argtypes = [vp, C.POINTER(PolicyMLP), C.POINTER(C.c_int64)]
     lib.rsx_task_lookahead_policy.argtypes = [vp, C.POINTER(PolicyMLP), vp, ip, ip, C.c_float, vp, vp, vp, vp, vp, vp, vp]
     lib.rsx_task_collect_policy.argtypes = [vp, C.POINTER(PolicyMLP), vp, vp, C.c_uint64, ip, C.POINTER(CollectOut), vp]
+    lib.rsx_task_collect_gaussian.argtypes = [vp, C.POINTER(PolicyMLP), vp, C.POINTER(CollectGaussianCfg), ip, C.POINTER(CollectOut), vp, vp]
     lib.rsx_task_collect_selfplay.argtypes = [vp, C.POINTER(PolicyMLP), vp, vp, C.POINTER(PolicyMLP), vp, vp, C.c_uint64, ip,
                                               C.POINTER(CollectOut), C.POINTER(SelfplayOut), vp]
     lib.rsx_task_lookahead_match.argtypes = [vp, C.POINTER(PolicyMLP), vp, ip, ip, C.POINTER(PolicyMLP), vp, ip, ip, ip, C.c_float,
@@ -356,6 +384,9 @@ def load():
     lib.rsx_task_ppo_update.argtypes = [vp, C.POINTER(PolicyMLP), vp, vp, C.POINTER(PolicyMLP), vp, C.POINTER(PpoIn), C.POINTER(PpoCfg),
                                         C.POINTER(PpoUpdateCfg), C.POINTER(AdamCfg), C.POINTER(AdamState), vp, vp, vp]
     lib.rsx_dpg_gradient_workspace.argtypes = [vp, C.POINTER(PolicyMLP), C.POINTER(PolicyMLP), ip, C.c_int64, ip, C.POINTER(C.c_int64)]
+    lib.rsx_sac_gradient_workspace.argtypes = [vp, C.POINTER(PolicyMLP), C.POINTER(PolicyMLP), ip, C.c_int64, ip, C.POINTER(C.c_int64)]
+    lib.rsx_task_sac_gradient.argtypes = [vp, C.POINTER(PolicyMLP), vp, C.POINTER(PolicyMLP), vp, vp, vp, C.POINTER(DpgIn), C.POINTER(SacCfg),
+                                          C.POINTER(SacOut), vp]
     lib.rsx_task_dpg_gradient.argtypes = [vp, C.POINTER(PolicyMLP), vp, vp, C.POINTER(PolicyMLP), vp, vp, C.POINTER(DpgIn), C.POINTER(DpgCfg),
                                           C.POINTER(DpgOut), vp]
     lib.rsx_replay_sample_rows.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, vp, C.c_uint64, C.c_int64, vp, vp]
@@ -778,6 +809,15 @@ class Sim:
         if rc:
             _chk(rc)
 
+    def task_collect_gaussian(self, spec, params_ptr, cfg, n_steps, out, log_std_ptr=None, stream=None):
+        """rsx_task_collect_gaussian: ``task_collect_policy`` under a state-dependent tanh-squashed Gaussian head: ``spec`` a PolicyMLP
+        with out_act = ACT_NONE whose output layer is 2 * act_dim wide (params [P] f32), ``cfg`` a CollectGaussianCfg, ``out`` a
+        CollectOut; each may be None to pass NULL.  ``log_std_ptr``: [T][B][act_dim] f32 device address for the clamped log-std, or None."""
+        ref = lambda v: None if v is None else C.byref(v)   # noqa: E731
+        rc = self._lib.rsx_task_collect_gaussian(self._h, ref(spec), params_ptr, ref(cfg), int(n_steps), ref(out), log_std_ptr, stream)
+        if rc:
+            _chk(rc)
+
     def task_collect_selfplay(self, spec, params_ptr, sigma_ptr, opp_spec, opp_params_ptr, opp_sigma_ptr, noise_seed, n_steps, out, sp,
                               stream=None):
         """rsx_task_collect_selfplay: ``task_collect_policy`` on a VSS-v0 handle with yellow robot 0 driven by a second MLP policy
@@ -867,6 +907,25 @@ class Sim:
         b = lambda x: None if x is None else C.byref(x)   # noqa: E731
         rc = self._lib.rsx_task_dpg_gradient(self._h, b(actor), actor_params_ptr, target_actor_params_ptr, b(critic), critic_params_ptr,
                                              target_critic_params_ptr, b(inp), b(cfg), b(out), stream)
+        if rc:
+            _chk(rc)
+
+    def sac_gradient_workspace(self, actor, critic, n_critics, n_rows, max_workgroups=0):
+        """rsx_sac_gradient_workspace: bytes of scratch rsx_task_sac_gradient needs for a minibatch of ``n_rows`` rows"""
+        n = C.c_int64(0)
+        _chk(self._lib.rsx_sac_gradient_workspace(self._h, None if actor is None else C.byref(actor), None if critic is None else C.byref(critic),
+                                                  int(n_critics), int(n_rows), int(max_workgroups), C.byref(n)))
+        return int(n.value)
+
+    def task_sac_gradient(self, actor, actor_params_ptr, critic, critic_params_ptr, target_critic_params_ptr, log_alpha_ptr, inp, cfg, out,
+                          stream=None):
+        """rsx_task_sac_gradient: gradients of the soft actor-critic losses with respect to the actor's and the critics' parameters and
+        the log-temperature on a minibatch of replayed transitions, in six launches.  ``actor`` / ``critic``: PolicyMLP specs (the actor's
+        output layer 2 * act_dim wide, out_act = ACT_NONE), ``inp``: a DpgIn, ``cfg``: a SacCfg, ``out``: a SacOut of device addresses
+        (None passes NULL).  Reads and writes nothing of the envs."""
+        b = lambda x: None if x is None else C.byref(x)   # noqa: E731
+        rc = self._lib.rsx_task_sac_gradient(self._h, b(actor), actor_params_ptr, b(critic), critic_params_ptr, target_critic_params_ptr,
+                                             log_alpha_ptr, b(inp), b(cfg), b(out), stream)
         if rc:
             _chk(rc)
 

@@ -431,6 +431,45 @@ int rsx_task_collect_policy(rsx_sim* h, const rsx_policy_mlp* p, const float* pa
     return debug_finite(h, s, "rsx_task_collect_policy");
 }
 
+// ---- the same under a state-dependent tanh-squashed Gaussian head: the output layer gives mean and log-std (rsx.h: rsx_task_collect_gaussian) ----
+int rsx_task_collect_gaussian(rsx_sim* h, const rsx_policy_mlp* p, const float* params_dev, const rsx_collect_gaussian_cfg* cfg, int n_steps,
+                              const rsx_collect_out* out, float* log_std_out, void* stream) {
+    RSX_ENTER(h);
+    PolicySpec S; int64_t n_params = 0;
+    if (!p) return fail(RSX_ERR_ARG, "the policy (rsx_policy_mlp) must not be null");
+    rsx_policy_mlp shape = *p;
+    shape.out_act = RSX_ACT_TANH;   // (what the head applies; the shape's own checks are rsx_task_collect_policy's)
+    if (int rc = policy_prologue(h, &shape, &S, &n_params)) return rc;
+    if (p->out_act != RSX_ACT_NONE)
+        return fail(RSX_ERR_ARG, "rsx_task_collect_gaussian: out_act must be RSX_ACT_NONE (the head clamps the log-std and squashes the sample itself)");
+    S.out_act = RSX_ACT_NONE;
+    n_params += (int64_t)h->M.act_dim * p->hidden + h->M.act_dim;   // the output layer is 2 * act_dim units wide
+    RSX_NEED_RESET(h);
+    if (!cfg) return fail(RSX_ERR_ARG, "cfg (rsx_collect_gaussian_cfg) must not be null");
+    if (!std::isfinite(cfg->log_std_min) || !std::isfinite(cfg->log_std_max) || !(cfg->log_std_min < cfg->log_std_max))
+        return fail(RSX_ERR_ARG, "log_std_min and log_std_max must be finite with log_std_min < log_std_max");
+    if (cfg->reserved != 0) return fail(RSX_ERR_ARG, "rsx_collect_gaussian_cfg.reserved must be 0");
+    if (n_steps < 1 || n_steps > RSX_N_STEPS_MASK) return fail(RSX_ERR_ARG, "n_steps must be in 1 .. 2^30 - 1");
+    if (!params_dev) return fail(RSX_ERR_ARG, "params_dev must not be null");
+    if (!out || !out->obs || !out->actions || !out->rewards || !out->flags)
+        return fail(RSX_ERR_ARG, "out and its obs, actions, rewards and flags arrays must not be null");
+    if (h->L > 32) return fail(RSX_ERR_ARG, "rsx_task_collect_gaussian has no 64-lanes-per-env kernels (unset RSX_LANES_PER_ENV)");
+    if (gaussian_lds_bytes(h->L, h->P.obs_dim, h->M.act_dim, S) > 65536ll)
+        return fail(RSX_ERR_ARG, "the policy's weights do not fit a workgroup's 64 KB of LDS at this observation width: use fewer or smaller hidden layers");
+    hipStream_t s = (hipStream_t)stream;
+    int fl = 0;
+    if (int rc = step_prologue(h, s, (uint64_t)n_steps, &fl)) return rc;   // capture of a host-keyed handle, counter limit
+    h->host_state_valid = false;
+    const int grid = grid_for(h);   // (the tick slots: as rsx_task_collect_policy, the launch has its grid)
+    if (h->tick_dev) launch_tick_fill(tick_slot0(h), h->tick_slots, grid, 0u, 1, s);
+    h->P.tick_base = h->tick; h->tick += (uint32_t)n_steps;
+    launch_task_collect_gaussian(h->P, buffers_of(h, nullptr), h->L, h->NR, h->d_phys, S, params_dev, (int)n_params, h->M.act_dim, *cfg,
+                                 n_steps | fl, *out, log_std_out, s);
+    if (h->tick_dev) launch_tick_fill(tick_slot0(h), grid, h->tick_slots, 0u, 1, s);
+    HIP_TRY(launch_status());
+    return debug_finite(h, s, "rsx_task_collect_gaussian");
+}
+
 // ---- the same with yellow robot 0 of VSS-v0 driven by a second policy from the mirrored observation (rsx.h: rsx_task_collect_selfplay) ----
 int rsx_task_collect_selfplay(rsx_sim* h, const rsx_policy_mlp* actor, const float* actor_params_dev, const float* sigma_dev,
                               const rsx_policy_mlp* opponent, const float* opponent_params_dev, const float* opponent_sigma_dev,
@@ -660,6 +699,76 @@ int rsx_task_dpg_gradient(rsx_sim* h, const rsx_policy_mlp* actor, const float* 
     if (!out || !out->grad_critics || !out->stats || !out->workspace)
         return fail(RSX_ERR_ARG, "out and its grad_critics, stats and workspace must not be null");
     launch_dpg_gradient(SA, na, actor_params_dev, target_actor_params_dev, SC, nc, critic_params_dev, target_critic_params_dev, h->P.obs_dim,
+                        h->M.act_dim, *in, *cfg, *out, (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
+// ---- soft actor-critic loss gradients of a squashed Gaussian actor, its Q critics and the temperature (rsx.h: rsx_task_sac_gradient) ----
+// what both calls check of the networks (dpg_prologue's checks with the actor's output layer 2 * act_dim wide and out_act = RSX_ACT_NONE)
+static int sac_prologue(const rsx_sim* h, const rsx_policy_mlp* actor, const rsx_policy_mlp* critic, int n_critics, PolicySpec* SA,
+                        int64_t* n_actor, PolicySpec* SC, int64_t* n_critic) {
+    if (h->P.task == RSX_TASK_NONE) return fail(RSX_ERR_ARG, "no task attached (rsx_task_attach): obs_dim and act_dim are the task's");
+    if (!actor) return fail(RSX_ERR_ARG, "the actor (rsx_policy_mlp) must not be null");
+    rsx_policy_mlp shape = *actor;
+    shape.out_act = RSX_ACT_TANH;   // (what the head applies; the shape's own checks are rsx_task_dpg_gradient's)
+    if (int rc = policy_prologue(h, &shape, SA, n_actor)) return rc;
+    if (actor->out_act != RSX_ACT_NONE)
+        return fail(RSX_ERR_ARG, "rsx_task_sac_gradient: the actor's out_act must be RSX_ACT_NONE (the head clamps the log-std and squashes the sample itself)");
+    SA->out_act = RSX_ACT_NONE;
+    if (int rc = critic_prologue(h, critic, SC, n_critic)) return rc;
+    if (n_critics != 1 && n_critics != 2) return fail(RSX_ERR_ARG, "n_critics must be 1 or 2");
+    const int OD = h->P.obs_dim, AD = h->M.act_dim;
+    if (AD > 8) return fail(RSX_ERR_ARG, "act_dim above 8 is not supported");
+    *n_actor += (int64_t)AD * actor->hidden + AD;   // the output layer is 2 * act_dim units wide
+    const int64_t H = critic->hidden;
+    *n_critic = H * (OD + AD) + H + (critic->n_hidden_layers == 2 ? H * H + H : 0) + H + 1;   // (the input row is [obs | action])
+    static const char* const names[5] = {"target", "critic", "sample", "critic-on-sample", "actor"};
+    for (int l = 0; l < 5; ++l) {
+        const long long bytes = sac_lds_bytes(l, OD, AD, *SA, *SC, n_critics);
+        if (bytes > 163840ll) {
+            char msg[200];
+            std::snprintf(msg, sizeof msg, "the %s launch needs %lld bytes of LDS per workgroup, a CU has 163840: use fewer or smaller hidden layers",
+                          names[l], bytes);
+            return fail(RSX_ERR_ARG, msg);
+        }
+    }
+    return RSX_OK;
+}
+
+int rsx_sac_gradient_workspace(const rsx_sim* h, const rsx_policy_mlp* actor, const rsx_policy_mlp* critic, int n_critics, int64_t n_rows,
+                               int max_workgroups, int64_t* bytes_out) {
+    if (!h) return fail(RSX_ERR_ARG, "null handle");
+    if (!bytes_out) return fail(RSX_ERR_ARG, "bytes_out must not be null");
+    PolicySpec SA, SC; int64_t na = 0, nc = 0;
+    if (int rc = sac_prologue(h, actor, critic, n_critics, &SA, &na, &SC, &nc)) return rc;
+    if (n_rows < 1 || n_rows > 0x7FFFFFFFll) return fail(RSX_ERR_ARG, "n_rows must be in 1 .. 2^31 - 1");
+    if (max_workgroups < 0) return fail(RSX_ERR_ARG, "max_workgroups must be >= 0");
+    *bytes_out = sac_workspace_bytes(na, nc, n_critics, n_rows, max_workgroups);
+    return RSX_OK;
+}
+
+int rsx_task_sac_gradient(rsx_sim* h, const rsx_policy_mlp* actor, const float* actor_params_dev, const rsx_policy_mlp* critic,
+                          const float* critic_params_dev, const float* target_critic_params_dev, const float* log_alpha_dev,
+                          const rsx_dpg_in* in, const rsx_sac_cfg* cfg, const rsx_sac_out* out, void* stream) {
+    RSX_ENTER(h);   // (nothing the handle owns is read or written by the launches)
+    if (!cfg) return fail(RSX_ERR_ARG, "cfg must not be null");
+    PolicySpec SA, SC; int64_t na = 0, nc = 0;
+    if (int rc = sac_prologue(h, actor, critic, cfg->n_critics, &SA, &na, &SC, &nc)) return rc;
+    if (!actor_params_dev || !critic_params_dev || !target_critic_params_dev || !log_alpha_dev)
+        return fail(RSX_ERR_ARG, "actor_params_dev, critic_params_dev, target_critic_params_dev and log_alpha_dev must not be null");
+    if (!in || !in->obs || !in->action || !in->reward || !in->next_obs || !in->terminated)
+        return fail(RSX_ERR_ARG, "in and its obs, action, reward, next_obs and terminated arrays must not be null");
+    if (in->n_rows < 1 || in->n_batch_rows < 1 || in->n_rows > 0x7FFFFFFFll || in->n_batch_rows > 0x7FFFFFFFll)
+        return fail(RSX_ERR_ARG, "n_rows and n_batch_rows must be in 1 .. 2^31 - 1");
+    if (!(std::isfinite(cfg->gamma) && cfg->gamma >= 0.0f && cfg->gamma <= 1.0f)) return fail(RSX_ERR_ARG, "gamma must be in [0, 1]");
+    if (!std::isfinite(cfg->target_entropy)) return fail(RSX_ERR_ARG, "target_entropy must be finite");
+    if (!std::isfinite(cfg->log_std_min) || !std::isfinite(cfg->log_std_max) || !(cfg->log_std_min < cfg->log_std_max))
+        return fail(RSX_ERR_ARG, "log_std_min and log_std_max must be finite with log_std_min < log_std_max");
+    if (cfg->max_workgroups < 0) return fail(RSX_ERR_ARG, "max_workgroups must be >= 0");
+    if (!out || !out->grad_actor || !out->grad_critics || !out->grad_log_alpha || !out->stats || !out->workspace)
+        return fail(RSX_ERR_ARG, "out and its grad_actor, grad_critics, grad_log_alpha, stats and workspace must not be null");
+    launch_sac_gradient(SA, na, actor_params_dev, SC, nc, critic_params_dev, target_critic_params_dev, log_alpha_dev, h->P.obs_dim,
                         h->M.act_dim, *in, *cfg, *out, (hipStream_t)stream);
     HIP_TRY(launch_status());
     return RSX_OK;

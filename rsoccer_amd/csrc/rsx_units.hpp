@@ -7,6 +7,7 @@
 
 struct rsx_render_view;   // include/rsx.h
 struct rsx_collect_out;
+struct rsx_collect_gaussian_cfg;
 struct rsx_selfplay_out;
 struct rsx_team_out;
 struct rsx_adv_in;
@@ -18,6 +19,8 @@ struct rsx_ppo_update_cfg;
 struct rsx_dpg_in;
 struct rsx_dpg_cfg;
 struct rsx_dpg_out;
+struct rsx_sac_cfg;
+struct rsx_sac_out;
 struct rsx_adam_cfg;
 struct rsx_adam_state;
 struct rsx_adam_io;
@@ -104,6 +107,13 @@ void launch_task_lookahead_policy(const Params& P, int L, int NR, const float* s
 void launch_task_collect_policy(const Params& P, const Buffers& b, int L, int NR, float* phys, const PolicySpec& p, const float* params,
                                 int n_params, int act_dim, const float* sigma, uint64_t noise_seed, int n_steps, float* obs, float* actions,
                                 float* rewards, uint8_t* flags, float* final_obs, float* mean, float* sample, hipStream_t s);
+// rsx_collect_gaussian.hip: the same collection under a state-dependent tanh-squashed Gaussian head (rsx_task_collect_gaussian): params
+// [n_params] with an output layer of 2 * act_dim units; cfg and out checked; log_std_out optional.  gaussian_lds_bytes: LDS of one
+// workgroup of that launch (Shared<L> and the wider image: the host refuses more than 64 KB)
+long long gaussian_lds_bytes(int L, int obs_dim, int act_dim, const PolicySpec& p);
+void launch_task_collect_gaussian(const Params& P, const Buffers& b, int L, int NR, float* phys, const PolicySpec& p, const float* params,
+                                  int n_params, int act_dim, const rsx_collect_gaussian_cfg& cfg, int n_steps, const rsx_collect_out& out,
+                                  float* log_std_out, hipStream_t s);
 // rsx_selfplay.hip: the same collection for VSS-v0 with yellow robot 0 driven by a second policy, the opponent, from the mirrored observation
 // (rsx_task_collect_selfplay).  p / params / sigma: the agent's, as above; opp / opp_params / opp_sigma: the opponent's (a shape of its own);
 // out: the agent's record, checked; sp: the opponent's, every member optional.  selfplay_lds_bytes: LDS of one workgroup of that launch
@@ -181,6 +191,18 @@ long long dpg_workspace_bytes(long long n_params_actor, long long n_params_criti
 void launch_dpg_gradient(const PolicySpec& actor, long long n_params_actor, const float* actor_params, const float* target_actor_params,
                          const PolicySpec& critic, long long n_params_critic, const float* critic_params, const float* target_critic_params,
                          int obs_dim, int act_dim, const rsx_dpg_in& in, const rsx_dpg_cfg& cfg, const rsx_dpg_out& out, hipStream_t s);
+// rsx_sac.hip: gradients of the soft actor-critic losses with respect to an MLP actor with a squashed Gaussian head (an output layer of
+// 2 * act_dim units), n_critics critics on [obs | action] and the log-temperature (rsx_task_sac_gradient).  The arguments as for
+// launch_dpg_gradient (no target actor; log_alpha: [1] on the device); in / cfg / out checked.  Six launches: the targets, the critics
+// (grid.y = critic), the actor's sample, each critic on (obs, sample) with its dQ/da (grid.y = critic), the actor's backward pass, the
+// reduce.  sac_grid / sac_workspace_bytes / sac_lds_bytes: as dpg_*
+enum : int { SAC_LAUNCH_TARGET = 0, SAC_LAUNCH_CRITIC = 1, SAC_LAUNCH_SAMPLE = 2, SAC_LAUNCH_QA = 3, SAC_LAUNCH_ACTOR = 4 };
+int sac_grid(long long n_rows, int max_workgroups);
+long long sac_lds_bytes(int launch, int obs_dim, int act_dim, const PolicySpec& actor, const PolicySpec& critic, int n_critics);
+long long sac_workspace_bytes(long long n_params_actor, long long n_params_critic, int n_critics, long long n_rows, int max_workgroups);
+void launch_sac_gradient(const PolicySpec& actor, long long n_params_actor, const float* actor_params, const PolicySpec& critic,
+                         long long n_params_critic, const float* critic_params, const float* target_critic_params, const float* log_alpha,
+                         int obs_dim, int act_dim, const rsx_dpg_in& in, const rsx_sac_cfg& cfg, const rsx_sac_out& out, hipStream_t s);
 // rsx_dpg_update.hip: the update phase around launch_dpg_gradient (rsx_replay_sample_rows, rsx_dpg_adam_step, rsx_task_dpg_update); every
 // argument checked by the caller.  One launch for the rows, two for the optimiser step (the norms of both groups, then Adam with the
 // Polyak step).  dpg_update_workspace_bytes: launch_dpg_update's workspace (rows_offset: where the int32 rows lie in it);

@@ -341,7 +341,7 @@ class VecFusedEnv(RenderMixin):
 
     def collect(self, policy, params, steps, log_std=None, noise_seed=None, iteration=0, return_final_obs=False,
                 critic=None, critic_params=None, gamma=0.99, lam=0.95, opponent=None, opponent_params=None, opponent_log_std=None,
-                team=False, opponent_team=False):
+                team=False, opponent_team=False, deterministic=False):
         """Advance the envs ``steps`` steps under an MLP policy in ONE launch and return the on-policy batch
         (``rsx_task_collect_policy``): what a PPO / A2C loop calls between two updates.
 
@@ -393,9 +393,18 @@ class VecFusedEnv(RenderMixin):
         critic on every seat's rows and runs GAE per (env, seat) with the shared reward and flags.
         ``rsoccer_amd.vec.policy.seat_rows(batch)`` turns such a batch into the ``[T, B * S, ...]`` mapping ``advantages()``,
         ``ppo_gradient()`` and ``ppo_update()`` take.  With both flags false nothing changes.
+
+        Soft actor-critic's actor (``rsx_task_collect_gaussian``): with ``policy`` an ``MLPGaussianPolicy`` — the output layer gives mean
+        and log-std per state — the head is ``log_std = clamp(raw, policy.log_std_min, policy.log_std_max)``, ``sample = mean +
+        exp(log_std) * eps`` (the same ``eps`` as above) and ``action = tanh(sample)``; ``deterministic=True`` takes ``action =
+        tanh(mean)`` without a draw.  The dict is the one above (``obs``, ``actions``, ``reward``, ``terminated``, ``truncated``,
+        ``next_obs``, ``final_obs`` on request) plus ``mean``, ``log_std``, ``sample`` ``[T, B, act_dim]`` and ``log_prob`` ``[T, B]``: the
+        density of the ACTION, tanh correction included (``rsoccer_amd.vec.policy.squashed_log_prob``, computed in torch).  ``ReplayBuffer.add()`` takes
+        it as it is.  ``log_std=``, ``critic=``, ``opponent=``, ``team=`` and ``opponent_team=`` are refused with this policy (a squashed
+        head for self-play seats is a different feature); ``deterministic`` is refused with every other policy unless it is ``False``.
         Capturable into a ``torch.cuda.CUDAGraph`` after ``enable_graph_capture()``: every replay draws fresh noise."""
         torch = self._torch
-        from rsoccer_amd.vec.policy import MLPPolicy
+        from rsoccer_amd.vec.policy import MLPGaussianPolicy, MLPPolicy
         if not isinstance(policy, MLPPolicy):
             raise ValueError("policy must be an rsoccer_amd.vec.policy.MLPPolicy")
         T = int(steps)
@@ -403,6 +412,17 @@ class VecFusedEnv(RenderMixin):
             raise ValueError(f"steps must be >= 1, got {steps}")
         if self.sim.act_dim != policy.act_dim or self.sim.obs_dim != policy.obs_dim:
             raise ValueError(f"the policy maps {policy.obs_dim} -> {policy.act_dim}, the env {self.sim.obs_dim} -> {self.sim.act_dim}")
+        if isinstance(policy, MLPGaussianPolicy):
+            for name, v in (("log_std", log_std), ("critic", critic), ("critic_params", critic_params), ("opponent", opponent),
+                            ("opponent_params", opponent_params), ("opponent_log_std", opponent_log_std)):
+                if v is not None:
+                    raise ValueError(f"{name} cannot be combined with an MLPGaussianPolicy (its head is its own)")
+            for name, v in (("team", team), ("opponent_team", opponent_team)):
+                if v:
+                    raise ValueError(f"{name} cannot be combined with an MLPGaussianPolicy (a squashed head for seats is a different feature)")
+            return self._collect_gaussian(policy, params, T, noise_seed, iteration, return_final_obs, bool(deterministic))
+        if deterministic is not False:
+            raise ValueError("deterministic is an MLPGaussianPolicy's keyword: a plain MLPPolicy is deterministic without log_std")
         if critic is not None:
             cp = self._critic_args(critic, critic_params, gamma, lam)   # (refused before anything is enqueued)
             return_final_obs = True
@@ -464,11 +484,7 @@ class VecFusedEnv(RenderMixin):
         ls, sigma = head(log_std, "log_std")
         ols, osigma = head(opponent_log_std, "opponent_log_std")
         if noise_seed is None:
-            m = (1 << 64) - 1   # splitmix64 of (seed, iteration), as _plan_sampler
-            z = (self._seed + 0x9E3779B97F4A7C15 * (int(iteration) + 1)) & m
-            z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
-            z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
-            noise_seed = z ^ (z >> 31)
+            noise_seed = self._collect_noise_seed(iteration)
         f32 = dict(dtype=torch.float32, device=dev)
         if team or opponent_team:
             op = None if opponent is None else device_params(opponent_params)
@@ -518,6 +534,50 @@ class VecFusedEnv(RenderMixin):
             out["log_prob"] = (-0.5 * z * z - ls - 0.9189385332046727).sum(-1)   # 0.5 * log(2 pi)
         if critic is not None:
             out.update(self._advantages(out, critic, cp, float(gamma), float(lam), False))
+        return out
+
+    def _collect_noise_seed(self, iteration):
+        """collect()'s default noise seed: splitmix64 of (seed, iteration), as _plan_sampler"""
+        m = (1 << 64) - 1
+        z = (self._seed + 0x9E3779B97F4A7C15 * (int(iteration) + 1)) & m
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+        return z ^ (z >> 31)
+
+    def _collect_gaussian(self, policy, params, T, noise_seed, iteration, return_final_obs, deterministic):
+        """collect()'s launch and batch under an MLPGaussianPolicy (rsx_task_collect_gaussian); policy, T and the keywords checked"""
+        torch = self._torch
+        from rsoccer_amd.vec.policy import squashed_log_prob
+        shape = tuple(np.shape(params))
+        if shape != (policy.num_params,):
+            raise ValueError(f"params must be [{policy.num_params}] (one policy, the output layer 2 * act_dim wide), got {shape}")
+        dev, B, OD, AD = self.device, self.num_envs, self.sim.obs_dim, self.sim.act_dim
+        if isinstance(params, torch.Tensor):
+            p = params.detach()
+            if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
+                p = p.to(device=dev, dtype=torch.float32).contiguous()
+        else:
+            p = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float32)).to(dev)
+        if noise_seed is None:
+            noise_seed = self._collect_noise_seed(iteration)
+        f32 = dict(dtype=torch.float32, device=dev)
+        obs = torch.empty((T, B, OD), **f32)
+        acts, mean, smp, ls = (torch.empty((T, B, AD), **f32) for _ in range(4))
+        rew = torch.empty((T, B), **f32)
+        flags = torch.empty((T, B), dtype=torch.uint8, device=dev)
+        fobs = torch.zeros((T, B, OD), **f32) if return_final_obs else None
+        rec = _lib.CollectOut(obs.data_ptr(), acts.data_ptr(), rew.data_ptr(), flags.data_ptr(), None if fobs is None else fobs.data_ptr(),
+                              mean.data_ptr(), smp.data_ptr())
+        cfg = _lib.CollectGaussianCfg(int(noise_seed) & 0xFFFFFFFFFFFFFFFF, policy.log_std_min, policy.log_std_max, int(deterministic), 0)
+        self.sim.task_collect_gaussian(policy.spec(), p.data_ptr(), cfg, T, rec, ls.data_ptr(), self._stream())
+        self._keep_plan = (p,)   # alive until the launch has consumed it
+        out = {"obs": obs, "actions": acts, "reward": rew, "terminated": (flags & 1).bool(), "truncated": (flags & 2).bool(),
+               "next_obs": self._t["obs"]}
+        if return_final_obs:
+            out["final_obs"] = fobs
+        out["mean"], out["log_std"], out["sample"] = mean, ls, smp
+        eps = (smp - mean) / ls.exp()   # (deterministic: 0, the density at the mode)
+        out["log_prob"] = squashed_log_prob(eps, ls, smp)
         return out
 
     def _collect_team(self, policy, p, ls, sigma, seats, opponent, op, ols, osigma, opp_seats, noise_seed, T, return_final_obs):
@@ -897,6 +957,133 @@ class VecFusedEnv(RenderMixin):
             res["target"], res["q"], res["target_noise"] = tgt, q, nz
             if actor:
                 res["action"] = pi
+        return res
+
+    def sac_gradient(self, data, policy, params, critic, critic_params, target_critic_params, log_alpha, rows=None, gamma=0.99,
+                     target_entropy=None, noise_seed=0, noise_step=0, max_workgroups=None, return_rows=False):
+        """Gradients of the soft actor-critic losses with respect to an ``MLPGaussianPolicy`` actor, its one or two Q critics and the
+        log-temperature on a minibatch of replayed transitions, in six launches (``rsx_task_sac_gradient``): what a SAC loop does per
+        gradient step before its three optimiser steps and the Polyak update of the target critics.
+
+        ``data``, ``rows``, ``critic`` / ``critic_params`` / ``target_critic_params`` ``[C, Pc]``, ``gamma``, ``noise_seed``,
+        ``noise_step`` (an int or an int64 device tensor ``[1]``) and ``max_workgroups`` are ``dpg_gradient``'s.  ``policy`` / ``params``
+        ``[P]``: the actor (there is no target actor; the log-std bounds are the policy's).  ``log_alpha``: ``[1]`` float32 on the
+        device, ``alpha = exp(log_alpha)`` read when the launches run.  ``target_entropy=None`` means ``-act_dim``.  The draws of
+        minibatch position ``t`` depend on ``(noise_seed, noise_step, t)`` only.  The losses and their float32 arithmetic are written out
+        in ``include/rsx.h``; the result bits depend on the inputs and ``max_workgroups`` only.
+
+        Returns fresh device tensors ``grad_params`` ``[P]``, ``grad_critic_params`` ``[C, Pc]``, ``grad_log_alpha`` ``[1]`` and
+        ``stats``: a dict of 0-d views (``_lib.SAC_STATS``; no synchronisation); with ``return_rows=True`` also ``target`` ``[M]``, ``q``
+        ``[C, M]``, ``action`` ``[M, act_dim]`` (the sample on ``obs``), ``log_prob`` ``[M]``, ``next_log_prob`` ``[M]``, ``eps``,
+        ``next_eps``, ``mean`` and ``log_std`` ``[M, act_dim]`` — zero for a skipped entry.  Touches nothing of the env, never
+        synchronises, capturable."""
+        torch = self._torch
+        from rsoccer_amd.vec.policy import MLPGaussianPolicy, MLPQCritic
+        if not isinstance(policy, MLPGaussianPolicy):
+            raise ValueError("policy must be an rsoccer_amd.vec.policy.MLPGaussianPolicy")
+        if not isinstance(critic, MLPQCritic):
+            raise ValueError("critic must be an rsoccer_amd.vec.policy.MLPQCritic")
+        OD, AD, dev = self.sim.obs_dim, self.sim.act_dim, self.device
+        if policy.obs_dim != OD or policy.act_dim != AD:
+            raise ValueError(f"the policy maps {policy.obs_dim} -> {policy.act_dim}, the env {OD} -> {AD}")
+        if critic.state_dim != OD or critic.action_dim != AD:
+            raise ValueError(f"the critic reads ({critic.state_dim}, {critic.action_dim}) floats, the env has ({OD}, {AD})")
+        gamma = float(gamma)
+        if not (np.isfinite(gamma) and 0.0 <= gamma <= 1.0):
+            raise ValueError(f"gamma must be in [0, 1], got {gamma}")
+        te = -float(AD) if target_entropy is None else float(target_entropy)
+        if not np.isfinite(te):
+            raise ValueError(f"target_entropy must be finite, got {target_entropy}")
+        mw = 0 if max_workgroups is None else int(max_workgroups)
+        if mw < 0 or (max_workgroups is not None and mw < 1):
+            raise ValueError(f"max_workgroups must be >= 1 or None, got {max_workgroups}")
+
+        def need(name, t, shape, dtypes=(torch.float32,)):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
+            if tuple(t.shape) != tuple(shape):
+                raise ValueError(f"{name} must be {list(shape)}, got {list(t.shape)}")
+            if t.dtype not in dtypes:
+                raise ValueError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+            if t.device != dev:
+                raise ValueError(f"{name} is on {t.device}, the env on {dev}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+            return t.detach()
+
+        for key in ("obs", "actions", "reward", "next_obs", "terminated"):
+            if key not in data:
+                raise ValueError(f"data lacks {key!r}")
+        obs = data["obs"]
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or obs.shape[0] < 1 or obs.shape[1] != OD:
+            raise ValueError(f"data['obs'] must be a [N >= 1, {OD}] tensor, got {tuple(np.shape(obs))}")
+        N = int(obs.shape[0])
+        obs = need("data['obs']", obs, (N, OD))
+        act = need("data['actions']", data["actions"], (N, AD))
+        rew = need("data['reward']", data["reward"], (N,))
+        nxt = need("data['next_obs']", data["next_obs"], (N, OD))
+        term = need("data['terminated']", data["terminated"], (N,), (torch.bool, torch.uint8))
+        p = need("params", params, (policy.num_params,))
+        if not isinstance(critic_params, torch.Tensor) or critic_params.dim() != 2 or critic_params.shape[0] not in (1, 2):
+            raise ValueError(f"critic_params must be a [C, {critic.num_params}] tensor with C in (1, 2), got {tuple(np.shape(critic_params))}")
+        C = int(critic_params.shape[0])
+        cp = need("critic_params", critic_params, (C, critic.num_params))
+        tcp = need("target_critic_params", target_critic_params, (C, critic.num_params))
+        la = need("log_alpha", log_alpha, (1,))
+        step_ptr, step = None, 0
+        if isinstance(noise_step, torch.Tensor):
+            step_t = need("noise_step", noise_step, (1,), (torch.int64,))
+            step_ptr = step_t.data_ptr()
+        else:
+            step_t, step = None, int(noise_step)
+        if rows is None:
+            r, M = None, N
+        else:
+            if not isinstance(rows, torch.Tensor) or not rows.is_cuda:   # host data: checked, then uploaded
+                host = np.asarray(rows.numpy() if isinstance(rows, torch.Tensor) else rows)
+                if host.ndim != 1 or host.size < 1 or host.dtype.kind not in "iu":
+                    raise ValueError(f"rows must be a 1-D integer array with at least one entry, got shape {host.shape} dtype {host.dtype}")
+                if int(host.min()) < 0 or int(host.max()) >= N:
+                    raise ValueError(f"rows must lie in [0, {N}), got {int(host.min())} .. {int(host.max())}")
+                rows = torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32)).to(dev)
+            if rows.dim() != 1 or rows.shape[0] < 1:
+                raise ValueError(f"rows must be 1-D with at least one entry, got {list(rows.shape)}")
+            if rows.dtype not in (torch.int32, torch.int64):
+                raise ValueError(f"rows must be torch.int32 or torch.int64, got {rows.dtype}")
+            if rows.device != dev:
+                raise ValueError(f"rows is on {rows.device}, the env on {dev}")
+            r = rows.to(torch.int32) if rows.dtype == torch.int64 else rows
+            if not r.is_contiguous():
+                raise ValueError("rows must be contiguous")
+            M = int(r.shape[0])
+        aspec, cspec = policy.spec(), critic.spec()
+        f32 = dict(dtype=torch.float32, device=dev)
+        # the workspace, cached per (shape, C, M, max_workgroups): calls on one stream are ordered, so they may share it
+        key = (policy.layers, policy.hidden, critic.layers, critic.hidden, C, M, mw)
+        cache = self.__dict__.setdefault("_sac_ws", {})
+        ws = cache.get(key)
+        if ws is None:
+            ws = cache[key] = torch.empty(((self.sim.sac_gradient_workspace(aspec, cspec, C, M, mw) + 3) // 4,), **f32)
+        ga = torch.empty((policy.num_params,), **f32)
+        gc = torch.empty((C, critic.num_params), **f32)
+        gl = torch.empty((1,), **f32)
+        stats = torch.empty((len(_lib.SAC_STATS),), **f32)
+        per = {}
+        if return_rows:
+            per = {"target": (M,), "q": (C, M), "action": (M, AD), "log_prob": (M,), "next_log_prob": (M,), "eps": (M, AD),
+                   "next_eps": (M, AD), "mean": (M, AD), "log_std": (M, AD)}
+            per = {k: torch.empty(shape, **f32) for k, shape in per.items()}
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731  (a bool tensor is one byte per element, 0 or 1)
+        inp = _lib.DpgIn(ptr(obs), ptr(act), ptr(rew), ptr(nxt), ptr(term), ptr(r), N, M)
+        cfg = _lib.SacCfg(step_ptr, int(noise_seed) & 0xFFFFFFFFFFFFFFFF, step, gamma, te, policy.log_std_min, policy.log_std_max, C, mw)
+        out = _lib.SacOut(ptr(ga), ptr(gc), ptr(gl), ptr(stats),
+                          *(ptr(per.get(k)) for k in ("target", "q", "action", "log_prob", "next_log_prob", "eps", "next_eps", "mean", "log_std")),
+                          ptr(ws))
+        self.sim.task_sac_gradient(aspec, ptr(p), cspec, ptr(cp), ptr(tcp), ptr(la), inp, cfg, out, self._stream())
+        self._keep_sac = (r, step_t, term)   # the call's own tensors: alive until the launches have consumed them
+        res = {"grad_params": ga, "grad_critic_params": gc, "grad_log_alpha": gl,
+               "stats": {name: stats[k] for k, name in enumerate(_lib.SAC_STATS)}}
+        res.update(per)
         return res
 
     def dpg_update(self, buf, policy, params, target_params, critic, critic_params, target_critic_params, opt, grad_steps=8,

@@ -5,8 +5,11 @@
 ``torch.nn.utils.parameters_to_vector`` of ``Sequential(Linear(obs_dim, hidden), act, [Linear(hidden, hidden), act,]
 Linear(hidden, act_dim))``: ``W1 [hidden, obs_dim]`` row-major, ``b1``, (``W2``, ``b2``,) ``Wo [act_dim, hidden]``, ``bo``.  Many
 parameter vectors of one shape — a population — form the ``[K, P]`` tensor the env call takes."""
+import math
+
 from rsoccer_amd import _lib
 
+_HALF_LOG_2PI, _LOG_2 = 0.5 * math.log(2.0 * math.pi), math.log(2.0)
 _HIDDEN_ACTS = {"relu": _lib.ACT_RELU, "tanh": _lib.ACT_TANH}
 _OUT_ACTS = {"clip": _lib.ACT_CLIP, "tanh": _lib.ACT_TANH}
 
@@ -155,6 +158,63 @@ class MLPQCritic(MLPPolicy):
         if obs.shape[-1] != self.state_dim or action.shape[-1] != self.action_dim:
             raise ValueError(f"expected obs [..., {self.state_dim}] and action [..., {self.action_dim}], got {list(obs.shape)} and {list(action.shape)}")
         return super().forward(torch.cat([obs, action.to(obs.device)], dim=-1), params, dtype=dtype)
+
+
+class MLPGaussianPolicy(MLPPolicy):
+    """``obs_dim -> hidden [-> hidden] -> 2 * act_dim``: soft actor-critic's actor, a state-dependent Gaussian squashed by tanh
+    (``rsx_task_collect_gaussian``; include/rsx.h states the head).  ``MLPPolicy``'s layout with an output layer of ``2 * act_dim``
+    units: rows ``[0, act_dim)`` of ``Wo`` / ``bo`` are the mean ``mu``, rows ``[act_dim, 2 * act_dim)`` the raw log-std, so the flat
+    parameters equal ``parameters_to_vector`` of ``Sequential(Linear(obs_dim, hidden), act, [Linear(hidden, hidden), act,]
+    Linear(hidden, 2 * act_dim))`` with ``mu, raw = out.chunk(2, -1)``.  ``log_std = clamp(raw, log_std_min, log_std_max)``,
+    ``u = mu + exp(log_std) * eps``, ``action = tanh(u)``.  ``act_dim <= 8`` and finite bounds with ``log_std_min < log_std_max``;
+    anything else: ValueError."""
+
+    def __init__(self, obs_dim, act_dim, hidden=64, layers=2, hidden_act="tanh", log_std_min=-20.0, log_std_max=2.0):
+        super().__init__(obs_dim, act_dim, hidden=hidden, layers=layers, hidden_act=hidden_act, out_act="tanh")   # (checks the shape)
+        self.out_act = "none"
+        if self.act_dim > 8:
+            raise ValueError(f"act_dim must be <= 8, got {act_dim}")
+        lo, hi = float(log_std_min), float(log_std_max)
+        if not (math.isfinite(lo) and math.isfinite(hi) and lo < hi):
+            raise ValueError(f"log_std_min and log_std_max must be finite with log_std_min < log_std_max, got {log_std_min}, {log_std_max}")
+        self.log_std_min, self.log_std_max = lo, hi
+
+    @property
+    def shapes(self):
+        out = super().shapes
+        out[-2:] = [(2 * self.act_dim, self.hidden), (2 * self.act_dim,)]
+        return out
+
+    def spec(self):
+        """the rsx_policy_mlp of this shape, with out_act = RSX_ACT_NONE"""
+        return _lib.PolicyMLP(self.layers, self.hidden, _HIDDEN_ACTS[self.hidden_act], _lib.ACT_NONE)
+
+    def _torch_acts(self):
+        hid, _ = super()._torch_acts()
+        return hid, (lambda v: v)
+
+    def forward(self, obs, params, dtype=None):
+        """The reference forward pass in torch: ``(mu, log_std)``, each ``[..., act_dim]`` in ``dtype`` (default float64), the
+        log-std clamped (``torch.clamp``: its gradient is 1 inside and at the bounds, 0 outside).  For tests."""
+        mu, raw = super().forward(obs, params, dtype=dtype).chunk(2, -1)
+        return mu, raw.clamp(self.log_std_min, self.log_std_max)
+
+    def sample(self, obs, params, eps, dtype=None):
+        """``(action, log_prob, u)`` for the standard normals ``eps [..., act_dim]`` by include/rsx.h's formulas, in torch:
+        ``u = mu + exp(log_std) * eps``, ``action = tanh(u)`` and ``log_prob [...]`` with the tanh correction in its stable form
+        ``2 (ln 2 - u - softplus(-2 u))``."""
+        mu, ls = self.forward(obs, params, dtype=dtype)
+        eps = eps.to(device=mu.device, dtype=mu.dtype)
+        u = mu + ls.exp() * eps
+        return u.tanh(), squashed_log_prob(eps, ls, u), u
+
+
+def squashed_log_prob(eps, log_std, u):
+    """``sum_k [-0.5 eps_k^2 - log_std_k - 0.5 ln(2 pi) - 2 (ln 2 - u_k - softplus(-2 u_k))]`` over the last axis, with
+    ``softplus(z) = max(z, 0) + log1p(exp(-|z|))`` written out: the log-density of ``tanh(u)`` for ``u = mu + exp(log_std) * eps``."""
+    z = -2.0 * u
+    softplus = z.clamp(min=0.0) + (-z.abs()).exp().log1p()
+    return (-0.5 * eps * eps - log_std - _HALF_LOG_2PI - 2.0 * (_LOG_2 - u - softplus)).sum(-1)
 
 
 _SEAT_KEYS = ("obs", "actions", "mean", "sample", "log_prob", "final_obs", "value", "advantage", "return")
