@@ -1,6 +1,7 @@
 """Soft actor-critic on VSS-v0 with the rollouts collected in one launch under the actor itself.
 
     python examples/sac_vss.py [--envs 256] [--steps 16] [--updates 10] [--grad-steps 8] [--batch 256] [--torch]
+                               [--device-update] [--graph]
 
 One update: env.collect(MLPGaussianPolicy, ...) advances the envs `steps` steps under the current actor — mean and log-std per state,
 the sample squashed by tanh, all inside the launch (rsx_task_collect_gaussian) — ReplayBuffer.add() stores the T * B transitions with
@@ -8,8 +9,10 @@ their true successors, and `grad-steps` gradient steps follow.  A gradient step:
 device, env.sac_gradient(...) returns the gradients of the critic loss, the actor loss and the temperature loss in six launches
 (rsx_task_sac_gradient), three torch Adam optimisers step on the flat tensors (the leaves), and lerp_ moves the target critics.
 --torch runs the same losses in torch autograd instead (sac_losses below, on the same flat vectors: MLPGaussianPolicy.sample and
-MLPQCritic.forward are plain torch; what tools/bench_sac_grad.py times the engine against).  A demonstration of the call pattern, not a
-tuned trainer."""
+MLPQCritic.forward are plain torch; what tools/bench_sac_grad.py times the engine against).  --device-update replaces the whole
+gradient-step loop by ONE call, env.sac_update with a SACOptimizer (rows from the engine's generator, the three Adam steps and the Polyak
+step on the device); --graph captures collect + add + sac_update once and replays them (device_update below).  A demonstration of the
+call pattern, not a tuned trainer."""
 import argparse
 import os
 import sys
@@ -44,6 +47,53 @@ def sac_losses(pol, p_actor, qnet, p_critics, t_critics, log_alpha, data, idx, g
     return loss_q, loss_pi, loss_alpha, logp.detach().mean()
 
 
+def device_update(args):
+    """--device-update: the loop body is collect, buf.add, env.sac_update — rows drawn by the engine's generator, Adam on the three
+    groups and the Polyak step on the device, no interpreter between the gradient steps.  --graph: those three calls captured once on a
+    device-keyed env and replayed; the optimiser's step count on the device keys every replay's rows and noise."""
+    from rsoccer_amd.vec.optim import SACOptimizer
+    torch.manual_seed(args.seed)
+    env = VecVSSEnv(args.envs, device=0, seed=args.seed)
+    dev, OD, AD = env.device, env.sim.obs_dim, env.sim.act_dim
+    pol = MLPGaussianPolicy(OD, AD, hidden=64, layers=2, hidden_act="tanh")
+    qnet = MLPQCritic(OD, AD, hidden=64, layers=2, hidden_act="tanh")
+    p_actor = pol.from_module(mlp(OD, 2 * AD)).to(dev)   # plain tensors: nothing here is differentiated by autograd
+    p_critics = torch.stack([qnet.from_module(mlp(OD + AD, 1)) for _ in range(2)]).to(dev)
+    t_critics, log_alpha = p_critics.clone(), torch.zeros(1, device=dev)
+    opt = SACOptimizer(pol, qnet, 2, device=dev, lr_actor=args.lr, lr_critic=args.lr, lr_alpha=args.lr, tau=args.tau)
+    buf = ReplayBuffer(args.capacity, OD, AD, dev)
+    env.reset()
+    if args.graph:
+        env.enable_graph_capture()
+
+    def iteration():
+        batch = env.collect(pol, p_actor, args.steps, noise_seed=args.seed + 2, return_final_obs=True)
+        buf.add(batch)
+        out = env.sac_update(buf, pol, p_actor, qnet, p_critics, t_critics, log_alpha, opt, grad_steps=args.grad_steps, batch_size=args.batch,
+                             gamma=args.gamma, seed=args.seed + 1)
+        return batch["reward"].mean(), out["stats"]
+
+    graph = None
+    for update in range(args.updates):
+        t0 = time.perf_counter()
+        if graph is not None:
+            graph.replay()
+        else:
+            reward, stats = iteration()   # (eager; with --graph also the warm-up before the capture)
+        torch.cuda.synchronize()
+        m = env.metrics()
+        print(f"update {update}: mean reward / step {float(reward):+.5f}, episodes {m['episodes']}, goals for / against "
+              f"{m['goals_for']} / {m['goals_against']}, buffer {int(buf.fill)} rows, gradient steps {int(opt.steps)}, loss_q "
+              f"{float(stats['loss_q0'][-1] + stats['loss_q1'][-1]):.5f}, loss_pi {float(stats['loss_pi'][-1]):+.5f}, alpha "
+              f"{float(log_alpha.exp()):.4f}, log_prob {float(stats['log_prob'][-1]):+.3f}; collect + add + {args.grad_steps} gradient steps "
+              f"{(time.perf_counter() - t0) * 1e3:.1f} ms")
+        if args.graph and graph is None:   # captured once (a capture records, it runs nothing): every further update is one replay
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                reward, stats = iteration()
+    env.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=256)
@@ -57,7 +107,13 @@ def main():
     ap.add_argument("--tau", type=float, default=0.005)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--torch", action="store_true", help="the same losses in torch autograd")
+    ap.add_argument("--device-update", action="store_true", help="the whole update phase in one call: env.sac_update with a SACOptimizer")
+    ap.add_argument("--graph", action="store_true", help="--device-update with collect + add + sac_update captured once and replayed")
     args = ap.parse_args()
+    if args.device_update or args.graph:
+        if args.torch:
+            ap.error("--device-update / --graph and --torch exclude each other")
+        return device_update(args)
 
     torch.manual_seed(args.seed)
     env = VecVSSEnv(args.envs, device=0, seed=args.seed)

@@ -1265,6 +1265,120 @@ int rsx_task_dpg_update(rsx_sim* h, const rsx_policy_mlp* actor, float* actor_pa
                         const rsx_dpg_cfg* cfg, const rsx_dpg_update_cfg* u, const rsx_dpg_adam_cfg* adam, const rsx_dpg_adam_state* st,
                         float* stats_dev, void* workspace, void* stream);
 
+/* ---- the soft actor-critic update phase on the device: sample, Adam, alpha, Polyak (additive extension of ABI 6) --------------------
+ * What a SAC trainer does around rsx_task_sac_gradient, per gradient step: draw the minibatch's rows, clip and step the critics and the
+ * actor with Adam, step the log-temperature, and move the target critics — the TD3 section's twin, stream-ordered and keyed by counters
+ * that live on the device, so that rsx_task_collect_gaussian + the ring's writes + rsx_task_sac_update captured once is one whole
+ * off-policy iteration per replay.  rsx_sac_adam_step takes no handle: it runs on the thread's current device.  Every call is
+ * stream-ordered, never synchronises, never allocates and is capturable; invalid arguments are refused with RSX_ERR_ARG before anything
+ * is enqueued (rsx_last_error says why); no float atomics: the result bits are a function of the inputs (and, for rsx_task_sac_update,
+ * of max_workgroups) alone.  The rows are rsx_replay_sample_rows' (domain word 11); this phase draws nothing else of its own.
+ *
+ * rsx_sac_adam_step:  the optimiser step of SAC — three torch.optim.Adam (no amsgrad, no weight decay), one on the critics' flat tensor
+ * [C * Pc], one on the actor's [Pa] and one on log_alpha [1], the first two each behind its own torch.nn.utils.clip_grad_norm_, and the
+ * Polyak step of the target critics — in two launches (the norms, then the update).  There is no target actor.
+ *   counters   int64 [4] device memory, part of the optimiser state (zero at the start of training): */
+#define RSX_SAC_T_CRITIC 0   /* the critics' Adam step count t */
+#define RSX_SAC_T_ACTOR  1   /* the actor's: it advances on steps with a grad_actor only */
+#define RSX_SAC_T_ALPHA  2   /* log_alpha's: it advances on steps with a grad_log_alpha only */
+#define RSX_SAC_STEPS    3   /* gradient steps finished (calls of rsx_sac_adam_step): the key of the row draws and the sampling noise */
+/*   groups   the critics always step.  The actor steps when io->grad_actor != NULL; a call without it leaves the actor's parameters,
+ *          its moments and counters[RSX_SAC_T_ACTOR] exactly as they were.  log_alpha steps when io->grad_log_alpha != NULL; a call
+ *          without it (a fixed temperature) leaves log_alpha, m_alpha, v_alpha and counters[RSX_SAC_T_ALPHA] exactly as they were.
+ *   per group, rsx_dpg_adam_step's arithmetic — rsx_adam_step's — word for word, on that group's tensor alone:
+ *     norm   = (float)sqrt(sum g^2), the float64 reduction in rsx_adam_step's fixed order (G = min(ceil(n / 256), 64) workgroups of the
+ *              GROUP's n; each g widened, g * g exact); the critics and the actor only
+ *     coef   = min(1, max_grad_norm / (norm + 1e-6f)) in float32;  max_grad_norm <= 0: coef = 1 (no clipping).  log_alpha is never
+ *              clipped: its coef is 1 whatever the other groups' norms are
+ *     t := t + 1 (the group's own);  bc1 = 1 - beta1^t, bc2 = 1 - beta2^t in float64 from the device's t, beta^t by squaring
+ *     g' = g * coef;   m = b1 * m + omb1 * g';   v = b2 * v + (omb2 * g') * g';   p = p - step * (m / (sqrtf(v) / s2 + eps))
+ *              in float32, every operation rounded, with b = (float)beta, omb = (float)(1.0 - beta), step = (float)((double)lr / bc1),
+ *              s2 = (float)sqrt(bc2).  A gradient entry that is 0 (of either sign) while its m is 0 leaves its parameter as it was.
+ *     lr     the group's: lr_critic / lr_actor / lr_alpha, or with the matching *_dev != NULL the float it points to, read on the device.
+ *   Polyak   with io->update_targets != 0, after the Adam step of the same call, on the NEW parameters, per entry of the target critics:
+ *          d = p - targ;  targ = targ + tau * d   in float32, each of the three operations rounded.  With update_targets == 0 the
+ *          targets are neither read nor written.
+ *   counters[RSX_SAC_STEPS] advances by one per call.
+ *   stats  [4] or NULL: the critics' norm before the clip; the actor's (0.0f without an actor step); log_alpha after the step; 1.0f
+ *          when the targets moved, else 0.0f.
+ *   workspace   RSX_SAC_ADAM_WORKSPACE_BYTES, 8-byte aligned.
+ * Refused: a null cfg, st, io, counters, workspace, critic array (parameters, gradient, m, v), actor array (parameters, m, v) or
+ * log_alpha, m_alpha, v_alpha; a size < 1 or above 2^31 - 1; lr_actor, lr_critic, lr_alpha or eps negative or non-finite; a beta
+ * outside [0, 1); max_grad_norm non-finite; tau outside [0, 1] or non-finite; update_targets != 0 with a null target_critic_params. */
+#define RSX_SAC_ADAM_WORKSPACE_BYTES 2048
+typedef struct rsx_sac_adam_cfg {
+    double       beta1;          /* in [0, 1) */
+    double       beta2;          /* in [0, 1) */
+    const float* lr_actor_dev;   /* [1] device memory, or NULL = lr_actor */
+    const float* lr_critic_dev;  /* [1] device memory, or NULL = lr_critic */
+    const float* lr_alpha_dev;   /* [1] device memory, or NULL = lr_alpha */
+    float        lr_actor;       /* >= 0, finite */
+    float        lr_critic;      /* >= 0, finite */
+    float        lr_alpha;       /* >= 0, finite */
+    float        eps;            /* >= 0, finite */
+    float        max_grad_norm;  /* <= 0: no clipping; else the bound of the critics' norm and of the actor's, each on its own */
+    float        tau;            /* in [0, 1] */
+} rsx_sac_adam_cfg;
+typedef struct rsx_sac_adam_state {
+    float*   m_actor;     /* [n_actor] */
+    float*   v_actor;
+    float*   m_critic;    /* [n_critic] */
+    float*   v_critic;
+    float*   m_alpha;     /* [1] */
+    float*   v_alpha;
+    int64_t* counters;    /* [4], RSX_SAC_* */
+    int64_t  n_actor;     /* Pa */
+    int64_t  n_critic;    /* C * Pc */
+} rsx_sac_adam_state;
+typedef struct rsx_sac_adam_io {
+    float*       actor_params;          /* [n_actor]   updated in place with a grad_actor   required */
+    float*       critic_params;         /* [n_critic]  updated in place   required */
+    float*       target_critic_params;  /* [n_critic]  required with update_targets */
+    float*       log_alpha;             /* [1]         updated in place with a grad_log_alpha   required */
+    const float* grad_actor;            /* [n_actor] or NULL: no actor step */
+    const float* grad_critic;           /* [n_critic]  required */
+    const float* grad_log_alpha;        /* [1] or NULL: a fixed temperature */
+    float*       stats;                 /* [4] or NULL */
+    void*        workspace;             /* RSX_SAC_ADAM_WORKSPACE_BYTES   required */
+    int32_t      update_targets;        /* != 0: the Polyak step */
+} rsx_sac_adam_io;
+int rsx_sac_adam_step(const rsx_sac_adam_cfg* cfg, const rsx_sac_adam_state* st, const rsx_sac_adam_io* io, void* stream);
+/* rsx_task_sac_update:  the whole update phase in one call.  For j = 0 .. grad_steps - 1 it enqueues, in this order:
+ * rsx_replay_sample_rows(m = in->n_rows, n_batch_rows = in->n_batch_rows, fill / fill_dev = u's, seed = u->seed, step_dev = the DEVICE's
+ * counters[RSX_SAC_STEPS]) into the workspace;  rsx_task_sac_gradient on those rows with noise_step_dev = the same counter
+ * (cfg->noise_step and cfg->noise_step_dev are ignored; cfg->noise_seed keys the sampling noise);  rsx_sac_adam_step with
+ * update_targets = 1, all three gradients when u->learn_alpha != 0 and without grad_log_alpha otherwise.  Every step is an actor step
+ * and moves the targets, so every call — eager, captured or replayed — has the same launch sequence (nine launches per gradient step:
+ * one row draw, the gradient's six, the optimiser's two).  The results equal that sequence of calls bit for bit.
+ *   the handle, actor, critic, in, cfg    as for rsx_task_sac_gradient; in->rows must be NULL, in->n_rows is the minibatch size m.
+ *   the four parameter tensors   actor, critics, target critics and log_alpha [1]: updated in place.  Nothing `in` points to is written.
+ *   stats_dev   [grad_steps][RSX_SAC_UPDATE_STATS]: rsx_task_sac_gradient's twelve, then rsx_sac_adam_step's four
+ *   workspace   rsx_sac_update_workspace bytes, 16-byte aligned: rsx_task_sac_gradient's for m rows, the rows, the three gradients and
+ *               the optimiser's partials.  rows_offset_out (or NULL): where in it the int32 rows [m] of the last step lie.
+ *   an empty ring   with a device fill of 0 every row is -1 and skipped; the critics' and the actor's gradients are +0 everywhere and
+ *               rsx_task_sac_gradient's grad_log_alpha is -0.0f (minus a sum of nothing: skipped entries add neither logp nor
+ *               target_entropy), which Adam treats as 0: no PARAMETER moves, log_alpha included (a zero gradient on a zero moment
+ *               leaves its parameter alone; with moments from earlier steps Adam goes on as torch's would); the four counters
+ *               advance and the target critics take their Polyak steps as always.
+ * Refused: everything rsx_replay_sample_rows, rsx_task_sac_gradient and rsx_sac_adam_step refuse; a null u, stats_dev or workspace; a
+ * non-NULL in->rows; grad_steps < 1; a negative u->fill with fill_dev == NULL; state sizes (st->n_actor, st->n_critic) that are not Pa
+ * and C * Pc.
+ * Not here: delayed actor or target steps, prioritised or n-step replay. */
+#define RSX_SAC_UPDATE_STATS 16
+typedef struct rsx_sac_update_cfg {
+    const int64_t* fill_dev;      /* the ring's fill count on the device, or NULL = fill */
+    uint64_t       seed;          /* the row draws' key */
+    int64_t        fill;          /* >= 0 */
+    int32_t        grad_steps;    /* >= 1 */
+    int32_t        learn_alpha;   /* != 0: log_alpha is stepped; 0: a fixed temperature */
+} rsx_sac_update_cfg;
+int rsx_sac_update_workspace(const rsx_sim* h, const rsx_policy_mlp* actor, const rsx_policy_mlp* critic, int n_critics, int64_t n_rows,
+                             int max_workgroups, int64_t* bytes_out, int64_t* rows_offset_out);
+int rsx_task_sac_update(rsx_sim* h, const rsx_policy_mlp* actor, float* actor_params_dev, const rsx_policy_mlp* critic,
+                        float* critic_params_dev, float* target_critic_params_dev, float* log_alpha_dev, const rsx_dpg_in* in,
+                        const rsx_sac_cfg* cfg, const rsx_sac_update_cfg* u, const rsx_sac_adam_cfg* adam, const rsx_sac_adam_state* st,
+                        float* stats_dev, void* workspace, void* stream);
+
 /* Debugging aid: number of non-finite floats in the state rows and, with a task attached, in the
  * observations, rewards and info rows.  Synchronises `stream`.  With RSX_DEBUG_FINITE=1 in the
  * environment every stepping call (rsx_step_dev, rsx_task_step, rsx_task_step_n, rsx_task_rollout, rsx_task_collect_policy)

@@ -59,6 +59,7 @@ SYMBOLS = (
     "rsx_dpg_gradient_workspace", "rsx_task_dpg_gradient",
     "rsx_sac_gradient_workspace", "rsx_task_sac_gradient",
     "rsx_replay_sample_rows", "rsx_dpg_adam_step", "rsx_dpg_update_workspace", "rsx_task_dpg_update",
+    "rsx_sac_adam_step", "rsx_sac_update_workspace", "rsx_task_sac_update",
 )
 # activations of rsx_policy_mlp (include/rsx.h: RSX_ACT_*)
 ACT_RELU, ACT_TANH, ACT_CLIP = 0, 1, 2
@@ -264,6 +265,44 @@ class DpgUpdateCfg(C.Structure):
     _fields_ = [("fill_dev", C.c_void_p), ("seed", C.c_uint64), ("fill", C.c_int64), ("grad_steps", C.c_int32), ("policy_delay", C.c_int32)]
 
 
+# the soft actor-critic update phase (include/rsx.h: rsx_sac_adam_step, rsx_task_sac_update)
+SAC_ADAM_WORKSPACE_BYTES = 2048
+# the slots of rsx_sac_adam_state.counters (RSX_SAC_*), of rsx_sac_adam_io.stats, and of one row of rsx_task_sac_update's stats
+SAC_COUNTERS = ("t_critic", "t_actor", "t_alpha", "steps")
+SAC_ADAM_STATS = ("grad_norm_critic", "grad_norm_actor", "log_alpha", "targets_moved")
+SAC_UPDATE_STATS = SAC_STATS + SAC_ADAM_STATS
+
+
+class SacAdamCfg(C.Structure):
+    """rsx_sac_adam_cfg (include/rsx.h): the betas as doubles, each group's lr (actor, critics, log_alpha) by value or as a device
+    address (None = by value), eps, the bound of the critics' and of the actor's own gradient norm (<= 0: none) and the Polyak step's tau"""
+    _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("lr_actor_dev", C.c_void_p), ("lr_critic_dev", C.c_void_p),
+                ("lr_alpha_dev", C.c_void_p), ("lr_actor", C.c_float), ("lr_critic", C.c_float), ("lr_alpha", C.c_float), ("eps", C.c_float),
+                ("max_grad_norm", C.c_float), ("tau", C.c_float)]
+
+
+class SacAdamState(C.Structure):
+    """rsx_sac_adam_state (include/rsx.h): m and v of the actor's and the critics' flat tensors and of log_alpha, the int64 counters [4]
+    and the two sizes; device addresses"""
+    _fields_ = [("m_actor", C.c_void_p), ("v_actor", C.c_void_p), ("m_critic", C.c_void_p), ("v_critic", C.c_void_p),
+                ("m_alpha", C.c_void_p), ("v_alpha", C.c_void_p), ("counters", C.c_void_p), ("n_actor", C.c_int64), ("n_critic", C.c_int64)]
+
+
+class SacAdamIo(C.Structure):
+    """rsx_sac_adam_io (include/rsx.h): the actor, the critics, the target critics and log_alpha (updated in place), the gradients
+    (grad_actor None: no actor step; grad_log_alpha None: a fixed temperature), the optional stats [4], the workspace and whether the
+    targets move; device addresses"""
+    _fields_ = [("actor_params", C.c_void_p), ("critic_params", C.c_void_p), ("target_critic_params", C.c_void_p), ("log_alpha", C.c_void_p),
+                ("grad_actor", C.c_void_p), ("grad_critic", C.c_void_p), ("grad_log_alpha", C.c_void_p), ("stats", C.c_void_p),
+                ("workspace", C.c_void_p), ("update_targets", C.c_int32)]
+
+
+class SacUpdateCfg(C.Structure):
+    """rsx_sac_update_cfg (include/rsx.h): the ring's fill count (by device address, or None and by value), the row draws' seed, the
+    gradient steps of the call and whether log_alpha is stepped"""
+    _fields_ = [("fill_dev", C.c_void_p), ("seed", C.c_uint64), ("fill", C.c_int64), ("grad_steps", C.c_int32), ("learn_alpha", C.c_int32)]
+
+
 class DevView(C.Structure):
     _fields_ = [("num_envs", C.c_int32), ("n_robots", C.c_int32), ("state_dim", C.c_int32),
                 ("cmd_dim", C.c_int32), ("state", C.c_void_p), ("cmds", C.c_void_p), ("row_stride", C.c_int32)]
@@ -395,6 +434,11 @@ def load():
                                              C.POINTER(C.c_int64)]
     lib.rsx_task_dpg_update.argtypes = [vp, C.POINTER(PolicyMLP), vp, vp, C.POINTER(PolicyMLP), vp, vp, C.POINTER(DpgIn), C.POINTER(DpgCfg),
                                         C.POINTER(DpgUpdateCfg), C.POINTER(DpgAdamCfg), C.POINTER(DpgAdamState), vp, vp, vp]
+    lib.rsx_sac_adam_step.argtypes = [C.POINTER(SacAdamCfg), C.POINTER(SacAdamState), C.POINTER(SacAdamIo), vp]
+    lib.rsx_sac_update_workspace.argtypes = [vp, C.POINTER(PolicyMLP), C.POINTER(PolicyMLP), ip, C.c_int64, ip, C.POINTER(C.c_int64),
+                                             C.POINTER(C.c_int64)]
+    lib.rsx_task_sac_update.argtypes = [vp, C.POINTER(PolicyMLP), vp, C.POINTER(PolicyMLP), vp, vp, vp, C.POINTER(DpgIn), C.POINTER(SacCfg),
+                                        C.POINTER(SacUpdateCfg), C.POINTER(SacAdamCfg), C.POINTER(SacAdamState), vp, vp, vp]
     lib.rsx_physics_defaults.argtypes = [ip, vp]
     lib.rsx_physics_derive.argtypes = [ip, ip, vp, vp]
     lib.rsx_physics_enable.argtypes = [vp, vp]
@@ -474,6 +518,15 @@ def replay_sample_rows(rows_ptr, m, n_batch_rows, fill, fill_ptr, seed, step, st
 def dpg_adam_step(cfg, state, io, stream=None):
     """rsx_dpg_adam_step: clip + Adam on the critics and (with a grad_actor) the actor, each group on its own, and the Polyak step"""
     rc = load().rsx_dpg_adam_step(None if cfg is None else C.byref(cfg), None if state is None else C.byref(state),
+                                  None if io is None else C.byref(io), stream)
+    if rc:
+        _chk(rc)
+
+
+def sac_adam_step(cfg, state, io, stream=None):
+    """rsx_sac_adam_step: clip + Adam on the critics, (with a grad_actor) the actor and (with a grad_log_alpha) log_alpha, each group on
+    its own, and the Polyak step of the target critics"""
+    rc = load().rsx_sac_adam_step(None if cfg is None else C.byref(cfg), None if state is None else C.byref(state),
                                   None if io is None else C.byref(io), stream)
     if rc:
         _chk(rc)
@@ -945,6 +998,24 @@ class Sim:
         rc = self._lib.rsx_task_dpg_update(self._h, b(actor), actor_params_ptr, target_actor_params_ptr, b(critic), critic_params_ptr,
                                            target_critic_params_ptr, b(inp), b(cfg), b(ucfg), b(adam), b(state), stats_ptr, workspace_ptr,
                                            stream)
+        if rc:
+            _chk(rc)
+
+    def sac_update_workspace(self, actor, critic, n_critics, n_rows, max_workgroups=0):
+        """rsx_sac_update_workspace: (bytes of scratch rsx_task_sac_update needs, the offset of its int32 rows in it)"""
+        n, off = C.c_int64(0), C.c_int64(0)
+        _chk(self._lib.rsx_sac_update_workspace(self._h, None if actor is None else C.byref(actor), None if critic is None else C.byref(critic),
+                                                int(n_critics), int(n_rows), int(max_workgroups), C.byref(n), C.byref(off)))
+        return int(n.value), int(off.value)
+
+    def task_sac_update(self, actor, actor_params_ptr, critic, critic_params_ptr, target_critic_params_ptr, log_alpha_ptr, inp, cfg, ucfg,
+                        adam, state, stats_ptr, workspace_ptr, stream=None):
+        """rsx_task_sac_update: the whole update phase of soft actor-critic enqueued by one call — per gradient step the row draw, the
+        gradients and the three-group clip + Adam + Polyak step; the actor, the critics, the target critics and log_alpha are updated
+        in place.  Reads and writes nothing of the envs."""
+        b = lambda x: None if x is None else C.byref(x)   # noqa: E731
+        rc = self._lib.rsx_task_sac_update(self._h, b(actor), actor_params_ptr, b(critic), critic_params_ptr, target_critic_params_ptr,
+                                           log_alpha_ptr, b(inp), b(cfg), b(ucfg), b(adam), b(state), stats_ptr, workspace_ptr, stream)
         if rc:
             _chk(rc)
 

@@ -869,6 +869,81 @@ int rsx_task_dpg_update(rsx_sim* h, const rsx_policy_mlp* actor, float* actor_pa
     return RSX_OK;
 }
 
+// ---- the soft actor-critic update phase (rsx.h: rsx_sac_adam_step, rsx_task_sac_update) ----
+// what rsx_sac_adam_step and rsx_task_sac_update check of the three-group optimiser's configuration and state
+static int sac_adam_prologue(const rsx_sac_adam_cfg* c, const rsx_sac_adam_state* st) {
+    if (!c) return fail(RSX_ERR_ARG, "the optimiser's configuration (rsx_sac_adam_cfg) must not be null");
+    if (!(std::isfinite(c->lr_actor) && c->lr_actor >= 0.0f)) return fail(RSX_ERR_ARG, "lr_actor must be finite and >= 0");
+    if (!(std::isfinite(c->lr_critic) && c->lr_critic >= 0.0f)) return fail(RSX_ERR_ARG, "lr_critic must be finite and >= 0");
+    if (!(std::isfinite(c->lr_alpha) && c->lr_alpha >= 0.0f)) return fail(RSX_ERR_ARG, "lr_alpha must be finite and >= 0");
+    if (!(std::isfinite(c->eps) && c->eps >= 0.0f)) return fail(RSX_ERR_ARG, "eps must be finite and >= 0");
+    if (!(c->beta1 >= 0.0 && c->beta1 < 1.0) || !(c->beta2 >= 0.0 && c->beta2 < 1.0)) return fail(RSX_ERR_ARG, "beta1 and beta2 must be in [0, 1)");
+    if (!std::isfinite(c->max_grad_norm)) return fail(RSX_ERR_ARG, "max_grad_norm must be finite (<= 0: no clipping)");
+    if (!(c->tau >= 0.0f && c->tau <= 1.0f)) return fail(RSX_ERR_ARG, "tau must be in [0, 1]");   // (a NaN fails both comparisons)
+    if (!st) return fail(RSX_ERR_ARG, "the optimiser's state (rsx_sac_adam_state) must not be null");
+    if (!st->m_actor || !st->v_actor || !st->m_critic || !st->v_critic || !st->m_alpha || !st->v_alpha || !st->counters)
+        return fail(RSX_ERR_ARG, "the state's m, v (actor, critic, alpha) and counters arrays must not be null");
+    if (st->n_actor < 1 || st->n_critic < 1 || st->n_actor > 0x7FFFFFFFll || st->n_critic > 0x7FFFFFFFll)
+        return fail(RSX_ERR_ARG, "n_actor and n_critic must be in 1 .. 2^31 - 1");
+    return RSX_OK;
+}
+
+int rsx_sac_adam_step(const rsx_sac_adam_cfg* cfg, const rsx_sac_adam_state* st, const rsx_sac_adam_io* io, void* stream) {
+    (void)launch_status();
+    if (int rc = sac_adam_prologue(cfg, st)) return rc;
+    if (!io || !io->actor_params || !io->critic_params || !io->log_alpha || !io->grad_critic || !io->workspace)
+        return fail(RSX_ERR_ARG, "io and its actor_params, critic_params, log_alpha, grad_critic and workspace must not be null");
+    if (io->update_targets && !io->target_critic_params) return fail(RSX_ERR_ARG, "update_targets needs target_critic_params");
+    launch_sac_adam_step(*cfg, *st, *io, (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
+int rsx_sac_update_workspace(const rsx_sim* h, const rsx_policy_mlp* actor, const rsx_policy_mlp* critic, int n_critics, int64_t n_rows,
+                             int max_workgroups, int64_t* bytes_out, int64_t* rows_offset_out) {
+    if (!h) return fail(RSX_ERR_ARG, "null handle");
+    if (!bytes_out) return fail(RSX_ERR_ARG, "bytes_out must not be null");
+    PolicySpec SA, SC; int64_t na = 0, nc = 0;
+    if (int rc = sac_prologue(h, actor, critic, n_critics, &SA, &na, &SC, &nc)) return rc;
+    if (n_rows < 1 || n_rows > 0x7FFFFFFFll) return fail(RSX_ERR_ARG, "n_rows must be in 1 .. 2^31 - 1");
+    if (max_workgroups < 0) return fail(RSX_ERR_ARG, "max_workgroups must be >= 0");
+    long long off = 0;
+    *bytes_out = sac_update_workspace_bytes(na, nc, n_critics, n_rows, max_workgroups, &off);
+    if (rows_offset_out) *rows_offset_out = off;
+    return RSX_OK;
+}
+
+int rsx_task_sac_update(rsx_sim* h, const rsx_policy_mlp* actor, float* actor_params_dev, const rsx_policy_mlp* critic,
+                        float* critic_params_dev, float* target_critic_params_dev, float* log_alpha_dev, const rsx_dpg_in* in,
+                        const rsx_sac_cfg* cfg, const rsx_sac_update_cfg* u, const rsx_sac_adam_cfg* adam, const rsx_sac_adam_state* st,
+                        float* stats_dev, void* workspace, void* stream) {
+    RSX_ENTER(h);   // (nothing the handle owns is read or written by the launches)
+    if (!cfg) return fail(RSX_ERR_ARG, "cfg must not be null");
+    PolicySpec SA, SC; int64_t na = 0, nc = 0;
+    if (int rc = sac_prologue(h, actor, critic, cfg->n_critics, &SA, &na, &SC, &nc)) return rc;
+    if (!actor_params_dev || !critic_params_dev || !target_critic_params_dev || !log_alpha_dev)
+        return fail(RSX_ERR_ARG, "actor_params_dev, critic_params_dev, target_critic_params_dev and log_alpha_dev must not be null");
+    if (!in || !in->obs || !in->action || !in->reward || !in->next_obs || !in->terminated)
+        return fail(RSX_ERR_ARG, "in and its obs, action, reward, next_obs and terminated arrays must not be null");
+    if (in->rows) return fail(RSX_ERR_ARG, "in->rows must be NULL: the update draws its own rows");
+    if (!(std::isfinite(cfg->gamma) && cfg->gamma >= 0.0f && cfg->gamma <= 1.0f)) return fail(RSX_ERR_ARG, "gamma must be in [0, 1]");
+    if (!std::isfinite(cfg->target_entropy)) return fail(RSX_ERR_ARG, "target_entropy must be finite");
+    if (!std::isfinite(cfg->log_std_min) || !std::isfinite(cfg->log_std_max) || !(cfg->log_std_min < cfg->log_std_max))
+        return fail(RSX_ERR_ARG, "log_std_min and log_std_max must be finite with log_std_min < log_std_max");
+    if (cfg->max_workgroups < 0) return fail(RSX_ERR_ARG, "max_workgroups must be >= 0");
+    if (!u) return fail(RSX_ERR_ARG, "the update's configuration (rsx_sac_update_cfg) must not be null");
+    if (u->grad_steps < 1) return fail(RSX_ERR_ARG, "grad_steps must be >= 1");
+    if (int rc = sample_rows_check(in->n_rows, in->n_batch_rows, u->fill, u->fill_dev)) return rc;
+    if (int rc = sac_adam_prologue(adam, st)) return rc;
+    if (st->n_actor != na || st->n_critic != (int64_t)cfg->n_critics * nc)
+        return fail(RSX_ERR_ARG, "the optimiser state's sizes (n_actor, n_critic) are not those of the actor and of n_critics critics");
+    if (!stats_dev || !workspace) return fail(RSX_ERR_ARG, "stats_dev and workspace must not be null");
+    launch_sac_update(SA, na, actor_params_dev, SC, nc, critic_params_dev, target_critic_params_dev, log_alpha_dev, h->P.obs_dim,
+                      h->M.act_dim, *in, *cfg, *u, *adam, *st, stats_dev, workspace, (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
 // ---- the update phase around it (rsx.h: rsx_ppo_normalize, rsx_ppo_permutation, rsx_adam_step, rsx_adam_mark, rsx_task_ppo_update) ----
 // what rsx_adam_step and rsx_task_ppo_update check of an optimiser's configuration and state
 static int adam_prologue(const rsx_adam_cfg* c, const rsx_adam_state* st) {

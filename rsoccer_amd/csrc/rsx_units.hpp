@@ -28,6 +28,10 @@ struct rsx_dpg_update_cfg;
 struct rsx_dpg_adam_cfg;
 struct rsx_dpg_adam_state;
 struct rsx_dpg_adam_io;
+struct rsx_sac_update_cfg;
+struct rsx_sac_adam_cfg;
+struct rsx_sac_adam_state;
+struct rsx_sac_adam_io;
 
 namespace rsx {
 
@@ -216,6 +220,18 @@ void launch_dpg_update(const PolicySpec& actor, long long n_params_actor, float*
                        const PolicySpec& critic, long long n_params_critic, float* critic_params, float* target_critic_params, int obs_dim,
                        int act_dim, const rsx_dpg_in& in, const rsx_dpg_cfg& cfg, const rsx_dpg_update_cfg& u, const rsx_dpg_adam_cfg& adam,
                        const rsx_dpg_adam_state& st, float* stats, void* workspace, hipStream_t s);
+// rsx_sac_update.hip: the update phase around launch_sac_gradient (rsx_sac_adam_step, rsx_task_sac_update); every argument checked by the
+// caller.  Two launches for the optimiser step (the norms of the critics and the actor, then Adam on three groups — log_alpha in one
+// thread — with the Polyak step of the target critics).  sac_update_workspace_bytes: launch_sac_update's workspace (rows_offset: where
+// the int32 rows lie in it); launch_sac_update enqueues the whole phase and calls launch_replay_sample_rows and launch_sac_gradient per
+// gradient step
+void launch_sac_adam_step(const rsx_sac_adam_cfg& c, const rsx_sac_adam_state& st, const rsx_sac_adam_io& io, hipStream_t s);
+long long sac_update_workspace_bytes(long long n_params_actor, long long n_params_critic, int n_critics, long long n_rows,
+                                     int max_workgroups, long long* rows_offset);
+void launch_sac_update(const PolicySpec& actor, long long n_params_actor, float* actor_params, const PolicySpec& critic,
+                       long long n_params_critic, float* critic_params, float* target_critic_params, float* log_alpha, int obs_dim,
+                       int act_dim, const rsx_dpg_in& in, const rsx_sac_cfg& cfg, const rsx_sac_update_cfg& u, const rsx_sac_adam_cfg& adam,
+                       const rsx_sac_adam_state& st, float* stats, void* workspace, hipStream_t s);
 // rsx_render.hip: batched rgb frames (rsx_render_*).  render_check_view: nullptr when the view is valid (and the frame size), else the
 // message; render_field_host: the static field image [H][W][3]; RenderGeom: what the kernel needs of a view, in float32
 struct RenderGeom { int W, H; float s, cx, cy, r, rb; int square; };

@@ -1197,6 +1197,115 @@ class VecFusedEnv(RenderMixin):
         self._keep_dpg_update = (ws, term, fill)   # the call's own tensors: alive until the launches have consumed them
         return {"stats": stats, "rows": ws[rows_off // 4: rows_off // 4 + M].view(torch.int32)}
 
+    def sac_update(self, buf, policy, params, critic, critic_params, target_critic_params, log_alpha, opt, grad_steps=8, batch_size=256,
+                   gamma=0.99, target_entropy=None, learn_alpha=True, seed=0, max_workgroups=None):
+        """The whole update phase of soft actor-critic enqueued by ONE call (``rsx_task_sac_update``): per gradient step
+        ``buf.sample_rows_device(batch_size, seed, opt.steps)``, ``sac_gradient(rows=those, noise_seed=seed, noise_step=opt.steps)``
+        and ``opt.step(..., update_targets=True)`` — bit for bit that sequence of calls, without the interpreter between them.  Every
+        step steps the critics and the actor and moves the target critics; ``learn_alpha=False`` keeps the temperature fixed
+        (``log_alpha``, its moments and its step count keep their bytes).
+
+        ``buf``: a ``ReplayBuffer``, or a ``data()`` mapping with a ``fill`` entry (int64 ``[1]`` on the env's device: the rows that
+        hold a transition, read when the launches run).  ``policy`` / ``critic``, the three parameter tensors, ``log_alpha`` ``[1]``,
+        ``gamma`` and ``target_entropy``: as for ``sac_gradient``; the four tensors are UPDATED IN PLACE, the transitions are not
+        written.  ``opt``: a ``rsoccer_amd.vec.optim.SACOptimizer`` of these networks on the env's device; its count of finished
+        gradient steps (on the device) keys the row draws and the sampling noise and advances by ``grad_steps``.  On an empty buffer
+        every row is skipped, no parameter moves (``log_alpha`` neither), the counters advance and the targets take their steps.
+
+        Returns ``{"stats": {name: [grad_steps]}, "table": [grad_steps, 16], "rows": [batch_size] int32}``: per step ``sac_gradient``'s
+        twelve values, the two gradient norms before the clip, ``log_alpha`` after the step and whether the targets moved
+        (``_lib.SAC_UPDATE_STATS``; ``stats`` holds the columns of ``table`` by name); ``rows`` is a view of the call's workspace holding
+        the last step's rows.  Touches nothing of the env, never synchronises, capturable into a ``torch.cuda.CUDAGraph``: with
+        ``collect()`` on a device-keyed env and ``buf.add`` in the same graph, one replay is one off-policy iteration."""
+        torch = self._torch
+        from rsoccer_amd.vec.optim import SACOptimizer
+        from rsoccer_amd.vec.policy import MLPGaussianPolicy, MLPQCritic
+        from rsoccer_amd.vec.replay import ReplayBuffer
+        if not isinstance(opt, SACOptimizer):
+            raise ValueError("opt must be an rsoccer_amd.vec.optim.SACOptimizer")
+        if not isinstance(policy, MLPGaussianPolicy):
+            raise ValueError("policy must be an rsoccer_amd.vec.policy.MLPGaussianPolicy")
+        if not isinstance(critic, MLPQCritic):
+            raise ValueError("critic must be an rsoccer_amd.vec.policy.MLPQCritic")
+        OD, AD, dev = self.sim.obs_dim, self.sim.act_dim, self.device
+        if policy.obs_dim != OD or policy.act_dim != AD:
+            raise ValueError(f"the policy maps {policy.obs_dim} -> {policy.act_dim}, the env {OD} -> {AD}")
+        if critic.state_dim != OD or critic.action_dim != AD:
+            raise ValueError(f"the critic reads ({critic.state_dim}, {critic.action_dim}) floats, the env has ({OD}, {AD})")
+        grad_steps, M = int(grad_steps), int(batch_size)
+        if grad_steps < 1:
+            raise ValueError(f"grad_steps must be >= 1, got {grad_steps}")
+        if not 1 <= M <= 2 ** 31 - 1:
+            raise ValueError(f"batch_size must be in 1 .. 2^31 - 1, got {batch_size}")
+        gamma = float(gamma)
+        if not (np.isfinite(gamma) and 0.0 <= gamma <= 1.0):
+            raise ValueError(f"gamma must be in [0, 1], got {gamma}")
+        te = -float(AD) if target_entropy is None else float(target_entropy)
+        if not np.isfinite(te):
+            raise ValueError(f"target_entropy must be finite, got {target_entropy}")
+        if not 0.0 <= opt.tau <= 1.0:
+            raise ValueError(f"tau must be in [0, 1], got {opt.tau}")
+        mw = 0 if max_workgroups is None else int(max_workgroups)
+        if mw < 0 or (max_workgroups is not None and mw < 1):
+            raise ValueError(f"max_workgroups must be >= 1 or None, got {max_workgroups}")
+
+        def need(name, t, shape, dtypes=(torch.float32,)):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
+            if tuple(t.shape) != tuple(shape):
+                raise ValueError(f"{name} must be {list(shape)}, got {list(t.shape)}")
+            if t.dtype not in dtypes:
+                raise ValueError(f"{name} must be {' or '.join(str(d) for d in dtypes)}, got {t.dtype}")
+            if t.device != dev:
+                raise ValueError(f"{name} is on {t.device}, the env on {dev}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+            return t.detach()
+
+        if isinstance(buf, ReplayBuffer):
+            data = dict(buf.data(), fill=buf.fill)
+        else:
+            data = buf
+            for key in ("obs", "actions", "reward", "next_obs", "terminated", "fill"):
+                if key not in data:
+                    raise ValueError(f"buf lacks {key!r}")
+        obs = data["obs"]
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or obs.shape[0] < 1 or obs.shape[1] != OD:
+            raise ValueError(f"buf['obs'] must be a [N >= 1, {OD}] tensor, got {tuple(np.shape(obs))}")
+        N = int(obs.shape[0])
+        obs = need("buf['obs']", obs, (N, OD))
+        act = need("buf['actions']", data["actions"], (N, AD))
+        rew = need("buf['reward']", data["reward"], (N,))
+        nxt = need("buf['next_obs']", data["next_obs"], (N, OD))
+        term = need("buf['terminated']", data["terminated"], (N,), (torch.bool, torch.uint8))
+        fill = need("buf['fill']", data["fill"], (1,), (torch.int64,))
+        p = need("params", params, (policy.num_params,))
+        if not isinstance(critic_params, torch.Tensor) or critic_params.dim() != 2 or critic_params.shape[0] not in (1, 2):
+            raise ValueError(f"critic_params must be a [C, {critic.num_params}] tensor with C in (1, 2), got {tuple(np.shape(critic_params))}")
+        C = int(critic_params.shape[0])
+        cp = need("critic_params", critic_params, (C, critic.num_params))
+        tcp = need("target_critic_params", target_critic_params, (C, critic.num_params))
+        la = need("log_alpha", log_alpha, (1,))
+        if opt.device != dev:
+            raise ValueError(f"the optimiser is on {opt.device}, the env on {dev}")
+        if opt.sizes != (policy.num_params, C * critic.num_params):
+            raise ValueError(f"the optimiser's state tensors have sizes {opt.sizes}, the networks "
+                             f"{(policy.num_params, C * critic.num_params)}")
+        aspec, cspec = policy.spec(), critic.spec()
+        nbytes, rows_off = self.sim.sac_update_workspace(aspec, cspec, C, M, mw)
+        ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=dev)
+        stats = torch.empty((grad_steps, len(_lib.SAC_UPDATE_STATS)), dtype=torch.float32, device=dev)
+        ptr = lambda t: t.data_ptr()   # noqa: E731  (a bool tensor is one byte per element, 0 or 1)
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        inp = _lib.DpgIn(ptr(obs), ptr(act), ptr(rew), ptr(nxt), ptr(term), None, N, M)
+        cfg = _lib.SacCfg(None, seed, 0, gamma, te, policy.log_std_min, policy.log_std_max, C, mw)
+        ucfg = _lib.SacUpdateCfg(ptr(fill), seed, 0, grad_steps, 1 if learn_alpha else 0)
+        self.sim.task_sac_update(aspec, ptr(p), cspec, ptr(cp), ptr(tcp), ptr(la), inp, cfg, ucfg, opt.cfg(), opt.state(), ptr(stats),
+                                 ptr(ws), self._stream())
+        self._keep_sac_update = (ws, term, fill)   # the call's own tensors: alive until the launches have consumed them
+        return {"stats": {name: stats[:, k] for k, name in enumerate(_lib.SAC_UPDATE_STATS)}, "table": stats,
+                "rows": ws[rows_off // 4: rows_off // 4 + M].view(torch.int32)}
+
     # ---- the update phase around ppo_gradient (include/rsx.h: rsx_ppo_normalize, rsx_ppo_permutation, rsx_task_ppo_update) ----
     def normalize_advantages(self, adv, eps=1e-8, return_moments=False):
         """``(adv - adv.mean()) / (adv.std() + eps)`` over all entries of a float32 device tensor (any shape, at least two entries,

@@ -2,7 +2,8 @@
 ``torch.optim.Adam`` on the three flat tensors ``VecFusedEnv.ppo_gradient`` differentiates — the actor's parameters, ``log_std`` and the
 critic's parameters — with its whole state on the device, the step count included, so that a step is stream-ordered and capturable.
 ``DPGOptimizer`` is its off-policy twin (rsx_dpg_adam_step): the critics and the actor of TD3 / DDPG as two groups with step counts of
-their own, and the Polyak step of the targets in the same two launches."""
+their own, and the Polyak step of the targets in the same two launches.  ``SACOptimizer`` is soft actor-critic's (rsx_sac_adam_step): a
+third group for the scalar log-temperature, target critics only."""
 import math
 
 import numpy as np
@@ -348,3 +349,160 @@ class DPGOptimizer:
             self.max_grad_norm = _finite("max_grad_norm", sd["max_grad_norm"])
         if "tau" in sd:
             self.tau = self._check_tau(sd["tau"])
+
+
+class SACOptimizer:
+    """The optimiser step of soft actor-critic for an ``MLPGaussianPolicy`` actor, ``n_critics`` ``MLPQCritic`` networks and the
+    log-temperature, in two launches (include/rsx.h: rsx_sac_adam_step): three parameter groups — the critics' ``[C, Pc]`` tensor, the
+    actor's ``[P]`` and ``log_alpha`` ``[1]`` — each with its own Adam (no amsgrad, no weight decay), its own ``lr`` and its own step
+    count, as three torch optimisers; the critics and the actor each behind a ``clip_grad_norm_`` of their own, ``log_alpha`` never
+    clipped; and the Polyak step of the target critics behind it, on the new parameters.  There is no target actor.
+
+    State, all on ``device``: ``m`` and ``v`` for the three tensors (actor, critics, log_alpha) and ``counters``, int64 ``[4]``
+    (``_lib.SAC_COUNTERS``): the critics' ``t``, the actor's, ``log_alpha``'s (a group's ``t`` advances only when the group steps) and
+    the gradient steps finished.  ``steps`` is a ``[1]`` view of the fourth: pass it as ``noise_step=`` to ``sac_gradient`` and as
+    ``step=`` to ``ReplayBuffer.sample_rows_device`` and a replayed graph draws new noise and new rows after every step.
+
+    ``lr_actor`` / ``lr_critic`` / ``lr_alpha``: a float, or a float32 CUDA tensor ``[1]`` read on the device at every step.
+    ``max_grad_norm``: ``None`` or ``<= 0`` for no clipping, else the bound of the critics' norm and of the actor's, each on its own.
+    ``tau`` in ``[0, 1]``.  Invalid values are a ``ValueError`` naming the offender, raised before anything is allocated."""
+
+    def __init__(self, policy, critic, n_critics, device=0, lr_actor=3e-4, lr_critic=3e-4, lr_alpha=3e-4, betas=(0.9, 0.999), eps=1e-8,
+                 max_grad_norm=None, tau=0.005):
+        import torch
+        from rsoccer_amd.vec.policy import MLPGaussianPolicy, MLPQCritic
+        if not isinstance(policy, MLPGaussianPolicy):
+            raise ValueError("policy must be an rsoccer_amd.vec.policy.MLPGaussianPolicy")
+        if not isinstance(critic, MLPQCritic):
+            raise ValueError("critic must be an rsoccer_amd.vec.policy.MLPQCritic")
+        if n_critics not in (1, 2):
+            raise ValueError(f"n_critics must be 1 or 2, got {n_critics!r}")
+        self._torch = torch
+        self.device = device if isinstance(device, torch.device) else torch.device("cuda", int(device))
+        self.n_critics = int(n_critics)
+        self.sizes = (policy.num_params, self.n_critics * critic.num_params)
+        self.lr_actor = self._check_lr("lr_actor", lr_actor)
+        self.lr_critic = self._check_lr("lr_critic", lr_critic)
+        self.lr_alpha = self._check_lr("lr_alpha", lr_alpha)
+        if len(tuple(betas)) != 2:
+            raise ValueError(f"betas must be a pair, got {betas!r}")
+        self.betas = tuple(float(b) for b in betas)
+        for k, b in enumerate(self.betas):
+            if not (0.0 <= b < 1.0):   # (a NaN fails both comparisons)
+                raise ValueError(f"betas[{k}] must be in [0, 1), got {b}")
+        self.eps = _finite("eps", eps, 0.0)
+        self.max_grad_norm = 0.0 if max_grad_norm is None else _finite("max_grad_norm", max_grad_norm)
+        self.tau = DPGOptimizer._check_tau(tau)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self.m = [torch.zeros((n,), **f32) for n in self.sizes + (1,)]
+        self.v = [torch.zeros((n,), **f32) for n in self.sizes + (1,)]
+        self.counters = torch.zeros((4,), dtype=torch.int64, device=self.device)
+        self._ws = torch.zeros((_lib.SAC_ADAM_WORKSPACE_BYTES // 8,), dtype=torch.float64, device=self.device)
+
+    _check_lr = DPGOptimizer._check_lr
+    _stream = PPOOptimizer._stream
+    _need = DPGOptimizer._need
+
+    @property
+    def steps(self):
+        """the gradient steps finished: an int64 ``[1]`` view of the device counter (the key of the row draws and the sampling noise)"""
+        k = _lib.SAC_COUNTERS.index("steps")
+        return self.counters[k:k + 1]
+
+    # ---- the C structs ----
+    def cfg(self):
+        """the ``rsx_sac_adam_cfg`` of this optimiser"""
+        is_t = lambda x: isinstance(x, self._torch.Tensor)   # noqa: E731
+        lrs = (self.lr_actor, self.lr_critic, self.lr_alpha)
+        return _lib.SacAdamCfg(self.betas[0], self.betas[1], *(x.data_ptr() if is_t(x) else None for x in lrs),
+                               *(0.0 if is_t(x) else x for x in lrs), self.eps, self.max_grad_norm, self.tau)
+
+    def state(self):
+        """the ``rsx_sac_adam_state`` of this optimiser"""
+        (ma, mc, ml), (va, vc, vl) = self.m, self.v
+        return _lib.SacAdamState(ma.data_ptr(), va.data_ptr(), mc.data_ptr(), vc.data_ptr(), ml.data_ptr(), vl.data_ptr(),
+                                 self.counters.data_ptr(), *self.sizes)
+
+    def _need_scalar(self, name, t):
+        torch = self._torch
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor, got {type(t).__name__}")
+        if tuple(t.shape) != (1,):
+            raise ValueError(f"{name} must be [1], got {list(t.shape)}")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{name} must be torch.float32, got {t.dtype}")
+        if t.device != self.device:
+            raise ValueError(f"{name} is on {t.device}, the optimiser on {self.device}")
+        return t.detach()
+
+    # ---- steps ----
+    def step(self, params, critic_params, target_critic_params, log_alpha, grad_params, grad_critic_params, grad_log_alpha,
+             update_targets=True):
+        """One optimiser step IN PLACE (``rsx_sac_adam_step``; the arithmetic is written out in ``include/rsx.h``): clip + Adam on
+        ``critic_params`` ``[C, Pc]`` with ``grad_critic_params``; with ``grad_params`` not ``None`` also on ``params`` ``[P]``; with
+        ``grad_log_alpha`` not ``None`` Adam (no clip) on ``log_alpha`` ``[1]``; a group whose gradient is ``None`` keeps its
+        parameters, moments and step count exactly as they were.  With ``update_targets`` the Polyak step
+        ``target += tau * (live - target)`` of the target critics on the new parameters.  The gradients are ``sac_gradient()``'s
+        outputs and are not changed.
+
+        Returns 0-d device views ``grad_norm_critic``, ``grad_norm_actor`` (before the clip; 0 without an actor step), ``log_alpha``
+        (after the step) and ``targets_moved`` (1.0 or 0.0).  Never synchronises, capturable."""
+        torch = self._torch
+        na, nc = self.sizes
+        p = self._need("params", params, na)
+        cp, tcp = self._need("critic_params", critic_params, nc), self._need("target_critic_params", target_critic_params, nc)
+        la = self._need_scalar("log_alpha", log_alpha)
+        ga = None if grad_params is None else self._need("grad_params", grad_params, na)
+        gc = self._need("grad_critic_params", grad_critic_params, nc)
+        gl = None if grad_log_alpha is None else self._need_scalar("grad_log_alpha", grad_log_alpha)
+        stats = torch.empty((len(_lib.SAC_ADAM_STATS),), dtype=torch.float32, device=self.device)
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        io = _lib.SacAdamIo(ptr(p), ptr(cp), ptr(tcp), ptr(la), ptr(ga), ptr(gc), ptr(gl), ptr(stats), ptr(self._ws),
+                            1 if update_targets else 0)
+        with torch.cuda.device(self.device):
+            _lib.sac_adam_step(self.cfg(), self.state(), io, self._stream())
+        return {name: stats[k] for k, name in enumerate(_lib.SAC_ADAM_STATS)}
+
+    # ---- checkpoints ----
+    def state_dict(self):
+        """clones of ``m``, ``v`` (three tensors each: actor, critics, log_alpha) and ``counters``, and the hyper-parameters"""
+        clone = lambda x: x.clone() if isinstance(x, self._torch.Tensor) else x   # noqa: E731
+        return {"m": [t.clone() for t in self.m], "v": [t.clone() for t in self.v], "counters": self.counters.clone(),
+                "lr_actor": clone(self.lr_actor), "lr_critic": clone(self.lr_critic), "lr_alpha": clone(self.lr_alpha),
+                "betas": self.betas, "eps": self.eps, "max_grad_norm": self.max_grad_norm, "tau": self.tau}
+
+    def load_state_dict(self, sd):
+        """copies a ``state_dict()`` into this optimiser's own tensors (their addresses stay: a captured graph keeps working);
+        tensors of another size are a ``ValueError``"""
+        torch = self._torch
+        for key in ("m", "v", "counters"):
+            if key not in sd:
+                raise ValueError(f"state dict lacks {key!r}")
+        for key, mine in (("m", self.m), ("v", self.v)):
+            theirs = list(sd[key])
+            if len(theirs) != 3:
+                raise ValueError(f"state dict's {key!r} must hold three tensors, got {len(theirs)}")
+            for k, (a, b) in enumerate(zip(mine, theirs)):
+                if tuple(np.shape(b)) != tuple(a.shape):
+                    raise ValueError(f"state dict's {key}[{k}] must be {list(a.shape)}, got {list(np.shape(b))}")
+        if tuple(np.shape(sd["counters"])) != (4,):
+            raise ValueError(f"state dict's counters must be [4], got {list(np.shape(sd['counters']))}")
+        for key, mine in (("m", self.m), ("v", self.v)):
+            for a, b in zip(mine, sd[key]):
+                a.copy_(torch.as_tensor(b).to(device=self.device, dtype=torch.float32))
+        self.counters.copy_(torch.as_tensor(sd["counters"]).to(device=self.device, dtype=torch.int64))
+        for name in ("lr_actor", "lr_critic", "lr_alpha"):
+            if name in sd:
+                lr, mine = sd[name], getattr(self, name)
+                if isinstance(lr, torch.Tensor) and isinstance(mine, torch.Tensor):
+                    mine.copy_(lr.to(self.device))
+                else:
+                    setattr(self, name, self._check_lr(name, lr.to(self.device) if isinstance(lr, torch.Tensor) else lr))
+        if "betas" in sd:
+            self.betas = tuple(float(b) for b in sd["betas"])
+        if "eps" in sd:
+            self.eps = _finite("eps", sd["eps"], 0.0)
+        if "max_grad_norm" in sd:
+            self.max_grad_norm = _finite("max_grad_norm", sd["max_grad_norm"])
+        if "tau" in sd:
+            self.tau = DPGOptimizer._check_tau(sd["tau"])
