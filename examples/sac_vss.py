@@ -1,7 +1,7 @@
 """Soft actor-critic on VSS-v0 with the rollouts collected in one launch under the actor itself.
 
     python examples/sac_vss.py [--envs 256] [--steps 16] [--updates 10] [--grad-steps 8] [--batch 256] [--torch]
-                               [--device-update] [--graph]
+                               [--device-update] [--graph] [--per [--alpha A --beta B]] [--n-step N]
 
 One update: env.collect(MLPGaussianPolicy, ...) advances the envs `steps` steps under the current actor — mean and log-std per state,
 the sample squashed by tanh, all inside the launch (rsx_task_collect_gaussian) — ReplayBuffer.add() stores the T * B transitions with
@@ -11,7 +11,10 @@ device, env.sac_gradient(...) returns the gradients of the critic loss, the acto
 --torch runs the same losses in torch autograd instead (sac_losses below, on the same flat vectors: MLPGaussianPolicy.sample and
 MLPQCritic.forward are plain torch; what tools/bench_sac_grad.py times the engine against).  --device-update replaces the whole
 gradient-step loop by ONE call, env.sac_update with a SACOptimizer (rows from the engine's generator, the three Adam steps and the Polyak
-step on the device); --graph captures collect + add + sac_update once and replays them (device_update below).  A demonstration of the
+step on the device); --graph captures collect + add + sac_update once and replays them (device_update below).  --per and --n-step N keep
+the transitions in a PrioritizedReplayBuffer and run the piecewise loop on the device (per_loop below): buf.sample,
+env.sac_gradient(weights=..., return_td_error=True), opt.step, buf.update_priorities; with --graph that loop is captured once, with
+collect and buf.add.  The fused phase (--device-update) does not take priorities or per-row discounts yet.  A demonstration of the
 call pattern, not a tuned trainer."""
 import argparse
 import os
@@ -23,7 +26,7 @@ import torch
 
 from rsoccer_amd.vec import VecVSSEnv
 from rsoccer_amd.vec.policy import MLPGaussianPolicy, MLPQCritic
-from rsoccer_amd.vec.replay import ReplayBuffer
+from rsoccer_amd.vec.replay import PrioritizedReplayBuffer, ReplayBuffer
 
 
 def mlp(n_in, n_out):
@@ -94,6 +97,59 @@ def device_update(args):
     env.close()
 
 
+def per_loop(args):
+    """--per / --n-step: prioritised and n-step replay, every piece on the device.  Without --per the priorities play no part
+    (alpha = 0 makes every leaf 1, beta = 0 every weight 1) and only the n-step fold and its per-row discounts remain.  --graph: one
+    whole update captured once on a device-keyed env and replayed; the optimiser's step count on the device keys every draw."""
+    from rsoccer_amd.vec.optim import SACOptimizer
+    torch.manual_seed(args.seed)
+    env = VecVSSEnv(args.envs, device=0, seed=args.seed)
+    dev, OD, AD = env.device, env.sim.obs_dim, env.sim.act_dim
+    pol = MLPGaussianPolicy(OD, AD, hidden=64, layers=2, hidden_act="tanh")
+    qnet = MLPQCritic(OD, AD, hidden=64, layers=2, hidden_act="tanh")
+    p_actor = pol.from_module(mlp(OD, 2 * AD)).to(dev)
+    p_critics = torch.stack([qnet.from_module(mlp(OD + AD, 1)) for _ in range(2)]).to(dev)
+    t_critics, log_alpha = p_critics.clone(), torch.zeros(1, device=dev)
+    opt = SACOptimizer(pol, qnet, 2, device=dev, lr_actor=args.lr, lr_critic=args.lr, lr_alpha=args.lr, tau=args.tau)
+    buf = PrioritizedReplayBuffer(args.capacity, OD, AD, dev, alpha=args.alpha if args.per else 0.0, n_step=args.n_step, gamma=args.gamma)
+    beta = args.beta if args.per else 0.0
+    env.reset()
+    if args.graph:
+        env.enable_graph_capture()
+
+    def iteration():
+        batch = env.collect(pol, p_actor, args.steps, noise_seed=args.seed + 2, return_final_obs=True)
+        buf.add(batch)
+        data = buf.data()   # carries "discount": the targets use each row's own gamma^m
+        for _ in range(args.grad_steps):
+            rows, weights = buf.sample(args.batch, beta=beta, seed=args.seed + 1, step=opt.steps)
+            out = env.sac_gradient(data, pol, p_actor, qnet, p_critics, t_critics, log_alpha, rows=rows, gamma=args.gamma,
+                                   noise_seed=args.seed + 1, noise_step=opt.steps, weights=weights, return_td_error=True)
+            opt.step(p_actor, p_critics, t_critics, log_alpha, out["grad_params"], out["grad_critic_params"], out["grad_log_alpha"])
+            buf.update_priorities(rows, out["td_error"])
+        return batch["reward"].mean(), out["stats"], weights
+
+    graph = None
+    for update in range(args.updates):
+        t0 = time.perf_counter()
+        if graph is not None:
+            graph.replay()
+        else:
+            reward, stats, weights = iteration()   # (eager; with --graph also the warm-up before the capture)
+        torch.cuda.synchronize()
+        m = env.metrics()
+        print(f"update {update}: mean reward / step {float(reward):+.5f}, episodes {m['episodes']}, goals for / against "
+              f"{m['goals_for']} / {m['goals_against']}, buffer {int(buf.fill)} rows, gradient steps {int(opt.steps)}, loss_q "
+              f"{float(stats['loss_q0'] + stats['loss_q1']):.5f}, alpha {float(log_alpha.exp()):.4f}, largest priority "
+              f"{float(buf.max_priority()):.4f}, smallest weight {float(weights.min()):.4f}; collect + add + {args.grad_steps} gradient steps "
+              f"{(time.perf_counter() - t0) * 1e3:.1f} ms")
+        if args.graph and graph is None:   # captured once (a capture records, it runs nothing): every further update is one replay
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                reward, stats, weights = iteration()
+    env.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=256)
@@ -109,7 +165,18 @@ def main():
     ap.add_argument("--torch", action="store_true", help="the same losses in torch autograd")
     ap.add_argument("--device-update", action="store_true", help="the whole update phase in one call: env.sac_update with a SACOptimizer")
     ap.add_argument("--graph", action="store_true", help="--device-update with collect + add + sac_update captured once and replayed")
+    ap.add_argument("--per", action="store_true", help="prioritised replay: the piecewise loop on the device (per_loop)")
+    ap.add_argument("--alpha", type=float, default=0.6, help="--per: the priorities' exponent")
+    ap.add_argument("--beta", type=float, default=0.4, help="--per: the importance weights' exponent")
+    ap.add_argument("--n-step", type=int, default=1, help="n-step transitions (1 .. 16); above 1 the piecewise loop on the device")
     args = ap.parse_args()
+    if args.per or args.n_step != 1:
+        if args.device_update:
+            ap.error("--per and --n-step are not available with --device-update: the fused update phase does not take priorities or per-row "
+                     "discounts yet; leave --device-update out (--graph still captures the whole piecewise iteration)")
+        if args.torch:
+            ap.error("--per / --n-step and --torch exclude each other")
+        return per_loop(args)
     if args.device_update or args.graph:
         if args.torch:
             ap.error("--device-update / --graph and --torch exclude each other")

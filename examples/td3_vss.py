@@ -1,7 +1,7 @@
 """TD3 / DDPG on VSS-v0 with the rollouts collected in one launch and the gradients of a replayed minibatch computed by the engine.
 
     python examples/td3_vss.py [--envs 256] [--steps 16] [--updates 10] [--grad-steps 8] [--batch 256] [--ddpg] [--torch]
-                               [--device-update] [--graph]
+                               [--device-update] [--graph] [--per [--alpha A --beta B]] [--n-step N]
 
 One update: env.collect(...) advances the envs `steps` steps under the current actor with Gaussian exploration noise of standard
 deviation --exploration (the engine clips the noisy sample: that is the executed action), ReplayBuffer.add() stores the T * B transitions
@@ -11,7 +11,10 @@ four launches, torch's Adam steps on the flat parameter vectors (the leaves), an
 target smoothing, no delay.  --torch runs the same update with torch modules and autograd instead (torch_losses below: what
 tools/bench_dpg_grad.py times the engine against).  --device-update replaces the whole gradient-step loop by ONE call, env.dpg_update
 with a DPGOptimizer (rows from the engine's generator, Adam and the Polyak step on the device); --graph captures collect + add +
-dpg_update once and replays them (device_update below).  A demonstration of the call pattern, not a tuned trainer."""
+dpg_update once and replays them (device_update below).  --per and --n-step N keep the transitions in a PrioritizedReplayBuffer and
+run the piecewise loop on the device (per_loop below): buf.sample, env.dpg_gradient(weights=..., return_td_error=True), opt.step,
+buf.update_priorities; with --graph that loop is captured once, with collect and buf.add.  The fused phase (--device-update) does not
+take priorities or per-row discounts yet.  A demonstration of the call pattern, not a tuned trainer."""
 import argparse
 import math
 import os
@@ -23,7 +26,7 @@ import torch
 
 from rsoccer_amd.vec import VecVSSEnv
 from rsoccer_amd.vec.policy import MLPPolicy, MLPQCritic
-from rsoccer_amd.vec.replay import ReplayBuffer
+from rsoccer_amd.vec.replay import PrioritizedReplayBuffer, ReplayBuffer
 
 
 def mlp(n_in, n_out, out_tanh):
@@ -108,6 +111,63 @@ def device_update(args, C, sigma, delay):
     env.close()
 
 
+def per_loop(args, C, sigma, delay):
+    """--per / --n-step: prioritised and n-step replay, every piece on the device.  Without --per the priorities play no part
+    (alpha = 0 makes every leaf 1, beta = 0 every weight 1) and only the n-step fold and its per-row discounts remain.  --graph: one
+    whole update captured once on a device-keyed env and replayed; the optimiser's step count on the device keys every draw."""
+    from rsoccer_amd.vec.optim import DPGOptimizer
+    if args.grad_steps % delay:
+        raise SystemExit(f"--grad-steps ({args.grad_steps}) must be a multiple of --policy-delay ({delay})")
+    torch.manual_seed(args.seed)
+    env = VecVSSEnv(args.envs, device=0, seed=args.seed)
+    dev, OD, AD = env.device, env.sim.obs_dim, env.sim.act_dim
+    pol = MLPPolicy(OD, AD, hidden=64, layers=2, hidden_act="tanh", out_act="tanh")
+    qnet = MLPQCritic(OD, AD, hidden=64, layers=2, hidden_act="tanh")
+    p_actor = pol.from_module(mlp(OD, AD, True)).to(dev)
+    p_critics = torch.stack([qnet.from_module(mlp(OD + AD, 1, False)) for _ in range(C)]).to(dev)
+    t_actor, t_critics = p_actor.clone(), p_critics.clone()
+    opt = DPGOptimizer(pol, qnet, C, device=dev, lr_actor=args.lr, lr_critic=args.lr, tau=args.tau)
+    buf = PrioritizedReplayBuffer(args.capacity, OD, AD, dev, alpha=args.alpha if args.per else 0.0, n_step=args.n_step, gamma=args.gamma)
+    beta = args.beta if args.per else 0.0
+    log_std = torch.full((AD,), math.log(args.exploration), device=dev)
+    env.reset()
+    if args.graph:
+        env.enable_graph_capture()
+
+    def iteration():
+        batch = env.collect(pol, p_actor, args.steps, log_std=log_std, noise_seed=args.seed + 2, return_final_obs=True)
+        buf.add(batch)
+        data = buf.data()   # carries "discount": the targets use each row's own gamma^m
+        for j in range(args.grad_steps):
+            with_actor = (j + 1) % delay == 0
+            rows, weights = buf.sample(args.batch, beta=beta, seed=args.seed + 1, step=opt.steps)
+            out = env.dpg_gradient(data, pol, p_actor, t_actor, qnet, p_critics, t_critics, rows=rows, gamma=args.gamma, target_noise=sigma,
+                                   noise_clip=args.noise_clip, noise_seed=args.seed + 1, noise_step=opt.steps, actor=with_actor,
+                                   weights=weights, return_td_error=True)
+            opt.step(p_actor, t_actor, p_critics, t_critics, out["grad_params"] if with_actor else None, out["grad_critic_params"])
+            buf.update_priorities(rows, out["td_error"])
+        return batch["reward"].mean(), out["stats"], weights
+
+    graph = None
+    for update in range(args.updates):
+        t0 = time.perf_counter()
+        if graph is not None:
+            graph.replay()
+        else:
+            reward, stats, weights = iteration()   # (eager; with --graph also the warm-up before the capture)
+        torch.cuda.synchronize()
+        m = env.metrics()
+        print(f"update {update}: mean reward / step {float(reward):+.5f}, episodes {m['episodes']}, goals for / against "
+              f"{m['goals_for']} / {m['goals_against']}, buffer {int(buf.fill)} rows, gradient steps {int(opt.steps)}, loss_q "
+              f"{float(stats['loss_q0'] + stats['loss_q1']):.5f}, largest priority {float(buf.max_priority()):.4f}, smallest weight "
+              f"{float(weights.min()):.4f}; collect + add + {args.grad_steps} gradient steps {(time.perf_counter() - t0) * 1e3:.1f} ms")
+        if args.graph and graph is None:   # captured once (a capture records, it runs nothing): every further update is one replay
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                reward, stats, weights = iteration()
+    env.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=256)
@@ -128,8 +188,19 @@ def main():
     ap.add_argument("--torch", action="store_true", help="the same update in torch autograd")
     ap.add_argument("--device-update", action="store_true", help="the whole update phase in one call: env.dpg_update with a DPGOptimizer")
     ap.add_argument("--graph", action="store_true", help="--device-update with collect + add + dpg_update captured once and replayed")
+    ap.add_argument("--per", action="store_true", help="prioritised replay: the piecewise loop on the device (per_loop)")
+    ap.add_argument("--alpha", type=float, default=0.6, help="--per: the priorities' exponent")
+    ap.add_argument("--beta", type=float, default=0.4, help="--per: the importance weights' exponent")
+    ap.add_argument("--n-step", type=int, default=1, help="n-step transitions (1 .. 16); above 1 the piecewise loop on the device")
     args = ap.parse_args()
     C, sigma, delay = (1, 0.0, 1) if args.ddpg else (2, args.target_noise, args.policy_delay)
+    if args.per or args.n_step != 1:
+        if args.device_update:
+            ap.error("--per and --n-step are not available with --device-update: the fused update phase does not take priorities or per-row "
+                     "discounts yet; leave --device-update out (--graph still captures the whole piecewise iteration)")
+        if args.torch:
+            ap.error("--per / --n-step and --torch exclude each other")
+        return per_loop(args, C, sigma, delay)
     if args.device_update or args.graph:
         if args.torch:
             ap.error("--device-update / --graph and --torch exclude each other")

@@ -1379,6 +1379,126 @@ int rsx_task_sac_update(rsx_sim* h, const rsx_policy_mlp* actor, float* actor_pa
                         const rsx_sac_cfg* cfg, const rsx_sac_update_cfg* u, const rsx_sac_adam_cfg* adam, const rsx_sac_adam_state* st,
                         float* stats_dev, void* workspace, void* stream);
 
+/* ---- prioritised and n-step replay on the device (additive extension of ABI 6) --------------------------------------------------------
+ * The ring of transitions that rsx_task_dpg_gradient and rsx_task_sac_gradient read, filled with n-step transitions and drawn from in
+ * proportion to per-row priorities, with everything an off-policy trainer keeps around it on the device.  No call here takes a handle:
+ * they run on the thread's current device.  Every call is stream-ordered, never synchronises, never allocates and is capturable; invalid
+ * arguments are refused with RSX_ERR_ARG before anything is enqueued (rsx_last_error says why); no atomic on floating-point numbers: the
+ * result bits are a function of the inputs alone; no kernel uses scratch memory.  The number of launches of a call depends on the
+ * capacity only.
+ *
+ * rsx_replay_add_nstep:  folds a [T][B] batch, as rsx_task_collect_* records it with final_obs, into n-step transitions and writes them
+ * into the ring at the device's write head, in one launch.  Row (t, b) lands at (head + t * B + b) % capacity (step-major); then head :=
+ * (head + T * B) % capacity and fill := min(fill + T * B, capacity), on the device.  With done(s) = terminated[s][b] | truncated[s][b]:
+ *   m            starts at 1 and grows by one while !done(t + m - 1) and m < n_step and t + m < T: a window never crosses an episode end
+ *                or the end of the batch, so the tail rows of a batch get fewer steps and a larger discount
+ *   reward       R = r[t];  g = gamma;  then for k = 1 .. m - 1:  R = R + g * r[t + k];  g = g * gamma   — float32, every operation
+ *                rounded (no fused multiply-add), in this order
+ *   discount     g after the loop: gamma^m as that running product (gamma itself for m = 1)
+ *   terminated   terminated[t + m - 1][b] != 0
+ *   next_obs     done(t + m - 1): final_obs[t + m - 1][b];  else t + m < T: obs[t + m][b];  else the batch's next_obs[b]
+ *   obs, action  those of (t, b)
+ * With n_step = 1 the obs, action, reward, next_obs and terminated bytes are what a one-step ring stores, and discount is gamma.
+ *   ticket_dev   int32 [1] device memory, 0 before the first call and between calls (the workgroup that finishes last advances head and
+ *                fill and clears it): RSX_REPLAY_STATE_TICKET of a state block will do.
+ * Refused: a null batch, ring or member; T < 1, B < 1; T * B > capacity; capacity < 1 or > 2^31 - 1; obs_dim or act_dim < 1; n_step
+ * outside 1 .. 16; gamma outside [0, 1] or not finite. */
+typedef struct rsx_replay_batch {
+    const float*   obs;         /* [T][B][obs_dim] */
+    const float*   actions;     /* [T][B][act_dim] */
+    const float*   reward;      /* [T][B] */
+    const uint8_t* terminated;  /* [T][B] */
+    const uint8_t* truncated;   /* [T][B] */
+    const float*   final_obs;   /* [T][B][obs_dim] */
+    const float*   next_obs;    /* [B][obs_dim] */
+    int32_t        T;
+    int32_t        B;
+} rsx_replay_batch;
+typedef struct rsx_replay_ring {
+    float*   obs;         /* [capacity][obs_dim] */
+    float*   actions;     /* [capacity][act_dim] */
+    float*   reward;      /* [capacity] */
+    float*   next_obs;    /* [capacity][obs_dim] */
+    uint8_t* terminated;  /* [capacity] */
+    float*   discount;    /* [capacity] */
+    int64_t* head_dev;    /* [1] the next row to write */
+    int64_t* fill_dev;    /* [1] rows that hold a transition */
+    int32_t* ticket_dev;  /* [1] */
+    int64_t  capacity;
+    int32_t  obs_dim;
+    int32_t  act_dim;
+} rsx_replay_ring;
+int rsx_replay_add_nstep(const rsx_replay_batch* batch, const rsx_replay_ring* ring, int n_step, float gamma, void* stream);
+/* The sum structure over per-row priorities: a tree of fan-out 64 in one float32 array.
+ *   levels   level 0 holds the capacity leaves, level l + 1 one node per 64 entries of level l, up to the first level above the leaves
+ *            that has one node, the root (a capacity of 1 .. 64 has the leaves and the root).  Every level is padded to a multiple of 64
+ *            floats; the padding stays 0.  Level l starts where level l - 1 ends.  rsx_replay_tree_geometry gives the floats of the
+ *            whole array, the index `levels` of the root's level and each level's first float (offsets_out [8], -1 past the root).
+ *   leaf     priority^alpha; a row behind the fill count holds 0 (the array starts zeroed and only rsx_replay_set_priorities writes it)
+ *   node     ((c_0 + c_1) + c_2) + ... + c_63 over its 64 children in float32, from c_0, every addition rounded.  A node is always
+ *            recomputed from its children, never adjusted by a difference, so the tree never drifts from its leaves.
+ *   state    RSX_REPLAY_STATE_WORDS 32-bit words of device memory: */
+#define RSX_REPLAY_STATE_MAX     0   /* f32: the running maximum leaf value; 1.0f at the start, it only grows */
+#define RSX_REPLAY_STATE_WMAX    1   /* f32: the last draw's largest weight before the division */
+#define RSX_REPLAY_STATE_SKIPPED 2   /* i32: entries of rsx_replay_set_priorities skipped for their index, since the state was zeroed */
+#define RSX_REPLAY_STATE_TICKET  3   /* i32: rsx_replay_add_nstep's ticket */
+#define RSX_REPLAY_STATE_WORDS   4
+/* rsx_replay_set_priorities:  leaf[rows[t]] := (|td_error[t]| + eps)^alpha for the m entries, powf of the device's math library on
+ * float32 (a NaN td_error counts as 0; the value is capped at FLT_MAX), and the running maximum is raised to the largest value written.
+ * With td_error_dev == NULL the leaf gets the running maximum instead: what newly added rows get.  With rows_dev == NULL the rows are
+ * the m rows behind the write head, (head - m + t) mod capacity with head read from head_dev on the device: rsx_replay_add_nstep
+ * followed by this call with m = T * B and both NULL is a prioritised ring's add().
+ *   skipped      an index outside [0, capacity) (-1 included) is skipped: nothing is read or written for it, and it is counted in
+ *                state[RSX_REPLAY_STATE_SKIPPED]
+ *   duplicates   where an index occurs more than once the largest value wins, so the result does not depend on the order
+ *   launches     2 + levels: the touched leaves cleared; raised to their values (an integer maximum of the bit patterns, whose order is
+ *                that of the values for floats >= 0); then per level, bottom up, every ancestor of a touched leaf recomputed
+ * Refused: a null tree_dev or state_dev; rows_dev and head_dev both null; capacity < 1 or > 2^31 - 1; m < 1 or m > 2^31 - 1; m >
+ * capacity with rows_dev == NULL; alpha or eps negative or not finite. */
+int rsx_replay_tree_geometry(int64_t capacity, int64_t* floats_out, int32_t* levels_out, int64_t* offsets_out /* [8] or NULL */);
+int rsx_replay_set_priorities(float* tree_dev, void* state_dev, int64_t capacity, const int32_t* rows_dev, const float* td_error_dev,
+                              const int64_t* head_dev, int64_t m, float alpha, float eps, void* stream);
+/* rsx_replay_sample_prioritized:  m stratified draws in proportion to the leaves, with their importance weights.
+ *   word     entry t takes word t & 3 of philox4x32-7(counter = (t >> 2, step >> 32, step & 0xFFFFFFFF, 14), key = (seed lo, seed hi)):
+ *            rsx_replay_sample_rows' counter shape under a domain word of its own, 14 (1 and 3 .. 13 are taken)
+ *   target   u = total * ((t + word * 2^-32) / m) in float64, in this order; total is the root as a double
+ *   descent  from the root down, at a node with children c_0 .. c_63 and the float32 running sums p_j = p_(j-1) + c_j (p_(-1) = 0, the
+ *            node's own additions): the child is the smallest j with c_j > 0 and u < p_j (p_j widened); if there is none, the largest j
+ *            with c_j > 0.  Then u := u - p_(j-1) in float64.  An entry therefore never returns a leaf that holds 0, even when rounding
+ *            pushes u to the total or past a node's last child.
+ *   weights  w_t = powf(((float)fill * leaf) / total, -beta) in float32, then divided by the largest w of the call's entries
+ *            (a second launch; the largest is kept in state[RSX_REPLAY_STATE_WMAX])
+ *   empty    with fill == 0 or a total that is not > 0, every index is -1 and every weight 0
+ *   fill, step   as for rsx_replay_sample_rows (fill clamped to [0, capacity]);  beta: the argument, or with beta_dev != NULL the float it
+ *            points to, read on the device, so a replayed graph anneals beta and draws anew
+ *   launches 2, behind a 4-byte memset node that clears the largest weight
+ * Refused: a null tree_dev, state_dev, rows_out or weights_out; capacity or m outside 1 .. 2^31 - 1; a negative fill with fill_dev ==
+ * NULL; beta negative or not finite (with beta_dev == NULL). */
+int rsx_replay_sample_prioritized(const float* tree_dev, void* state_dev, int64_t capacity, int64_t fill, const int64_t* fill_dev,
+                                  int32_t* rows_out, float* weights_out, int64_t m, float beta, const float* beta_dev, uint64_t seed,
+                                  int64_t step, const int64_t* step_dev, void* stream);
+/* rsx_task_dpg_gradient_w, rsx_task_sac_gradient_w:  rsx_task_dpg_gradient and rsx_task_sac_gradient with per-row discounts, per-entry
+ * importance weights and the per-entry TD error.  Every member of rsx_grad_per may be NULL, per == NULL is all three NULL, and with all
+ * three NULL the call is the plain one, bit for bit (the plain entry points are these with per == NULL).
+ *   discount   [N], by ROW: replaces cfg->gamma in the target, y = terminated ? r : r + discount[row] * (...); cfg->gamma is still checked
+ *   weight     [M], by POSITION in the minibatch: scales the critic loss only.  dL_q/dQ_c = ((Q_c - y) * w_t) * (1 / M), in this order,
+ *              so a weight of exactly 1 leaves the bits alone; stats L_q becomes 0.5 * mean(w (Q_c - y)^2), summed as (w_t * d) * d.
+ *              The actor's loss and the temperature's stay unweighted.
+ *   td_error   [M], out: max over c of |Q_c - y| from the per-entry q and target the call writes, 0 for a skipped entry; one more
+ *              launch.  Needs out->q and out->target. */
+typedef struct rsx_grad_per {
+    const float* discount;  /* [N] or NULL */
+    const float* weight;    /* [M] or NULL */
+    float*       td_error;  /* [M] or NULL */
+} rsx_grad_per;
+int rsx_task_dpg_gradient_w(rsx_sim* h, const rsx_policy_mlp* actor, const float* actor_params_dev, const float* target_actor_params_dev,
+                            const rsx_policy_mlp* critic, const float* critic_params_dev, const float* target_critic_params_dev,
+                            const rsx_dpg_in* in, const rsx_dpg_cfg* cfg, const rsx_dpg_out* out, const rsx_grad_per* per, void* stream);
+int rsx_task_sac_gradient_w(rsx_sim* h, const rsx_policy_mlp* actor, const float* actor_params_dev,
+                            const rsx_policy_mlp* critic, const float* critic_params_dev, const float* target_critic_params_dev,
+                            const float* log_alpha_dev /* [1] */, const rsx_dpg_in* in, const rsx_sac_cfg* cfg,
+                            const rsx_sac_out* out, const rsx_grad_per* per, void* stream);
+
 /* Debugging aid: number of non-finite floats in the state rows and, with a task attached, in the
  * observations, rewards and info rows.  Synchronises `stream`.  With RSX_DEBUG_FINITE=1 in the
  * environment every stepping call (rsx_step_dev, rsx_task_step, rsx_task_step_n, rsx_task_rollout, rsx_task_collect_policy)

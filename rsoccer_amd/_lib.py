@@ -60,6 +60,8 @@ SYMBOLS = (
     "rsx_sac_gradient_workspace", "rsx_task_sac_gradient",
     "rsx_replay_sample_rows", "rsx_dpg_adam_step", "rsx_dpg_update_workspace", "rsx_task_dpg_update",
     "rsx_sac_adam_step", "rsx_sac_update_workspace", "rsx_task_sac_update",
+    "rsx_replay_add_nstep", "rsx_replay_tree_geometry", "rsx_replay_set_priorities", "rsx_replay_sample_prioritized",
+    "rsx_task_dpg_gradient_w", "rsx_task_sac_gradient_w",
 )
 # activations of rsx_policy_mlp (include/rsx.h: RSX_ACT_*)
 ACT_RELU, ACT_TANH, ACT_CLIP = 0, 1, 2
@@ -265,6 +267,30 @@ class DpgUpdateCfg(C.Structure):
     _fields_ = [("fill_dev", C.c_void_p), ("seed", C.c_uint64), ("fill", C.c_int64), ("grad_steps", C.c_int32), ("policy_delay", C.c_int32)]
 
 
+# prioritised and n-step replay (include/rsx.h: rsx_replay_add_nstep, rsx_replay_set_priorities, rsx_replay_sample_prioritized)
+# the 32-bit words of a state block (RSX_REPLAY_STATE_*)
+REPLAY_STATE = ("max", "wmax", "skipped", "ticket")
+
+
+class ReplayBatch(C.Structure):
+    """rsx_replay_batch (include/rsx.h): the arrays of a collected [T][B] batch with final_obs; device addresses"""
+    _fields_ = [("obs", C.c_void_p), ("actions", C.c_void_p), ("reward", C.c_void_p), ("terminated", C.c_void_p), ("truncated", C.c_void_p),
+                ("final_obs", C.c_void_p), ("next_obs", C.c_void_p), ("T", C.c_int32), ("B", C.c_int32)]
+
+
+class ReplayRing(C.Structure):
+    """rsx_replay_ring (include/rsx.h): the ring's arrays, its head and fill counts and the add's ticket on the device, and its shape"""
+    _fields_ = [("obs", C.c_void_p), ("actions", C.c_void_p), ("reward", C.c_void_p), ("next_obs", C.c_void_p), ("terminated", C.c_void_p),
+                ("discount", C.c_void_p), ("head_dev", C.c_void_p), ("fill_dev", C.c_void_p), ("ticket_dev", C.c_void_p),
+                ("capacity", C.c_int64), ("obs_dim", C.c_int32), ("act_dim", C.c_int32)]
+
+
+class GradPer(C.Structure):
+    """rsx_grad_per (include/rsx.h): the rows' discounts [N], the entries' weights [M] and the TD error [M] (out) of the weighted
+    gradient calls; device addresses, each may be None"""
+    _fields_ = [("discount", C.c_void_p), ("weight", C.c_void_p), ("td_error", C.c_void_p)]
+
+
 # the soft actor-critic update phase (include/rsx.h: rsx_sac_adam_step, rsx_task_sac_update)
 SAC_ADAM_WORKSPACE_BYTES = 2048
 # the slots of rsx_sac_adam_state.counters (RSX_SAC_*), of rsx_sac_adam_io.stats, and of one row of rsx_task_sac_update's stats
@@ -439,6 +465,15 @@ def load():
                                              C.POINTER(C.c_int64)]
     lib.rsx_task_sac_update.argtypes = [vp, C.POINTER(PolicyMLP), vp, C.POINTER(PolicyMLP), vp, vp, vp, C.POINTER(DpgIn), C.POINTER(SacCfg),
                                         C.POINTER(SacUpdateCfg), C.POINTER(SacAdamCfg), C.POINTER(SacAdamState), vp, vp, vp]
+    lib.rsx_replay_add_nstep.argtypes = [C.POINTER(ReplayBatch), C.POINTER(ReplayRing), ip, C.c_float, vp]
+    lib.rsx_replay_tree_geometry.argtypes = [C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    lib.rsx_replay_set_priorities.argtypes = [vp, vp, C.c_int64, vp, vp, vp, C.c_int64, C.c_float, C.c_float, vp]
+    lib.rsx_replay_sample_prioritized.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp, vp, C.c_int64, C.c_float, vp, C.c_uint64, C.c_int64,
+                                                  vp, vp]
+    lib.rsx_task_dpg_gradient_w.argtypes = [vp, C.POINTER(PolicyMLP), vp, vp, C.POINTER(PolicyMLP), vp, vp, C.POINTER(DpgIn), C.POINTER(DpgCfg),
+                                            C.POINTER(DpgOut), C.POINTER(GradPer), vp]
+    lib.rsx_task_sac_gradient_w.argtypes = [vp, C.POINTER(PolicyMLP), vp, C.POINTER(PolicyMLP), vp, vp, vp, C.POINTER(DpgIn), C.POINTER(SacCfg),
+                                            C.POINTER(SacOut), C.POINTER(GradPer), vp]
     lib.rsx_physics_defaults.argtypes = [ip, vp]
     lib.rsx_physics_derive.argtypes = [ip, ip, vp, vp]
     lib.rsx_physics_enable.argtypes = [vp, vp]
@@ -511,6 +546,41 @@ def replay_sample_rows(rows_ptr, m, n_batch_rows, fill, fill_ptr, seed, step, st
     (seed, step or the int64 at step_ptr); -1 everywhere on an empty ring"""
     rc = load().rsx_replay_sample_rows(rows_ptr, int(m), int(n_batch_rows), int(fill), fill_ptr, int(seed) & ((1 << 64) - 1), int(step),
                                        step_ptr, stream)
+    if rc:
+        _chk(rc)
+
+
+def replay_add_nstep(batch, ring, n_step, gamma, stream=None):
+    """rsx_replay_add_nstep: the [T][B] batch (a ReplayBatch) folded into n-step transitions and written into the ring (a ReplayRing)
+    at the device's write head, in one launch; head and fill advance on the device"""
+    rc = load().rsx_replay_add_nstep(None if batch is None else C.byref(batch), None if ring is None else C.byref(ring), int(n_step),
+                                     float(gamma), stream)
+    if rc:
+        _chk(rc)
+
+
+def replay_tree_geometry(capacity):
+    """rsx_replay_tree_geometry: (floats of the priority tree's array, the root's level, each level's first float)"""
+    floats, levels, off = C.c_int64(0), C.c_int32(0), (C.c_int64 * 8)()
+    _chk(load().rsx_replay_tree_geometry(int(capacity), C.byref(floats), C.byref(levels), off))
+    return int(floats.value), int(levels.value), [int(o) for o in off[:levels.value + 1]]
+
+
+def replay_set_priorities(tree_ptr, state_ptr, capacity, rows_ptr, td_error_ptr, head_ptr, m, alpha, eps, stream=None):
+    """rsx_replay_set_priorities: leaf[rows[t]] := (|td_error[t]| + eps)^alpha (td_error_ptr None: the running maximum; rows_ptr None:
+    the m rows behind the write head at head_ptr), the largest value where rows repeat, and the touched ancestors recomputed"""
+    rc = load().rsx_replay_set_priorities(tree_ptr, state_ptr, int(capacity), rows_ptr, td_error_ptr, head_ptr, int(m), float(alpha),
+                                          float(eps), stream)
+    if rc:
+        _chk(rc)
+
+
+def replay_sample_prioritized(tree_ptr, state_ptr, capacity, fill, fill_ptr, rows_ptr, weights_ptr, m, beta, beta_ptr, seed, step, step_ptr,
+                              stream=None):
+    """rsx_replay_sample_prioritized: rows [m] int32 and weights [m] float32 := stratified draws in proportion to the tree's leaves and
+    their importance weights over the largest; -1 and 0 everywhere on an empty ring"""
+    rc = load().rsx_replay_sample_prioritized(tree_ptr, state_ptr, int(capacity), int(fill), fill_ptr, rows_ptr, weights_ptr, int(m),
+                                              float(beta), beta_ptr, int(seed) & ((1 << 64) - 1), int(step), step_ptr, stream)
     if rc:
         _chk(rc)
 
@@ -963,6 +1033,16 @@ class Sim:
         if rc:
             _chk(rc)
 
+    def task_dpg_gradient_w(self, actor, actor_params_ptr, target_actor_params_ptr, critic, critic_params_ptr, target_critic_params_ptr, inp,
+                            cfg, out, per, stream=None):
+        """rsx_task_dpg_gradient_w: task_dpg_gradient with ``per``, a GradPer: per-row discounts in the target, per-entry weights on the
+        critic loss and the per-entry TD error (one more launch)"""
+        b = lambda x: None if x is None else C.byref(x)   # noqa: E731
+        rc = self._lib.rsx_task_dpg_gradient_w(self._h, b(actor), actor_params_ptr, target_actor_params_ptr, b(critic), critic_params_ptr,
+                                               target_critic_params_ptr, b(inp), b(cfg), b(out), b(per), stream)
+        if rc:
+            _chk(rc)
+
     def sac_gradient_workspace(self, actor, critic, n_critics, n_rows, max_workgroups=0):
         """rsx_sac_gradient_workspace: bytes of scratch rsx_task_sac_gradient needs for a minibatch of ``n_rows`` rows"""
         n = C.c_int64(0)
@@ -979,6 +1059,16 @@ class Sim:
         b = lambda x: None if x is None else C.byref(x)   # noqa: E731
         rc = self._lib.rsx_task_sac_gradient(self._h, b(actor), actor_params_ptr, b(critic), critic_params_ptr, target_critic_params_ptr,
                                              log_alpha_ptr, b(inp), b(cfg), b(out), stream)
+        if rc:
+            _chk(rc)
+
+    def task_sac_gradient_w(self, actor, actor_params_ptr, critic, critic_params_ptr, target_critic_params_ptr, log_alpha_ptr, inp, cfg, out,
+                            per, stream=None):
+        """rsx_task_sac_gradient_w: task_sac_gradient with ``per``, a GradPer: per-row discounts in the target, per-entry weights on the
+        critic loss and the per-entry TD error (one more launch)"""
+        b = lambda x: None if x is None else C.byref(x)   # noqa: E731
+        rc = self._lib.rsx_task_sac_gradient_w(self._h, b(actor), actor_params_ptr, b(critic), critic_params_ptr, target_critic_params_ptr,
+                                               log_alpha_ptr, b(inp), b(cfg), b(out), b(per), stream)
         if rc:
             _chk(rc)
 

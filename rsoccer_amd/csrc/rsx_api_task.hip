@@ -679,9 +679,22 @@ int rsx_dpg_gradient_workspace(const rsx_sim* h, const rsx_policy_mlp* actor, co
     return RSX_OK;
 }
 
+// what the weighted calls check of rsx_grad_per against the per-entry outputs (q, target) the TD error is computed from
+static int grad_per_check(const rsx_grad_per* per, const float* q, const float* target) {
+    if (per && per->td_error && (!q || !target)) return fail(RSX_ERR_ARG, "per->td_error needs out->q and out->target: it is computed from them");
+    return RSX_OK;
+}
+
 int rsx_task_dpg_gradient(rsx_sim* h, const rsx_policy_mlp* actor, const float* actor_params_dev, const float* target_actor_params_dev,
                           const rsx_policy_mlp* critic, const float* critic_params_dev, const float* target_critic_params_dev,
                           const rsx_dpg_in* in, const rsx_dpg_cfg* cfg, const rsx_dpg_out* out, void* stream) {
+    return rsx_task_dpg_gradient_w(h, actor, actor_params_dev, target_actor_params_dev, critic, critic_params_dev, target_critic_params_dev, in,
+                                   cfg, out, nullptr, stream);
+}
+
+int rsx_task_dpg_gradient_w(rsx_sim* h, const rsx_policy_mlp* actor, const float* actor_params_dev, const float* target_actor_params_dev,
+                            const rsx_policy_mlp* critic, const float* critic_params_dev, const float* target_critic_params_dev,
+                            const rsx_dpg_in* in, const rsx_dpg_cfg* cfg, const rsx_dpg_out* out, const rsx_grad_per* per, void* stream) {
     RSX_ENTER(h);   // (nothing the handle owns is read or written by the launches)
     if (!cfg) return fail(RSX_ERR_ARG, "cfg must not be null");
     PolicySpec SA, SC; int64_t na = 0, nc = 0;
@@ -698,8 +711,10 @@ int rsx_task_dpg_gradient(rsx_sim* h, const rsx_policy_mlp* actor, const float* 
     if (cfg->max_workgroups < 0) return fail(RSX_ERR_ARG, "max_workgroups must be >= 0");
     if (!out || !out->grad_critics || !out->stats || !out->workspace)
         return fail(RSX_ERR_ARG, "out and its grad_critics, stats and workspace must not be null");
+    if (int rc = grad_per_check(per, out->q, out->target)) return rc;
     launch_dpg_gradient(SA, na, actor_params_dev, target_actor_params_dev, SC, nc, critic_params_dev, target_critic_params_dev, h->P.obs_dim,
-                        h->M.act_dim, *in, *cfg, *out, (hipStream_t)stream);
+                        h->M.act_dim, *in, *cfg, *out, (hipStream_t)stream, per);
+    if (per && per->td_error) launch_replay_td_error(out->q, out->target, cfg->n_critics, in->n_rows, per->td_error, (hipStream_t)stream);
     HIP_TRY(launch_status());
     return RSX_OK;
 }
@@ -751,6 +766,13 @@ int rsx_sac_gradient_workspace(const rsx_sim* h, const rsx_policy_mlp* actor, co
 int rsx_task_sac_gradient(rsx_sim* h, const rsx_policy_mlp* actor, const float* actor_params_dev, const rsx_policy_mlp* critic,
                           const float* critic_params_dev, const float* target_critic_params_dev, const float* log_alpha_dev,
                           const rsx_dpg_in* in, const rsx_sac_cfg* cfg, const rsx_sac_out* out, void* stream) {
+    return rsx_task_sac_gradient_w(h, actor, actor_params_dev, critic, critic_params_dev, target_critic_params_dev, log_alpha_dev, in, cfg, out,
+                                   nullptr, stream);
+}
+
+int rsx_task_sac_gradient_w(rsx_sim* h, const rsx_policy_mlp* actor, const float* actor_params_dev, const rsx_policy_mlp* critic,
+                            const float* critic_params_dev, const float* target_critic_params_dev, const float* log_alpha_dev,
+                            const rsx_dpg_in* in, const rsx_sac_cfg* cfg, const rsx_sac_out* out, const rsx_grad_per* per, void* stream) {
     RSX_ENTER(h);   // (nothing the handle owns is read or written by the launches)
     if (!cfg) return fail(RSX_ERR_ARG, "cfg must not be null");
     PolicySpec SA, SC; int64_t na = 0, nc = 0;
@@ -768,8 +790,10 @@ int rsx_task_sac_gradient(rsx_sim* h, const rsx_policy_mlp* actor, const float* 
     if (cfg->max_workgroups < 0) return fail(RSX_ERR_ARG, "max_workgroups must be >= 0");
     if (!out || !out->grad_actor || !out->grad_critics || !out->grad_log_alpha || !out->stats || !out->workspace)
         return fail(RSX_ERR_ARG, "out and its grad_actor, grad_critics, grad_log_alpha, stats and workspace must not be null");
+    if (int rc = grad_per_check(per, out->q, out->target)) return rc;
     launch_sac_gradient(SA, na, actor_params_dev, SC, nc, critic_params_dev, target_critic_params_dev, log_alpha_dev, h->P.obs_dim,
-                        h->M.act_dim, *in, *cfg, *out, (hipStream_t)stream);
+                        h->M.act_dim, *in, *cfg, *out, (hipStream_t)stream, per);
+    if (per && per->td_error) launch_replay_td_error(out->q, out->target, cfg->n_critics, in->n_rows, per->td_error, (hipStream_t)stream);
     HIP_TRY(launch_status());
     return RSX_OK;
 }
@@ -865,6 +889,67 @@ int rsx_task_dpg_update(rsx_sim* h, const rsx_policy_mlp* actor, float* actor_pa
     if (!stats_dev || !workspace) return fail(RSX_ERR_ARG, "stats_dev and workspace must not be null");
     launch_dpg_update(SA, na, actor_params_dev, target_actor_params_dev, SC, nc, critic_params_dev, target_critic_params_dev, h->P.obs_dim,
                       h->M.act_dim, *in, *cfg, *u, *adam, *st, stats_dev, workspace, (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
+// ---- prioritised and n-step replay (rsx.h: rsx_replay_add_nstep, rsx_replay_set_priorities, rsx_replay_sample_prioritized) ----
+int rsx_replay_add_nstep(const rsx_replay_batch* b, const rsx_replay_ring* r, int n_step, float gamma, void* stream) {
+    (void)launch_status();
+    if (!b || !b->obs || !b->actions || !b->reward || !b->terminated || !b->truncated || !b->final_obs || !b->next_obs)
+        return fail(RSX_ERR_ARG, "the batch and its obs, actions, reward, terminated, truncated, final_obs and next_obs arrays must not be null");
+    if (!r || !r->obs || !r->actions || !r->reward || !r->next_obs || !r->terminated || !r->discount || !r->head_dev || !r->fill_dev || !r->ticket_dev)
+        return fail(RSX_ERR_ARG, "the ring and its obs, actions, reward, next_obs, terminated, discount, head_dev, fill_dev and ticket_dev must not be null");
+    if (r->capacity < 1 || r->capacity > 0x7FFFFFFFll) return fail(RSX_ERR_ARG, "capacity must be in 1 .. 2^31 - 1");
+    if (r->obs_dim < 1 || r->act_dim < 1) return fail(RSX_ERR_ARG, "obs_dim and act_dim must be >= 1");
+    if (b->T < 1 || b->B < 1) return fail(RSX_ERR_ARG, "T and B must be >= 1");
+    if ((long long)b->T * b->B > r->capacity) return fail(RSX_ERR_ARG, "the batch has more rows (T * B) than the ring's capacity");
+    if (n_step < 1 || n_step > 16) return fail(RSX_ERR_ARG, "n_step must be in 1 .. 16");
+    if (!(std::isfinite(gamma) && gamma >= 0.0f && gamma <= 1.0f)) return fail(RSX_ERR_ARG, "gamma must be in [0, 1]");
+    launch_replay_add_nstep(*b, *r, n_step, gamma, (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
+int rsx_replay_tree_geometry(int64_t capacity, int64_t* floats_out, int32_t* levels_out, int64_t* offsets_out) {
+    if (capacity < 1 || capacity > 0x7FFFFFFFll) return fail(RSX_ERR_ARG, "capacity must be in 1 .. 2^31 - 1");
+    long long floats = 0, off[8];
+    int levels = 0;
+    replay_tree_geometry(capacity, &floats, &levels, off);
+    if (floats_out) *floats_out = floats;
+    if (levels_out) *levels_out = levels;
+    if (offsets_out)
+        for (int l = 0; l < 8; ++l) offsets_out[l] = off[l];
+    return RSX_OK;
+}
+
+int rsx_replay_set_priorities(float* tree_dev, void* state_dev, int64_t capacity, const int32_t* rows_dev, const float* td_error_dev,
+                              const int64_t* head_dev, int64_t m, float alpha, float eps, void* stream) {
+    (void)launch_status();
+    if (!tree_dev || !state_dev) return fail(RSX_ERR_ARG, "tree_dev and state_dev must not be null");
+    if (!rows_dev && !head_dev) return fail(RSX_ERR_ARG, "rows_dev and head_dev must not both be null");
+    if (capacity < 1 || capacity > 0x7FFFFFFFll) return fail(RSX_ERR_ARG, "capacity must be in 1 .. 2^31 - 1");
+    if (m < 1 || m > 0x7FFFFFFFll) return fail(RSX_ERR_ARG, "m (the entries) must be in 1 .. 2^31 - 1");
+    if (!rows_dev && m > capacity) return fail(RSX_ERR_ARG, "m must not exceed the capacity when the rows are those behind the write head");
+    if (!(std::isfinite(alpha) && alpha >= 0.0f)) return fail(RSX_ERR_ARG, "alpha must be finite and >= 0");
+    if (!(std::isfinite(eps) && eps >= 0.0f)) return fail(RSX_ERR_ARG, "eps must be finite and >= 0");
+    launch_replay_set_priorities(tree_dev, state_dev, capacity, rows_dev, td_error_dev, reinterpret_cast<const long long*>(head_dev), m, alpha,
+                                 eps, (hipStream_t)stream);
+    HIP_TRY(launch_status());
+    return RSX_OK;
+}
+
+int rsx_replay_sample_prioritized(const float* tree_dev, void* state_dev, int64_t capacity, int64_t fill, const int64_t* fill_dev,
+                                  int32_t* rows_out, float* weights_out, int64_t m, float beta, const float* beta_dev, uint64_t seed,
+                                  int64_t step, const int64_t* step_dev, void* stream) {
+    (void)launch_status();
+    if (!tree_dev || !state_dev || !rows_out || !weights_out)
+        return fail(RSX_ERR_ARG, "tree_dev, state_dev, rows_out and weights_out must not be null");
+    if (int rc = sample_rows_check(m, capacity, fill, fill_dev)) return rc;
+    if (!beta_dev && !(std::isfinite(beta) && beta >= 0.0f)) return fail(RSX_ERR_ARG, "beta must be finite and >= 0");
+    HIP_TRY(launch_replay_sample_prioritized(tree_dev, state_dev, capacity, fill, reinterpret_cast<const long long*>(fill_dev), rows_out,
+                                             weights_out, m, beta, beta_dev, seed, step, reinterpret_cast<const long long*>(step_dev),
+                                             (hipStream_t)stream));
     HIP_TRY(launch_status());
     return RSX_OK;
 }

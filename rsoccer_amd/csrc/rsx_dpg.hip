@@ -56,6 +56,8 @@ struct DpgArgs {
     int stride, OD, AD, C;
     int wide, wide_next;         // OD % 4 == 0 and the array 16-byte aligned: rows are read four floats at a time
     float gamma, sigma, noise_clip, inv_m;
+    const float* discount;       // [N] or nullptr: the row's own discount in place of gamma (rsx_grad_per)
+    const float* weight;         // [M] or nullptr: the entry's weight on the critic loss
 };
 
 // LDS of the three row kernels, in floats
@@ -167,7 +169,8 @@ __global__ __launch_bounds__(64) void dpg_target_kernel(const DpgArgs G) {
         }
         if (e.in_m) {
             const float r = G.reward[e.idx];
-            const float y = G.terminated[e.idx] != 0 ? r : r + G.gamma * qmin;
+            const float gm = G.discount != nullptr ? G.discount[e.idx] : G.gamma;
+            const float y = G.terminated[e.idx] != 0 ? r : r + gm * qmin;
             G.y[e.t] = e.live ? y : 0.0f;
             G.absa[e.t] = e.live ? absa : 0.0f;
             if (G.out_target != nullptr) G.out_target[e.t] = e.live ? y : 0.0f;
@@ -209,9 +212,10 @@ __global__ __launch_bounds__(64) void dpg_critic_kernel(const DpgArgs G) {
         if (G.out_q != nullptr && e.in_m) G.out_q[(size_t)c * (size_t)G.M + (size_t)e.t] = e.live ? q : 0.0f;
         const float y = e.in_m ? G.y[e.t] : 0.0f;
         const float diff = q - y;
-        O[lane] = e.live ? diff * G.inv_m : 0.0f;
+        const float w = G.weight != nullptr && e.in_m ? G.weight[e.t] : 1.0f;   // (times 1.0f is exact: the plain call's bits)
+        O[lane] = e.live ? (diff * w) * G.inv_m : 0.0f;
         if (e.live) {
-            st0 += diff * diff;
+            st0 += (w * diff) * diff;
             st1 += q;
             st2 += y;
             st3 += G.absa[e.t];
@@ -377,7 +381,7 @@ long long dpg_workspace_bytes(const long long n_params_actor, const long long n_
 void launch_dpg_gradient(const PolicySpec& actor, const long long n_params_actor, const float* actor_params, const float* target_actor_params,
                          const PolicySpec& critic, const long long n_params_critic, const float* critic_params,
                          const float* target_critic_params, const int obs_dim, const int act_dim, const rsx_dpg_in& in, const rsx_dpg_cfg& cfg,
-                         const rsx_dpg_out& out, hipStream_t s) {
+                         const rsx_dpg_out& out, hipStream_t s, const rsx_grad_per* per) {
     const int C = cfg.n_critics;
     const int grid = dpg_grid(in.n_rows, cfg.max_workgroups);
     const int stride_c = stride_of(n_params_critic), stride_a = stride_of(n_params_actor);
@@ -397,6 +401,7 @@ void launch_dpg_gradient(const PolicySpec& actor, const long long n_params_actor
     G.OD = obs_dim; G.AD = act_dim; G.C = C;
     G.wide = wide(in.obs); G.wide_next = wide(in.next_obs);
     G.gamma = cfg.gamma; G.sigma = cfg.sigma; G.noise_clip = cfg.noise_clip; G.inv_m = inv_m;
+    if (per != nullptr) { G.discount = per->discount; G.weight = per->weight; }
     const Net net_a{actor_params, (int)n_params_actor, actor.layers, actor.hidden_act, actor.out_act};
     const Net net_c{critic_params, (int)n_params_critic, critic.layers, critic.hidden_act, critic.out_act};
     const int ha = actor.hidden, hc = critic.hidden;

@@ -72,6 +72,8 @@ struct SacArgs {
     int stride, OD, AD, C;
     int wide, wide_next;         // OD % 4 == 0 and the array 16-byte aligned: rows are read four floats at a time
     float gamma, target_entropy, ls_min, ls_max, inv_m;
+    const float* discount;       // [N] or nullptr: the row's own discount in place of gamma (rsx_grad_per)
+    const float* weight;         // [M] or nullptr: the entry's weight on the critic loss
 };
 
 // LDS of the row kernels, in floats
@@ -196,7 +198,8 @@ __global__ __launch_bounds__(64) void sac_target_kernel(const SacArgs G) {
         }
         if (e.in_m) {
             const float r = G.reward[e.idx];
-            const float y = G.terminated[e.idx] != 0 ? r : r + G.gamma * (qmin - alpha * logp);
+            const float gm = G.discount != nullptr ? G.discount[e.idx] : G.gamma;
+            const float y = G.terminated[e.idx] != 0 ? r : r + gm * (qmin - alpha * logp);
             G.y[e.t] = e.live ? y : 0.0f;
             G.nlogp[e.t] = e.live ? logp : 0.0f;
             if (G.out_target != nullptr) G.out_target[e.t] = e.live ? y : 0.0f;
@@ -239,9 +242,10 @@ __global__ __launch_bounds__(64) void sac_critic_kernel(const SacArgs G) {
         if (G.out_q != nullptr && e.in_m) G.out_q[(size_t)c * (size_t)G.M + (size_t)e.t] = e.live ? q : 0.0f;
         const float y = e.in_m ? G.y[e.t] : 0.0f;
         const float diff = q - y;
-        O[lane] = e.live ? diff * G.inv_m : 0.0f;
+        const float w = G.weight != nullptr && e.in_m ? G.weight[e.t] : 1.0f;   // (times 1.0f is exact: the plain call's bits)
+        O[lane] = e.live ? (diff * w) * G.inv_m : 0.0f;
         if (e.live) {
-            st0 += diff * diff;
+            st0 += (w * diff) * diff;
             st1 += q;
             st2 += y;
             st3 += G.nlogp[e.t];
@@ -488,7 +492,7 @@ long long sac_workspace_bytes(const long long n_params_actor, const long long n_
 void launch_sac_gradient(const PolicySpec& actor, const long long n_params_actor, const float* actor_params, const PolicySpec& critic,
                          const long long n_params_critic, const float* critic_params, const float* target_critic_params,
                          const float* log_alpha, const int obs_dim, const int act_dim, const rsx_dpg_in& in, const rsx_sac_cfg& cfg,
-                         const rsx_sac_out& out, hipStream_t s) {
+                         const rsx_sac_out& out, hipStream_t s, const rsx_grad_per* per) {
     const int C = cfg.n_critics;
     const int grid = sac_grid(in.n_rows, cfg.max_workgroups);
     const int stride_c = sac_stride_of(n_params_critic), stride_a = sac_stride_of(n_params_actor);
@@ -506,6 +510,7 @@ void launch_sac_gradient(const PolicySpec& actor, const long long n_params_actor
     SacArgs G{};
     G.obs = in.obs; G.action = in.action; G.reward = in.reward; G.next_obs = in.next_obs; G.terminated = in.terminated; G.rows = in.rows;
     G.log_alpha = log_alpha;
+    if (per != nullptr) { G.discount = per->discount; G.weight = per->weight; }
     G.y = y; G.nlogp = nlogp; G.logp = logp; G.at = at; G.qa = qa; G.dqda = dqda;
     G.out_target = out.target; G.out_q = out.q; G.out_action = out.action; G.out_logp = out.log_prob; G.out_nlogp = out.next_log_prob;
     G.out_eps = out.eps; G.out_neps = out.next_eps; G.out_mean = out.mean; G.out_ls = out.log_std;

@@ -32,6 +32,9 @@ struct rsx_sac_update_cfg;
 struct rsx_sac_adam_cfg;
 struct rsx_sac_adam_state;
 struct rsx_sac_adam_io;
+struct rsx_replay_batch;
+struct rsx_replay_ring;
+struct rsx_grad_per;
 
 namespace rsx {
 
@@ -194,7 +197,8 @@ long long dpg_lds_bytes(int launch, int obs_dim, int act_dim, const PolicySpec& 
 long long dpg_workspace_bytes(long long n_params_actor, long long n_params_critic, int n_critics, long long n_rows, int max_workgroups);
 void launch_dpg_gradient(const PolicySpec& actor, long long n_params_actor, const float* actor_params, const float* target_actor_params,
                          const PolicySpec& critic, long long n_params_critic, const float* critic_params, const float* target_critic_params,
-                         int obs_dim, int act_dim, const rsx_dpg_in& in, const rsx_dpg_cfg& cfg, const rsx_dpg_out& out, hipStream_t s);
+                         int obs_dim, int act_dim, const rsx_dpg_in& in, const rsx_dpg_cfg& cfg, const rsx_dpg_out& out, hipStream_t s,
+                         const rsx_grad_per* per = nullptr);
 // rsx_sac.hip: gradients of the soft actor-critic losses with respect to an MLP actor with a squashed Gaussian head (an output layer of
 // 2 * act_dim units), n_critics critics on [obs | action] and the log-temperature (rsx_task_sac_gradient).  The arguments as for
 // launch_dpg_gradient (no target actor; log_alpha: [1] on the device); in / cfg / out checked.  Six launches: the targets, the critics
@@ -206,7 +210,8 @@ long long sac_lds_bytes(int launch, int obs_dim, int act_dim, const PolicySpec& 
 long long sac_workspace_bytes(long long n_params_actor, long long n_params_critic, int n_critics, long long n_rows, int max_workgroups);
 void launch_sac_gradient(const PolicySpec& actor, long long n_params_actor, const float* actor_params, const PolicySpec& critic,
                          long long n_params_critic, const float* critic_params, const float* target_critic_params, const float* log_alpha,
-                         int obs_dim, int act_dim, const rsx_dpg_in& in, const rsx_sac_cfg& cfg, const rsx_sac_out& out, hipStream_t s);
+                         int obs_dim, int act_dim, const rsx_dpg_in& in, const rsx_sac_cfg& cfg, const rsx_sac_out& out, hipStream_t s,
+                         const rsx_grad_per* per = nullptr);
 // rsx_dpg_update.hip: the update phase around launch_dpg_gradient (rsx_replay_sample_rows, rsx_dpg_adam_step, rsx_task_dpg_update); every
 // argument checked by the caller.  One launch for the rows, two for the optimiser step (the norms of both groups, then Adam with the
 // Polyak step).  dpg_update_workspace_bytes: launch_dpg_update's workspace (rows_offset: where the int32 rows lie in it);
@@ -232,6 +237,19 @@ void launch_sac_update(const PolicySpec& actor, long long n_params_actor, float*
                        long long n_params_critic, float* critic_params, float* target_critic_params, float* log_alpha, int obs_dim,
                        int act_dim, const rsx_dpg_in& in, const rsx_sac_cfg& cfg, const rsx_sac_update_cfg& u, const rsx_sac_adam_cfg& adam,
                        const rsx_sac_adam_state& st, float* stats, void* workspace, hipStream_t s);
+// rsx_replay.hip: prioritised and n-step replay (rsx_replay_add_nstep, rsx_replay_tree_geometry, rsx_replay_set_priorities,
+// rsx_replay_sample_prioritized) and the TD error of the weighted gradient calls; every argument checked by the caller.  One launch for
+// the add; 2 + levels for the priorities (the leaves cleared, raised, then each level's touched nodes); a memset node and two launches
+// for the draw; one for the TD error (q: [n_critics][m]).  launch_replay_sample_prioritized returns the memset's status.  per (the two
+// gradient launches above): the rows' discounts and the entries' weights, or nullptr; its td_error is the caller's to fill
+void replay_tree_geometry(long long capacity, long long* floats, int* levels, long long* offsets);
+void launch_replay_add_nstep(const rsx_replay_batch& b, const rsx_replay_ring& r, int n_step, float gamma, hipStream_t s);
+void launch_replay_set_priorities(float* tree, void* state, long long capacity, const int32_t* rows, const float* td_error,
+                                  const long long* head_dev, long long m, float alpha, float eps, hipStream_t s);
+hipError_t launch_replay_sample_prioritized(const float* tree, void* state, long long capacity, long long fill, const long long* fill_dev,
+                                            int32_t* rows, float* weights, long long m, float beta, const float* beta_dev, uint64_t seed,
+                                            long long step, const long long* step_dev, hipStream_t s);
+void launch_replay_td_error(const float* q, const float* target, int n_critics, long long m, float* td_error, hipStream_t s);
 // rsx_render.hip: batched rgb frames (rsx_render_*).  render_check_view: nullptr when the view is valid (and the frame size), else the
 // message; render_field_host: the static field image [H][W][3]; RenderGeom: what the kernel needs of a view, in float32
 struct RenderGeom { int W, H; float s, cx, cy, r, rb; int square; };

@@ -828,7 +828,8 @@ class VecFusedEnv(RenderMixin):
 
     # ---- off-policy updates (include/rsx.h: rsx_task_dpg_gradient) ----
     def dpg_gradient(self, data, policy, params, target_params, critic, critic_params, target_critic_params, rows=None, gamma=0.99,
-                     target_noise=0.0, noise_clip=0.5, noise_seed=0, noise_step=0, actor=True, max_workgroups=None, return_rows=False):
+                     target_noise=0.0, noise_clip=0.5, noise_seed=0, noise_step=0, actor=True, max_workgroups=None, return_rows=False,
+                     weights=None, return_td_error=False):
         """Gradients of the TD3 / DDPG losses with respect to an MLP actor and its one or two Q critics on a minibatch of replayed
         transitions, in four launches (``rsx_task_dpg_gradient``): what an off-policy loop does per gradient step before
         ``opt.step()`` and the Polyak update.
@@ -848,7 +849,14 @@ class VecFusedEnv(RenderMixin):
         Returns fresh device tensors ``grad_params`` ``[P]`` (absent with ``actor=False``), ``grad_critic_params`` ``[C, Pc]`` and
         ``stats``: a dict of 0-d views (``_lib.DPG_STATS``; ``loss_pi`` absent with ``actor=False``; no synchronisation); with
         ``return_rows=True`` also ``target`` ``[M]``, ``q`` ``[C, M]``, ``target_noise`` ``[M, act_dim]`` and, with the actor,
-        ``action`` ``[M, act_dim]``.  Touches nothing of the env, never synchronises, capturable."""
+        ``action`` ``[M, act_dim]``.  Touches nothing of the env, never synchronises, capturable.
+
+        Prioritised and n-step replay (``rsx_task_dpg_gradient_w``): a ``data`` mapping that carries ``"discount"`` ``[N]`` (float32;
+        ``PrioritizedReplayBuffer.data()``) uses it per row in place of ``gamma`` in the target; ``gamma`` then only validates.
+        ``weights`` ``[M]`` (float32, by position in the minibatch: ``PrioritizedReplayBuffer.sample``'s) scale the critic loss only —
+        the actor's loss stays unweighted; a weight of exactly 1 leaves every bit alone.  ``return_td_error=True`` adds ``td_error``
+        ``[M]``, ``max_c |Q_c - y|`` per entry (0 for a skipped one), in one more launch: what ``update_priorities`` takes.  Without
+        these two arguments and without that key the call is the plain entry point's, as before."""
         torch = self._torch
         from rsoccer_amd.vec.policy import MLPCritic, MLPPolicy, MLPQCritic
         if not isinstance(policy, MLPPolicy) or isinstance(policy, (MLPCritic, MLPQCritic)):
@@ -928,6 +936,9 @@ class VecFusedEnv(RenderMixin):
             if not r.is_contiguous():
                 raise ValueError("rows must be contiguous")
             M = int(r.shape[0])
+        disc = need("data['discount']", data["discount"], (N,)) if "discount" in data else None
+        wts = need("weights", weights, (M,)) if weights is not None else None
+        with_per = disc is not None or wts is not None or bool(return_td_error)
         aspec, cspec = policy.spec(), critic.spec()
         f32 = dict(dtype=torch.float32, device=dev)
         # the workspace, cached per (shape, C, M, max_workgroups): calls on one stream are ordered, so they may share it
@@ -939,16 +950,21 @@ class VecFusedEnv(RenderMixin):
         ga = torch.empty((policy.num_params,), **f32) if actor else None
         gc = torch.empty((C, critic.num_params), **f32)
         stats = torch.empty((len(_lib.DPG_STATS),), **f32)
-        tgt = torch.empty((M,), **f32) if return_rows else None
-        q = torch.empty((C, M), **f32) if return_rows else None
+        tgt = torch.empty((M,), **f32) if return_rows or return_td_error else None   # (the TD error is computed from these two)
+        q = torch.empty((C, M), **f32) if return_rows or return_td_error else None
+        td = torch.empty((M,), **f32) if return_td_error else None
         pi = torch.empty((M, AD), **f32) if return_rows and actor else None
         nz = torch.empty((M, AD), **f32) if return_rows else None
         ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731  (a bool tensor is one byte per element, 0 or 1)
         inp = _lib.DpgIn(ptr(obs), ptr(act), ptr(rew), ptr(nxt), ptr(term), ptr(r), N, M)
         cfg = _lib.DpgCfg(step_ptr, int(noise_seed) & 0xFFFFFFFFFFFFFFFF, step, gamma, sigma, noise_clip, C, mw)
         out = _lib.DpgOut(ptr(ga), ptr(gc), ptr(stats), ptr(tgt), ptr(q), ptr(pi), ptr(nz), ptr(ws))
-        self.sim.task_dpg_gradient(aspec, ptr(p), ptr(tp), cspec, ptr(cp), ptr(tcp), inp, cfg, out, self._stream())
-        self._keep_dpg = (r, step_t, term)   # the call's own tensors: alive until the launches have consumed them
+        if with_per:
+            self.sim.task_dpg_gradient_w(aspec, ptr(p), ptr(tp), cspec, ptr(cp), ptr(tcp), inp, cfg, out,
+                                         _lib.GradPer(ptr(disc), ptr(wts), ptr(td)), self._stream())
+        else:
+            self.sim.task_dpg_gradient(aspec, ptr(p), ptr(tp), cspec, ptr(cp), ptr(tcp), inp, cfg, out, self._stream())
+        self._keep_dpg = (r, step_t, term, disc, wts, tgt, q)   # the call's own tensors: alive until the launches have consumed them
         res = {"grad_critic_params": gc,
                "stats": {name: stats[k] for k, name in enumerate(_lib.DPG_STATS) if actor or name != "loss_pi"}}
         if actor:
@@ -957,10 +973,13 @@ class VecFusedEnv(RenderMixin):
             res["target"], res["q"], res["target_noise"] = tgt, q, nz
             if actor:
                 res["action"] = pi
+        if return_td_error:
+            res["td_error"] = td
         return res
 
     def sac_gradient(self, data, policy, params, critic, critic_params, target_critic_params, log_alpha, rows=None, gamma=0.99,
-                     target_entropy=None, noise_seed=0, noise_step=0, max_workgroups=None, return_rows=False):
+                     target_entropy=None, noise_seed=0, noise_step=0, max_workgroups=None, return_rows=False, weights=None,
+                     return_td_error=False):
         """Gradients of the soft actor-critic losses with respect to an ``MLPGaussianPolicy`` actor, its one or two Q critics and the
         log-temperature on a minibatch of replayed transitions, in six launches (``rsx_task_sac_gradient``): what a SAC loop does per
         gradient step before its three optimiser steps and the Polyak update of the target critics.
@@ -976,7 +995,12 @@ class VecFusedEnv(RenderMixin):
         ``stats``: a dict of 0-d views (``_lib.SAC_STATS``; no synchronisation); with ``return_rows=True`` also ``target`` ``[M]``, ``q``
         ``[C, M]``, ``action`` ``[M, act_dim]`` (the sample on ``obs``), ``log_prob`` ``[M]``, ``next_log_prob`` ``[M]``, ``eps``,
         ``next_eps``, ``mean`` and ``log_std`` ``[M, act_dim]`` — zero for a skipped entry.  Touches nothing of the env, never
-        synchronises, capturable."""
+        synchronises, capturable.
+
+        Prioritised and n-step replay (``rsx_task_sac_gradient_w``): ``data["discount"]`` ``[N]``, ``weights`` ``[M]`` and
+        ``return_td_error`` are ``dpg_gradient``'s: a per-row discount in place of ``gamma`` in the target (``gamma`` then only
+        validates), a per-entry weight on the critic loss only (the actor's and the temperature's losses stay unweighted) and
+        ``td_error`` ``[M]``.  Without them the call is the plain entry point's, as before."""
         torch = self._torch
         from rsoccer_amd.vec.policy import MLPGaussianPolicy, MLPQCritic
         if not isinstance(policy, MLPGaussianPolicy):
@@ -1056,6 +1080,9 @@ class VecFusedEnv(RenderMixin):
             if not r.is_contiguous():
                 raise ValueError("rows must be contiguous")
             M = int(r.shape[0])
+        disc = need("data['discount']", data["discount"], (N,)) if "discount" in data else None
+        wts = need("weights", weights, (M,)) if weights is not None else None
+        with_per = disc is not None or wts is not None or bool(return_td_error)
         aspec, cspec = policy.spec(), critic.spec()
         f32 = dict(dtype=torch.float32, device=dev)
         # the workspace, cached per (shape, C, M, max_workgroups): calls on one stream are ordered, so they may share it
@@ -1073,17 +1100,25 @@ class VecFusedEnv(RenderMixin):
             per = {"target": (M,), "q": (C, M), "action": (M, AD), "log_prob": (M,), "next_log_prob": (M,), "eps": (M, AD),
                    "next_eps": (M, AD), "mean": (M, AD), "log_std": (M, AD)}
             per = {k: torch.empty(shape, **f32) for k, shape in per.items()}
+        td = torch.empty((M,), **f32) if return_td_error else None
+        own = per if return_rows or not return_td_error else {"target": torch.empty((M,), **f32), "q": torch.empty((C, M), **f32)}
         ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731  (a bool tensor is one byte per element, 0 or 1)
         inp = _lib.DpgIn(ptr(obs), ptr(act), ptr(rew), ptr(nxt), ptr(term), ptr(r), N, M)
         cfg = _lib.SacCfg(step_ptr, int(noise_seed) & 0xFFFFFFFFFFFFFFFF, step, gamma, te, policy.log_std_min, policy.log_std_max, C, mw)
         out = _lib.SacOut(ptr(ga), ptr(gc), ptr(gl), ptr(stats),
-                          *(ptr(per.get(k)) for k in ("target", "q", "action", "log_prob", "next_log_prob", "eps", "next_eps", "mean", "log_std")),
+                          *(ptr(own.get(k)) for k in ("target", "q", "action", "log_prob", "next_log_prob", "eps", "next_eps", "mean", "log_std")),
                           ptr(ws))
-        self.sim.task_sac_gradient(aspec, ptr(p), cspec, ptr(cp), ptr(tcp), ptr(la), inp, cfg, out, self._stream())
-        self._keep_sac = (r, step_t, term)   # the call's own tensors: alive until the launches have consumed them
+        if with_per:
+            self.sim.task_sac_gradient_w(aspec, ptr(p), cspec, ptr(cp), ptr(tcp), ptr(la), inp, cfg, out,
+                                         _lib.GradPer(ptr(disc), ptr(wts), ptr(td)), self._stream())
+        else:
+            self.sim.task_sac_gradient(aspec, ptr(p), cspec, ptr(cp), ptr(tcp), ptr(la), inp, cfg, out, self._stream())
+        self._keep_sac = (r, step_t, term, disc, wts, own)   # the call's own tensors: alive until the launches have consumed them
         res = {"grad_params": ga, "grad_critic_params": gc, "grad_log_alpha": gl,
                "stats": {name: stats[k] for k, name in enumerate(_lib.SAC_STATS)}}
         res.update(per)
+        if return_td_error:
+            res["td_error"] = td
         return res
 
     def dpg_update(self, buf, policy, params, target_params, critic, critic_params, target_critic_params, opt, grad_steps=8,
